@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- MikuDance denoising loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run does what the headline needs and nothing else: it builds the models, warms up W steps, times K steps and prints ONE JSON
+line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...).  --dump-outputs DIR writes what the
+timed path returned in its last step -- the final latents of every clip, gathered on rank 0 -- as DIR/latents.npy (float32; over 60 MB
+a fixed, seeded sample of its elements); inputs and weights are seeded, so two builds can be compared output for output.  --full adds
+every diagnostic below, each measured after the timed region.
 
 A "step" is one pass of the hot path over one batch of synthetic input: the full denoising loop (20 DDIM steps,
 reference_unet + denoising_unet + motion modules + CFG + DDIM) of ONE 768x768x16-frame clip per GPU (BASELINE.json
@@ -11,7 +17,8 @@ region starts: every rank stages its own clip (--scatter: rank 0 owns the batch 
 RCCL inside the region); the final latents are gathered on rank 0 inside the region.  value = frames of all ranks /
 max-over-ranks time.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of --full (beside executed_tflop_per_clip, kernel_families, top_launch_shapes, vae_ms_per_clip, e2e_frames_per_s, and the
+collectives of a multi-rank run timed on their own):
   roofline     dominant kernel: algorithmic FLOPs per launch / average launch duration measured live with HIP events on the
                launch stream, against the dense fp16 MFMA peak (2.5 PFLOP/s).  The events bracket every C-ABI launch of ONE extra
                pass of the same clip run right after the timed region (instrumenting ~17k launches per clip inside the timed
@@ -59,6 +66,47 @@ def emit_line(text):
     out.flush()
 
 
+def build_models_threaded(geom, device):
+    """(ref, den) of mikudance_amd.selftest.build_models(geom, device=device, keep_state_dicts=False), bit for bit (every weight is a pure
+    function of its key and seed, mikudance_amd.synth), with the per-tensor synthesis spread over the intra-op thread count: CPU randn is
+    serial per tensor, so the 2.2 G parameters one after another take over 10 s before the first step; ATen releases the GIL inside randn."""
+    from concurrent.futures import ThreadPoolExecutor
+    from mikudance_amd import UNet2DConditionModel, UNet3DConditionModel
+    from mikudance_amd.selftest import MM_KWARGS, SMALL
+    from mikudance_amd.synth import synth_tensors
+
+    def synth_one(key, shape, seed):
+        return key, next(synth_tensors({key: shape}, seed=seed))[1].half()
+    geom = dict(SMALL if geom is None else geom)
+    models = []
+    for cls, kw, seed in ((UNet2DConditionModel, {}, 4321), (UNet3DConditionModel, MM_KWARGS, 1234)):    # build_models' default seeds
+        with torch.device("meta"):
+            model = cls(sample_size=16, **geom, **kw)
+        shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+        with ThreadPoolExecutor(max(1, torch.get_num_threads())) as ex:
+            sd = dict(ex.map(synth_one, shapes, shapes.values(), [seed] * len(shapes)))
+        model.load_state_dict(sd, strict=True, assign=True)
+        del sd
+        models.append(model.to(device=device))
+    return models
+
+
+DUMP_BYTES = 60 * 2 ** 20            # --dump-outputs: float32 payload in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as <out_dir>/<name>.npy in float32.  Over DUMP_BYTES in all, every array keeps the same
+    fraction of its elements: a fixed sample of the flattened array (numpy default_rng(0), without replacement, in index order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, a.size * DUMP_BYTES // total, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -68,6 +116,9 @@ def main():
     ap.add_argument("--size", type=int, default=768)
     ap.add_argument("--ddim-steps", type=int, default=20)
     ap.add_argument("--guidance", type=float, default=3.5)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the final latents of the last timed step as DIR/latents.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure the diagnostics: per-launch timing pass (roofline, "
+                    "kernel families), PMC traffic, VAE, CPU baseline, the collectives of a multi-rank run; the --no-* flags below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the two rocprofv3 --pmc passes behind roofline.traffic (quote profiles/pmc_traffic.json)")
     ap.add_argument("--no-vae", action="store_true", help="skip the AutoencoderKL timing behind the extra keys vae_ms_per_clip / e2e_frames_per_s")
@@ -106,7 +157,7 @@ def main():
     from mikudance_amd.selftest import SCHED_KWARGS, build_models
     from mikudance_amd.synth import synth_inputs
 
-    rank, world = dp.init()
+    rank, world = dp.init("gloo" if args.dry_run_cpu else None)     # the dry run's tensors live on the CPU, also on a machine with GPUs
     try:
         _main_rank(args, rank, world, dp, _lib, DDIMScheduler, MikuDanceVideoPipeline, SCHED_KWARGS, build_models, synth_inputs)
     finally:
@@ -135,8 +186,12 @@ def _main_rank(args, rank, world, dp, _lib, DDIMScheduler, MikuDanceVideoPipelin
     geom = None if args.small else FULL
     ctx = (5, 64) if args.small else (257, 768)
     t0 = time.time()
-    want_cpu = world == 1 and not args.no_cpu_baseline and not dry
-    ref, den, ref_sd, den_sd = build_models(geom=geom, device=dev, keep_state_dicts=want_cpu)
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline and not dry
+    if want_cpu:                                                     # the CPU oracle is fed the fp32 state dicts
+        ref, den, ref_sd, den_sd = build_models(geom=geom, device=dev, keep_state_dicts=True)
+    else:
+        ref, den = build_models_threaded(geom, dev)
+        ref_sd = den_sd = None
     pipe = MikuDanceVideoPipeline(None, None, ref, den, DDIMScheduler(**SCHED_KWARGS))
     pipe.reference_reuse = not args.no_reuse
     pipe.share_first_layers = not args.no_share
@@ -187,13 +242,15 @@ def _main_rank(args, rank, world, dp, _lib, DDIMScheduler, MikuDanceVideoPipelin
     elapsed = time.perf_counter() - t0
     elapsed = dp.max_over_ranks(elapsed, dev)
     n_ranks_seen = int(round(dp.sum_over_ranks(1.0, dev)))          # every rank of the job reached the end of the timed region
+    if args.dump_outputs and rank == 0:                              # before the --full passes below reuse the pipeline
+        dump_outputs(args.dump_outputs, {"latents": torch.cat(list(res), 0)})
 
     # Diagnostics of a multi-rank run, all OUTSIDE the timed region (the first real 8-GPU run must be readable without a second lease):
     # who computed where (device UUID / PCI bus id per rank: N distinct GPUs, not LOCAL_RANK % device_count aliasing), each rank's own
-    # loop time, the collective library, and the scatter / gather of one batch timed on their own.
+    # loop time, the collective library, and (--full) the scatter / gather of one batch timed on their own.
     ident = dict(dp.device_identity(None if dry else dev), own_elapsed_s=own_elapsed, own_ms_per_step=own_elapsed / args.steps * 1e3)
     comm_ms = {}
-    if world > 1 or dp.active():                                     # dp.active(): a forced one-rank group (MD_DIST_FORCE=1) times them too
+    if args.full and (world > 1 or dp.active()):                     # dp.active(): a forced one-rank group (MD_DIST_FORCE=1) times them too
         for name, fn in (("gather_latents", lambda: dp.gather_latents(torch.zeros((1, 4, args.frames, h, w), device=dev, dtype=torch.float16))),
                          ("scatter_clips", (lambda: dp.scatter_clips(staged, dev)) if args.scatter else None),
                          ("window_all_reduce", (lambda: wp.reduce(torch.zeros((2, args.frames, h * w, 4), device=dev), torch.zeros((args.frames,), device=dev)))
@@ -213,7 +270,7 @@ def _main_rank(args, rank, world, dp, _lib, DDIMScheduler, MikuDanceVideoPipelin
     # per clip add launch gaps that would otherwise be charged to `value` (see "instrumented_ms_per_step" next to "ms_per_step").
     inst_steps = 1
     inst_elapsed = 0.0
-    if rank == 0 and not dry:
+    if args.full and rank == 0 and not dry:
         clip0 = staged[0] if args.scatter else staged
         # the two clip-halves run as two kernel queues (pipe.two_queues): for THIS pass queue 1 waits for queue 0 -- the same launches, one at a
         # time -- so that a launch's HIP events time that launch alone (side by side they would time whatever the other queue squeezed in)
@@ -245,7 +302,48 @@ def _main_rank(args, rank, world, dp, _lib, DDIMScheduler, MikuDanceVideoPipelin
                           "config": {"workload": "dry-run", "parallelism": f"dp{world}", "input_staging": "scatter" if args.scatter else "rank-local"},
                           "clips_gathered": len(res), "clip_means": [float(r.float().mean()) for r in res], "multi_gpu": multi}))
         return
-    prof = _lib.PROFILER.summary()
+    peak_gb = torch.cuda.max_memory_allocated(dev) / 2 ** 30
+    frames_total = args.frames * args.steps * (1 if wp else world)   # window-parallel: ONE clip, whatever the rank count (strong scaling)
+    value = frames_total / elapsed
+    line = {
+        "metric": f"frames/sec ({args.size}x{args.size}, {args.frames}f, {args.ddim_steps} DDIM steps)", "value": value, "unit": "frames/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "strong" if wp else "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic", "n_ranks_seen": n_ranks_seen,
+        "config": {"workload": f"configs[{args.config}]: {args.size}x{args.size}, {args.frames}-frame clip, {args.ddim_steps} DDIM steps, fp16, "
+                               "reference_unet + denoising_unet + motion_module, CFG 3.5, one clip per GPU per step"
+                               + (", full guidance: scene-motion flow from the demo camera tracks (tests/golden/g2) through "
+                                  "camera_to_scene_motion + non-zero face/hand latents" if args.config == 2 else "")
+                               + (", context 30 / overlap 8 -> 3 wrapping windows, 60-frame UNet batches" if args.config == 4 else ""),
+                   "parallelism": (f"wp{world}" if wp else f"dp{world}"), "input_staging": "scatter from rank 0 inside the timed region" if args.scatter
+                   else "rank-local (every rank stages its own clip in HBM before the timed region)", "reference_reuse": pipe.reference_reuse,
+                   "queues": "2 (unconditional | conditional half of the denoising UNet side by side)" if pipe.two_queues and pipe.share_first_layers and args.guidance > 1 else "1",
+                   "weights": "random-init SD-1.5 geometry "
+                   "(N(0,1/fan_in), seeds 1234/4321)", "width": "reduced(debug)" if args.small else "full"},
+        "peak_hbm_gb": peak_gb, "setup_s": setup_s, "multi_gpu": multi,
+    }
+    if args.full:
+        line.update(launch_figures(_lib.PROFILER.summary(), inst_steps, inst_elapsed, elapsed, args, world, dev))
+    if args.full and world == 1 and not args.small and not args.no_vae:
+        # SURVEY 8d reports the VAE beside the headline, never inside it: 3F + 2 encodes and F decodes per clip (the calls of
+        # src/pipelines/pipeline_mikudance.py:456-549 and :115-130), batches of 8 images as the product pipeline issues them
+        del ref, den, pipe
+        torch.cuda.empty_cache()
+        vae = vae_ms_per_clip(dev, args.size, args.frames)
+        # the loop's time is the same for configs[1] and configs[2] (same shapes); the VAE's is not: absent face / hand guidance is 2F copies
+        # of one black frame, encoded once
+        mine = "configs[2]" if args.config == 2 else "configs[1]"
+        line["vae_ms_per_clip"] = vae[mine]["ms"]
+        line["vae_by_config"] = vae
+        line["e2e_frames_per_s"] = args.frames / (elapsed / args.steps + vae[mine]["ms"] * 1e-3)
+        line["e2e_frames_per_s_by_config"] = {k: args.frames / (elapsed / args.steps + v["ms"] * 1e-3) for k, v in vae.items()}
+    if want_cpu:
+        line["cpu_baseline"] = cpu_baseline(ref_sd, den_sd, args, ctx)
+    emit_line(json.dumps(line))
+
+
+def launch_figures(prof, inst_steps, inst_elapsed, elapsed, args, world, dev):
+    """--full: the figures of the per-launch HIP-event pass (`prof` = _lib.PROFILER.summary() over `inst_steps` clips): executed FLOPs,
+    kernel families, the dominant kernel's roofline with its HBM traffic, the top launch shapes (MD_BENCH_DUMP=<file>: all of them)."""
     total_flops = sum(d["flops"] for d in prof.values()) / inst_steps
     kernel_ms = sum(d["ms"] for d in prof.values()) / inst_steps
 
@@ -285,25 +383,9 @@ def _main_rank(args, rank, world, dp, _lib, DDIMScheduler, MikuDanceVideoPipelin
                                           "method": rec.get("method", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, "
                                                                       "FETCH_SIZE x2 (gfx950 correction, MI355X guide HBM section)")}
 
-    peak_gb = torch.cuda.max_memory_allocated(dev) / 2 ** 30
-    frames_total = args.frames * args.steps * (1 if wp else world)   # window-parallel: ONE clip, whatever the rank count (strong scaling)
-    value = frames_total / elapsed
     line = {
-        "metric": f"frames/sec ({args.size}x{args.size}, {args.frames}f, {args.ddim_steps} DDIM steps)", "value": value, "unit": "frames/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "strong" if wp else "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic", "n_ranks_seen": n_ranks_seen,
-        "config": {"workload": f"configs[{args.config}]: {args.size}x{args.size}, {args.frames}-frame clip, {args.ddim_steps} DDIM steps, fp16, "
-                               "reference_unet + denoising_unet + motion_module, CFG 3.5, one clip per GPU per step"
-                               + (", full guidance: scene-motion flow from the demo camera tracks (tests/golden/g2) through "
-                                  "camera_to_scene_motion + non-zero face/hand latents" if args.config == 2 else "")
-                               + (", context 30 / overlap 8 -> 3 wrapping windows, 60-frame UNet batches" if args.config == 4 else ""),
-                   "parallelism": (f"wp{world}" if wp else f"dp{world}"), "input_staging": "scatter from rank 0 inside the timed region" if args.scatter
-                   else "rank-local (every rank stages its own clip in HBM before the timed region)", "reference_reuse": pipe.reference_reuse,
-                   "queues": "2 (unconditional | conditional half of the denoising UNet side by side)" if pipe.two_queues and pipe.share_first_layers and args.guidance > 1 else "1",
-                   "weights": "random-init SD-1.5 geometry "
-                   "(N(0,1/fan_in), seeds 1234/4321)", "width": "reduced(debug)" if args.small else "full"},
         "executed_tflop_per_clip": total_flops / 1e12, "mfma_frac_whole_loop": total_flops / (elapsed / args.steps) / PEAK_MFMA_F16,
-        "peak_hbm_gb": peak_gb, "kernel_ms_per_clip": kernel_ms, "instrumented_ms_per_step": inst_elapsed / inst_steps * 1e3, "setup_s": setup_s,
+        "kernel_ms_per_clip": kernel_ms, "instrumented_ms_per_step": inst_elapsed / inst_steps * 1e3,
         # tflops for the contraction kernels; gbps = algorithmic bytes (inputs + outputs once) / time for every family: it is THE
         # figure for the HBM-class ones (norms, temporal attention whose f x f core is 4 bytes per 2 f MACs, the skinny GEMMs)
         "kernel_families": {k: dict(ms_per_clip=v["ms"] / inst_steps,
@@ -311,7 +393,6 @@ def _main_rank(args, rank, world, dp, _lib, DDIMScheduler, MikuDanceVideoPipelin
                                     gbps=v["bytes"] / (v["ms"] * 1e-3) / 1e9,
                                     launches=v["count"] // inst_steps) for k, v in sorted(fam.items(), key=lambda kv: -kv[1]["ms"])},
         "roofline": roofline,
-        "multi_gpu": multi,
     }
     top = sorted(prof.items(), key=lambda kv: -kv[1]["ms"])[:16]
     line["top_launch_shapes"] = [dict(label=k, ms_per_clip=v["ms"] / inst_steps, launches=v["count"] // inst_steps,
@@ -323,22 +404,7 @@ def _main_rank(args, rank, world, dp, _lib, DDIMScheduler, MikuDanceVideoPipelin
                 fh.write(f"{v['ms'] / inst_steps:10.3f} ms/clip  {v['count'] // inst_steps:6d} launches  "
                          f"{(v['flops'] / (v['ms'] * 1e-3) / 1e12) if v['flops'] else 0:8.1f} TF  "
                          f"{v['bytes'] / (v['ms'] * 1e-3) / 1e9:8.1f} GB/s  {k}\n")
-    if world == 1 and not args.small and not args.no_vae:
-        # SURVEY 8d reports the VAE beside the headline, never inside it: 3F + 2 encodes and F decodes per clip (the calls of
-        # src/pipelines/pipeline_mikudance.py:456-549 and :115-130), batches of 8 images as the product pipeline issues them
-        del ref, den, pipe
-        torch.cuda.empty_cache()
-        vae = vae_ms_per_clip(dev, args.size, args.frames)
-        # the loop's time is the same for configs[1] and configs[2] (same shapes); the VAE's is not: absent face / hand guidance is 2F copies
-        # of one black frame, encoded once
-        mine = "configs[2]" if args.config == 2 else "configs[1]"
-        line["vae_ms_per_clip"] = vae[mine]["ms"]
-        line["vae_by_config"] = vae
-        line["e2e_frames_per_s"] = args.frames / (elapsed / args.steps + vae[mine]["ms"] * 1e-3)
-        line["e2e_frames_per_s_by_config"] = {k: args.frames / (elapsed / args.steps + v["ms"] * 1e-3) for k, v in vae.items()}
-    if world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(ref_sd, den_sd, args, ctx)
-    emit_line(json.dumps(line))
+    return line
 
 
 def measure_traffic(label, device_index=0):

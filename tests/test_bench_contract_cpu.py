@@ -111,13 +111,13 @@ def test_two_rank_launch_protocol_under_gloo():
     """bench.py exactly as the driver launches it for N = 2 (python -m torch.distributed.run ... bench.py --gpus 2 ...), on CPU
     with the gloo backend and the kernels replaced by a stand-in (--dry-run-cpu): rendezvous, rank-local staging AND the
     --scatter variant, barrier / max-over-ranks timing, gather on rank 0, ONE JSON line from rank 0 only, every rank exits 0
-    through destroy_process_group()."""
+    through destroy_process_group(); --full adds the collectives timed on their own."""
     import socket
     for extra in ([], ["--scatter"]):
         s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--small",
-               "--dry-run-cpu", "--size", "128", "--frames", "4", "--ddim-steps", "2"] + extra
+               "--dry-run-cpu", "--size", "128", "--frames", "4", "--ddim-steps", "2", "--full"] + extra
         # MD_BENCH_TEST_BANNER: every rank printf()s a line to the C-level stdout the way RCCL does when its first communicator comes up (seen on
         # MI355X: five lines that reach the file AFTER the JSON line, at exit); stdout must still hold the line and nothing else
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="2", MD_BENCH_TEST_BANNER="1"))
@@ -157,6 +157,7 @@ def test_eight_rank_launch_protocol_under_gloo():
     assert d["n_gpus"] == 8 and d["n_ranks_seen"] == 8 and d["clips_gathered"] == 8 and d["config"]["parallelism"] == "dp8"
     assert len(set(d["clip_means"])) == 8                               # eight different clips (seeds 100 .. 107) came back
     assert [r["local_rank"] for r in d["multi_gpu"]["per_rank"]] == list(range(8))
+    assert d["multi_gpu"]["comm_ms_outside_timed_region"] == {}          # timing the collectives on their own is --full's work
 
 
 def test_cpu_quota_parsing(tmp_path):
@@ -224,3 +225,52 @@ def test_round6_line_carries_the_diagnostics_the_first_multi_gpu_run_needs():
     assert lin["within_10_percent"] == (abs(lin["ratio_to_linear"] - 1) <= 0.10)
     want = (1.0 / (lin["s_per_step_1_frame"] * 20)) if lin["within_10_percent"] else (4.0 / (lin["s_per_step_4_frames"] * 20))
     assert math.isclose(c["value"], want, rel_tol=2e-2) and c["cores"] == c["usable_cores"] and c["value"] < d["value"]
+
+
+def test_dump_outputs_writes_the_same_latents_every_run(tmp_path):
+    """--dump-outputs DIR: the final latents of the last timed step as DIR/latents.npy in float32, identical from run to run (seeded inputs),
+    after exactly --steps timed steps."""
+    import numpy as np
+    got = []
+    for i in range(2):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--small", "--dry-run-cpu", "--size", "128",
+               "--frames", "4", "--ddim-steps", "2", "--dump-outputs", str(tmp_path / f"run{i}")]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="2"))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and "cpu_baseline" not in d and "roofline" not in d
+        assert os.listdir(tmp_path / f"run{i}") == ["latents.npy"]
+        got.append(np.load(tmp_path / f"run{i}" / "latents.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (1, 4, 4, 16, 16) and np.array_equal(got[0], got[1])
+    assert math.isclose(float(got[0].mean()), json.loads(r.stdout.strip().splitlines()[-1])["clip_means"][0], rel_tol=1e-6)
+
+
+def test_dump_outputs_samples_a_large_output_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    x = torch.arange(3000, dtype=torch.float32).reshape(3, 1000)
+    y = torch.randn(2, 500, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "y": y})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float32 and a.size == 3000 * 4096 // (4000 * 4) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.all(np.isin(a, x.float().numpy()))           # distinct elements, in index order
+    assert np.load(tmp_path / "a" / "y.npy").size == 1000 * 4096 // (4000 * 4)
+    bench.dump_outputs(str(tmp_path / "c"), {"y": y})                                   # within the bound: the whole array
+    assert np.array_equal(np.load(tmp_path / "c" / "y.npy"), y.float().numpy())
+
+
+def test_threaded_weight_build_is_build_models_bit_for_bit():
+    """The plain run builds its weights on a thread pool (bench.build_models_threaded): the same tensors as selftest.build_models."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from mikudance_amd.selftest import build_models
+    fast = bench.build_models_threaded(None, "cpu")
+    ref, den, _, _ = build_models(device="cpu", keep_state_dicts=True)
+    for a, b in zip(fast, (ref, den)):
+        sa, sb = a.state_dict(), b.state_dict()
+        assert list(sa) == list(sb) and all(sa[k].dtype == torch.float16 and torch.equal(sa[k], sb[k]) for k in sb)

@@ -98,10 +98,11 @@ def test_read_frames_other_containers(tmp_path):
 
 
 def test_convert_video_to_natively_readable_forms(tmp_path):
-    """The one-time conversion for clips whose codec needs an external decoder (the reference's demo poses are H.264): gif -> frames
+    """The one-time conversion for clips whose codec needs an external decoder (the reference's demo poses are MPEG-4 video): gif -> frames
     directory and -> Motion-JPEG mp4, both read back by the native reader; the command-line form; and the reference's own demo clip
-    answers with the conversion hint on a box without a decoder (nothing in this image decodes H.264, so the demo clip itself cannot be
-    shipped as a fixture: INTEGRATION.md gives the command)."""
+    answers with the conversion hint where no decoder is installed.  The clip is stored as its container boxes alone
+    (tests/golden/pose_demo1_moov.mp4: ftyp + moov of demo_samples/poses/pose-demo1.mp4, 1.9 kB; the 2.2 MB of coded samples are left
+    out): the reader decides from the sample description, so the hint comes before any sample is read.  INTEGRATION.md gives the command."""
     import subprocess
     import sys
     frames = _frames(5)
@@ -115,13 +116,13 @@ def test_convert_video_to_natively_readable_forms(tmp_path):
     r = subprocess.run([sys.executable, "-m", "mikudance_amd.io_utils", "convert", str(tmp_path / "v.gif"), str(tmp_path / "cli")], cwd=root,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "5 frames" in r.stdout and len(os.listdir(tmp_path / "cli")) == 5
-    demo = "/root/reference/demo_samples/poses/pose-demo1.mp4"          # only in the build container; skipped on the GPU box
-    if os.path.exists(demo):
-        try:
-            n = len(U.read_frames(demo))                                  # a decoder happens to be installed: fine
-            assert n > 0
-        except RuntimeError as e:
-            assert "mikudance_amd.io_utils convert" in str(e)
+    demo = os.path.join(root, "tests", "golden", "pose_demo1_moov.mp4")
+    codec, samples, fps = U._mp4_index(open(demo, "rb").read())
+    assert codec == b"mp4v" and len(samples) == 232 and fps == 30 and U.get_fps(demo) == 30
+    import importlib.util
+    if not any(importlib.util.find_spec(m) for m in ("av", "cv2", "imageio")):     # with a decoder installed the full clip would decode
+        with pytest.raises(RuntimeError, match="mikudance_amd.io_utils convert"):
+            U.read_frames(demo)
 
 
 def _mp4(tmp_path, frames):

@@ -9,9 +9,9 @@ cd $R
 cp mikudance_amd/libmdance_hip.so /tmp/lib_keep_ab.so
 timeout 300 python tools/sp_trace.py > $O/sp_trace.log 2>&1; echo "trace rc=$?"; tail -4 $O/sp_trace.log
 cp /tmp/lib_keep_ab.so mikudance_amd/libmdance_hip.so
-MD_BENCH_DUMP=$O/shapes_all.txt timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_cfg1.json 2> $O/bench_cfg1.err; echo "cfg1 rc=$?"
-timeout 600 python bench.py --config 2 --steps 2 --warmup 1 --no-cpu-baseline --no-vae > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "cfg2 rc=$?"
-timeout 900 python bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-vae > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"
+MD_BENCH_DUMP=$O/shapes_all.txt timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_cfg1.json 2> $O/bench_cfg1.err; echo "cfg1 rc=$?"
+timeout 600 python bench.py --full --config 2 --steps 2 --warmup 1 --no-cpu-baseline --no-vae > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "cfg2 rc=$?"
+timeout 900 python bench.py --full --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-vae > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"
 python - <<PY
 import json
 for f in ("bench_cfg1.json","bench_cfg2.json","bench_cfg4.json"):
@@ -20,7 +20,7 @@ for f in ("bench_cfg1.json","bench_cfg2.json","bench_cfg4.json"):
     except Exception as e: print(f, "ERR", e)
 PY
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-vae > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-vae > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
 cd $R
 DB=$(ls $O/prof/*results.db 2>/dev/null | head -1)
 [ -n "$DB" ] && python profiles/summarize_rocprof.py $DB $O/kernel_stats.md $O/prof_bench.json > /dev/null

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/${1:-final}; mkdir -p $O
 bash tools/r04_suite.sh ${1:-final} | tail -8
-SECONDS=0; timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$? wall ${SECONDS}s" | tee $O/bench.time
+SECONDS=0; timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$? wall ${SECONDS}s" | tee $O/bench.time
 python - <<PY
 import json
 d=json.load(open("$O/bench.json"))

@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-.}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-MD_BENCH_DUMP=$O/shapes_all.txt timeout 1500 python bench.py > $O/bench_cfg1.json 2> $O/bench_cfg1.err; echo "cfg1 rc=$?"
-timeout 600 python bench.py --config 2 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "cfg2 rc=$?"
-MD_BENCH_DUMP=$O/shapes_cfg4.txt timeout 900 python bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"
+MD_BENCH_DUMP=$O/shapes_all.txt timeout 1500 python bench.py --full > $O/bench_cfg1.json 2> $O/bench_cfg1.err; echo "cfg1 rc=$?"
+timeout 600 python bench.py --full --config 2 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "cfg2 rc=$?"
+MD_BENCH_DUMP=$O/shapes_cfg4.txt timeout 900 python bench.py --full --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"
 python - <<PY
 import json
 for f in ("bench_cfg1.json","bench_cfg2.json","bench_cfg4.json"):
@@ -20,7 +20,7 @@ PY
 timeout 900 python tests/e2e_parity.py --config4 --out $O/e2e_parity_cfg4.json > $O/e2e_parity_cfg4.log 2>&1; echo "e2e cfg4 rc=$?"; grep -v "^{" $O/e2e_parity_cfg4.log | tail -4
 MD_VAE_DUMP=$O/vae_shapes.txt timeout 600 python tools/bench_vae.py > $O/vae.json 2> $O/vae.err; echo "vae rc=$?"; cat $O/vae.json
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
 cd $R
 DB=$(ls $O/prof/*results.db 2>/dev/null | head -1)
 [ -n "$DB" ] && python profiles/summarize_rocprof.py $DB $O/kernel_stats.md $O/prof_bench.json > /dev/null

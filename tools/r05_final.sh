@@ -9,9 +9,9 @@ mkdir -p $O
 cd $R
 SECONDS=0; timeout 1200 python -m pytest tests/ -x -q -m gpu --durations=15 > $O/pytest.log 2>&1; RC=$?; echo "pytest rc=$RC wall ${SECONDS}s" | tee $O/pytest.time; tail -22 $O/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.log
-SECONDS=0; MD_BENCH_DUMP=$O/shapes_all.txt timeout 1200 python bench.py > $O/bench_cfg1.json 2> $O/bench_cfg1.err; echo "cfg1 rc=$? wall ${SECONDS}s"
-timeout 500 python bench.py --config 2 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "cfg2 rc=$?"
-MD_BENCH_DUMP=$O/shapes_cfg4.txt timeout 800 python bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"
+SECONDS=0; MD_BENCH_DUMP=$O/shapes_all.txt timeout 1200 python bench.py --full > $O/bench_cfg1.json 2> $O/bench_cfg1.err; echo "cfg1 rc=$? wall ${SECONDS}s"
+timeout 500 python bench.py --full --config 2 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "cfg2 rc=$?"
+MD_BENCH_DUMP=$O/shapes_cfg4.txt timeout 800 python bench.py --full --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"
 python - <<PY
 import json
 for f in ("bench_cfg1.json","bench_cfg2.json","bench_cfg4.json"):
@@ -21,7 +21,7 @@ for f in ("bench_cfg1.json","bench_cfg2.json","bench_cfg4.json"):
     except Exception as e: print(f, "ERR", e)
 PY
 cd /tmp && export TMPDIR=/tmp
-timeout 500 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
+timeout 500 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
 cd $R
 DB=$(ls $O/prof/*results.db 2>/dev/null | head -1)
 [ -n "$DB" ] && python profiles/summarize_rocprof.py $DB $O/kernel_stats.md $O/prof_bench.json > /dev/null

@@ -58,14 +58,14 @@ e2e)
   SECONDS=0; timeout 1500 python tests/e2e_parity.py --frames 16 --steps 20 --out $O/e2e_parity.json > $O/e2e.log 2>&1; echo "e2e rc=$? wall ${SECONDS}s"; grep -v "^{" $O/e2e.log | tail -5
   python -c "import json; d=json.load(open('$O/e2e_parity.json')); print({k: (v['rel_l2'], v['cosine']) for k, v in d.items() if isinstance(v, dict) and 'rel_l2' in v})" ;;
 bench)
-  SECONDS=0; MD_BENCH_DUMP=$O/shapes_all.txt timeout 1500 python bench.py > $O/bench_cfg1.json 2> $O/bench_cfg1.err; echo "cfg1 rc=$? wall ${SECONDS}s"; summ $O/bench_cfg1.json ;;
+  SECONDS=0; MD_BENCH_DUMP=$O/shapes_all.txt timeout 1500 python bench.py --full > $O/bench_cfg1.json 2> $O/bench_cfg1.err; echo "cfg1 rc=$? wall ${SECONDS}s"; summ $O/bench_cfg1.json ;;
 bench2)
-  timeout 600 python bench.py --config 2 --no-cpu-baseline --no-pmc > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "cfg2 rc=$?"; summ $O/bench_cfg2.json ;;
+  timeout 600 python bench.py --full --config 2 --no-cpu-baseline --no-pmc > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "cfg2 rc=$?"; summ $O/bench_cfg2.json ;;
 bench4)
-  MD_BENCH_DUMP=$O/shapes_cfg4.txt timeout 900 python bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"; summ $O/bench_cfg4.json ;;
+  MD_BENCH_DUMP=$O/shapes_cfg4.txt timeout 900 python bench.py --full --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"; summ $O/bench_cfg4.json ;;
 prof)
   cd /tmp && export TMPDIR=/tmp
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
   cd $R
   DB=$(ls $O/prof/*results.db 2>/dev/null | head -1)
   [ -n "$DB" ] && python profiles/summarize_rocprof.py $DB $O/kernel_stats.md $O/prof_bench.json > /dev/null
@@ -79,7 +79,7 @@ ab)
   cp mikudance_amd/libmdance_hip.so /tmp/lib_keep.so
   for r in 1 2; do for v in $MD_AB; do
     cp tools/ab/lib_$v.so mikudance_amd/libmdance_hip.so
-    MD_BENCH_DUMP=$O/shapes_${v}_$r.txt timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-pmc 2>/dev/null > $O/ab_${v}_$r.json; echo "== $v (round $r)"; summ $O/ab_${v}_$r.json
+    MD_BENCH_DUMP=$O/shapes_${v}_$r.txt timeout 400 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-pmc 2>/dev/null > $O/ab_${v}_$r.json; echo "== $v (round $r)"; summ $O/ab_${v}_$r.json
   done; done 2>&1 | tee $O/ab.log
   cp /tmp/lib_keep.so mikudance_amd/libmdance_hip.so ;;
 trace)
@@ -90,13 +90,13 @@ trace)
 abenv)
   # same-box A/B of ONE environment knob in ONE library: MD_AB_ENV=MD_WS_EXTRA MD_AB_VALUES="0 1" [MD_AB_FLAGS="--no-share"]; two rounds, family table + per-shape dumps
   for r in 1 2; do for v in ${MD_AB_VALUES:-0 1}; do
-    env ${MD_AB_ENV:-MD_NONE}=$v MD_BENCH_DUMP=$O/shapes_${v}_$r.txt timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-pmc $MD_AB_FLAGS 2>/dev/null > $O/ab_${v}_$r.json
+    env ${MD_AB_ENV:-MD_NONE}=$v MD_BENCH_DUMP=$O/shapes_${v}_$r.txt timeout 400 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-pmc $MD_AB_FLAGS 2>/dev/null > $O/ab_${v}_$r.json
     echo "== ${MD_AB_ENV}=$v (round $r)"; summ $O/ab_${v}_$r.json
   done; done 2>&1 | tee $O/ab.log ;;
 abflag)
   # same-box A/B of a bench.py flag: MD_AB_FLAG="--no-share" (off = the flag given); two rounds
   for r in 1 2; do for f in "$MD_AB_FLAG" ""; do
-    timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-pmc $f 2>/dev/null > $O/ab.json; echo "== flag '${f:-(none)}' (round $r)"; summ $O/ab.json
+    timeout 400 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-pmc $f 2>/dev/null > $O/ab.json; echo "== flag '${f:-(none)}' (round $r)"; summ $O/ab.json
   done; done 2>&1 | tee $O/ab.log ;;
 kernab)
   # micro-benchmarks (tools/bench_kernels.py $MD_KERN) under each library of MD_AB (tools/ab/lib_*.so): ablation / A-B builds at the kernel level
@@ -112,7 +112,7 @@ ranks2)
   # bench.py's multi-rank paths with the REAL kernels on the one GPU a lease has (both ranks on cuda:0, collectives over gloo): clip data-parallel (rank-local and
   # --scatter) at configs[1], window-parallel at configs[4].  Control-flow records (per-rank diagnostics, collectives timed outside the region), NOT scaling figures.
   export MD_DIST_BACKEND=gloo
-  r2() { timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $1 bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc "${@:3}" > $O/$2.json 2> $O/$2.err; echo "$2 rc=$?"; }
+  r2() { timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $1 bench.py --full --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc "${@:3}" > $O/$2.json 2> $O/$2.err; echo "$2 rc=$?"; }
   r2 29511 bench_2rank_dp; r2 29512 bench_2rank_dp_scatter --scatter; r2 29513 bench_cfg4_2rank_window_parallel --config 4 --window-parallel
   summ $O/bench_2rank_dp.json $O/bench_2rank_dp_scatter.json $O/bench_cfg4_2rank_window_parallel.json ;;
 rccl1)
@@ -120,8 +120,8 @@ rccl1)
   # the device-bound barrier -- goes through RCCL on the one GPU a lease has.  Proves the library loads and accepts the calls as made; says nothing about xGMI.
   export MD_DIST_FORCE=1
   B="--gpus 1 --steps 1 --warmup 1 --no-cpu-baseline --no-vae --no-pmc"
-  MASTER_PORT=29541 timeout 600 python bench.py $B --scatter > $O/rccl1_dp_scatter.json 2> $O/rccl1_dp_scatter.err; echo "rccl1 dp scatter rc=$?"
-  MASTER_PORT=29542 timeout 600 python bench.py $B --window-parallel > $O/rccl1_window_parallel.json 2> $O/rccl1_window_parallel.err; echo "rccl1 window-parallel rc=$?"
+  MASTER_PORT=29541 timeout 600 python bench.py --full $B --scatter > $O/rccl1_dp_scatter.json 2> $O/rccl1_dp_scatter.err; echo "rccl1 dp scatter rc=$?"
+  MASTER_PORT=29542 timeout 600 python bench.py --full $B --window-parallel > $O/rccl1_window_parallel.json 2> $O/rccl1_window_parallel.err; echo "rccl1 window-parallel rc=$?"
   unset MD_DIST_FORCE
   summ $O/rccl1_dp_scatter.json $O/rccl1_window_parallel.json
   python -c "
@@ -133,9 +133,9 @@ queues)
   # one CFG clip / one guidance-free clip / two guidance-free clips from two processes / two CFG clips from two processes (profiles/r06_ab_two_queues.log)
   export MD_DIST_BACKEND=gloo
   B="--steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-pmc"
-  timeout 400 python bench.py $B > $O/a.json 2>/dev/null; timeout 400 python bench.py $B --guidance 1.0 > $O/b.json 2>/dev/null
-  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29521 bench.py --gpus 2 $B --guidance 1.0 > $O/c.json 2>/dev/null
-  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29522 bench.py --gpus 2 $B > $O/d.json 2>/dev/null
+  timeout 400 python bench.py --full $B > $O/a.json 2>/dev/null; timeout 400 python bench.py --full $B --guidance 1.0 > $O/b.json 2>/dev/null
+  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29521 bench.py --full --gpus 2 $B --guidance 1.0 > $O/c.json 2>/dev/null
+  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29522 bench.py --full --gpus 2 $B > $O/d.json 2>/dev/null
   summ $O/a.json $O/b.json $O/c.json $O/d.json ;;
 *) echo "unknown step $step" ;;
 esac

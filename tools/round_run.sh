@@ -8,11 +8,11 @@ mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q --durations=12 > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee $O/pytest.rc
 tail -4 $O/pytest.log
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-python bench.py --config 2 --no-cpu-baseline > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "bench cfg2 rc=$?"
-MD_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --small --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo_small.json 2> $O/bench_2rank.err; echo "2-rank rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --config 2 --no-cpu-baseline > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "bench cfg2 rc=$?"
+MD_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --small --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo_small.json 2> $O/bench_2rank.err; echo "2-rank rc=$?"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
+rocprofv3 --kernel-trace --stats -d $O/prof -o prof -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.err; echo "prof rc=$?"
 cd $R
 DB=$(ls $O/prof/*results.db 2>/dev/null | head -1)
 [ -n "$DB" ] && python profiles/summarize_rocprof.py $DB $O/kernel_stats.md $O/prof_bench.json > /dev/null
