@@ -176,6 +176,17 @@ int md_cfg_ddim_step(void* latents, const void* noise_sum, const void* counter, 
 int md_cfg_ddim_step_eta(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW,
                          int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
 
+/* (noise_pred / counter) -> classifier-free guidance -> one DPM-Solver++ multistep update (orders 1 / 2, ODE or SDE), latents updated
+ * in place: m0 = alpha_s x - sigma_s v, x' = c_x x + c_m0 m0 + c_m1 m1 + c_z z, with m1 = history (fp32 [Ftot][HW][4], the previous
+ * step's m0) read only when c_m1 != 0 and then overwritten with m0.  The coefficients come from the host
+ * (DPMSolverMultistepScheduler.multistep_coefficients); variance_noise (fp16, laid out like the latents) may be NULL when c_z == 0.
+ * noise_sum, counter, Ftot, HW, halves, guidance as md_cfg_ddim_step.  Latents / variance_noise 8-byte, noise_sum / history 16-byte aligned.
+ * src/pipelines/pipeline_mikudance.py:45-52 (scheduler typed as one of six diffusers schedulers, DPMSolverMultistepScheduler among
+ * them) and :670-678 (self.scheduler.step). */
+int md_cfg_multistep_step(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise, int Ftot,
+                          int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
+                          void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

@@ -48,6 +48,7 @@ SIGNATURES = {
     "md_window_accumulate": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "md_cfg_ddim_step": (c_int, [P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, P]),
     "md_cfg_ddim_step_eta": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P]),
+    "md_cfg_multistep_step": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),
 }
 
 _lib = None

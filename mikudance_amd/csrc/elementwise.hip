@@ -1,6 +1,7 @@
 // Small HBM-bound kernels around the two UNets: layout packing at the API boundary, channel concat for the decoder
 // skip connections, window accumulation + classifier-free guidance + DDIM step (reference
-// src/pipelines/pipeline_mikudance.py:577-589, 662-678 and diffusers DDIMScheduler.step, v-prediction, eta = 0).
+// src/pipelines/pipeline_mikudance.py:577-589, 662-678 and diffusers DDIMScheduler.step, v-prediction, eta = 0) or DPM-Solver++
+// multistep step (the same call site's scheduler.step with a DPMSolverMultistepScheduler).
 #include "common.h"
 #include <stdarg.h>
 
@@ -151,6 +152,59 @@ extern "C" int md_cfg_ddim_step_eta(void* latents, const void* noise_sum, const 
                                     float guidance, float alpha_t, float alpha_prev, float eta, void* stream) {
   return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream,
                          "md_cfg_ddim_step_eta");
+}
+
+// ---- CFG combine + DPM-Solver++ multistep step (orders 1 / 2, ODE or SDE; Lu et al., arXiv 2211.01095) ------------------
+//   v   = window-averaged, guided v-output exactly as in cfg_ddim_kernel
+//   m0  = alpha_s x - sigma_s v                    data prediction (x0) of this step
+//   x'  = c_x x + c_m0 m0 + c_m1 m1 + c_z z        m1 = the previous step's m0 (history), z = variance noise
+// The coefficients are host scalars (DPMSolverMultistepScheduler.multistep_coefficients): every solver variant is this one update.
+// One thread per pixel (4 channels): 8-byte latents / noise, 16-byte noise_sum / history.  history is read (only when c_m1 != 0: on
+// the first step it is uninitialised) and then overwritten with m0 by the same thread at the same index.
+__global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
+                                     float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, int halves,
+                                     float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z) {
+  const long total = (long)Ftot * HW;  // pixels
+  const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
+  floatx4* hist = reinterpret_cast<floatx4*>(history);
+  half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
+  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const int fr = (int)(p / HW);
+    const float inv = halves == 2 ? 1.f / counter[fr] : 1.f;  // no division without guidance (see cfg_ddim_kernel)
+    floatx4 v = ns[p] * inv;
+    if (halves == 2) {
+      const floatx4 c = ns[total + p] * inv;
+      v = v + guidance * (c - v);
+    }
+    const floatx4 x = __builtin_convertvector(lat4[p], floatx4);
+    const floatx4 m0 = alpha_s * x - sigma_s * v;
+    floatx4 out = c_x * x + c_m0 * m0;
+    if (c_m1 != 0.f) out += c_m1 * hist[p];
+    hist[p] = m0;
+    if (variance_noise) out += c_z * __builtin_convertvector(reinterpret_cast<const half4_t*>(variance_noise)[p], floatx4);
+    lat4[p] = __builtin_convertvector(out, half4_t);
+  }
+}
+
+extern "C" int md_cfg_multistep_step(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise, int Ftot,
+                                     int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
+                                     void* stream) {
+  MD_CHECK_ARG(latents && noise_sum && history && Ftot > 0 && HW > 0 && (halves == 1 || (halves == 2 && counter)),
+               "md_cfg_multistep_step: bad arguments");
+  MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
+                   ((uintptr_t)variance_noise % 8) == 0,
+               "md_cfg_multistep_step: latents / variance_noise need 8-byte, noise_sum / history 16-byte alignment");
+  MD_CHECK_ARG(__builtin_isfinite(guidance) && __builtin_isfinite(alpha_s) && __builtin_isfinite(sigma_s) && __builtin_isfinite(c_x) &&
+                   __builtin_isfinite(c_m0) && __builtin_isfinite(c_m1) && __builtin_isfinite(c_z),
+               "md_cfg_multistep_step: non-finite coefficient");
+  MD_CHECK_ARG(c_z == 0.f || variance_noise, "md_cfg_multistep_step: c_z != 0 needs variance_noise");
+  const long total = (long)Ftot * HW;
+  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(cfg_multistep_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+                     (const float*)counter, (float*)history, c_z != 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW, halves, guidance, alpha_s,
+                     sigma_s, c_x, c_m0, c_m1, c_z);
+  MD_CHECK_LAUNCH("md_cfg_multistep_step");
+  return MD_OK;
 }
 
 // ---- generic strided scatter of NHWC fp16 -> any layout/dtype (API boundary: UNet.forward returns NCFHW) ---------------

@@ -11,6 +11,7 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                                                              unet_additional_kwargs=infer_config.unet_additional_kwargs)  (:90-95)
     image_enc      = CLIPVisionModelWithProjection.from_pretrained(config.image_encoder_path)      (:97-99)
     scheduler      = DDIMScheduler(**infer_config.noise_scheduler_kwargs)                          (:101-102)
+                     (--sampler dpmpp_2m / dpmpp_2m_sde: DPMSolverMultistepScheduler from the same kwargs; an addition)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -26,10 +27,17 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import (AutoencoderKL, AutoencoderKLTemporalDecoder, CLIPVisionModelWithProjection, DDIMScheduler, MikuDanceVideoPipeline,
-               UNet2DConditionModel, UNet2DConditionModelPlain, UNet3DConditionModel)
+from . import (AutoencoderKL, AutoencoderKLTemporalDecoder, CLIPVisionModelWithProjection, DDIMScheduler, DPMSolverMultistepScheduler,
+               MikuDanceVideoPipeline, UNet2DConditionModel, UNet2DConditionModelPlain, UNet3DConditionModel)
 from .io_utils import frames_to_tensor, get_fps, load_config, read_frames, resize_depth, save_videos_grid, to_container
 from .scene_motion import camera_to_scene_motion
+
+
+# --sampler -> the scheduler built from the YAML's noise_scheduler_kwargs (the YAML's own `sampler: DDIM` key stays ignored, as in the
+# reference script)
+SAMPLERS = {"ddim": lambda kw: DDIMScheduler(**kw),
+            "dpmpp_2m": lambda kw: DPMSolverMultistepScheduler.from_config(kw, solver_order=2, algorithm_type="dpmsolver++"),
+            "dpmpp_2m_sde": lambda kw: DPMSolverMultistepScheduler.from_config(kw, solver_order=2, algorithm_type="sde-dpmsolver++")}
 
 
 def parse_args(argv=None):
@@ -44,6 +52,9 @@ def parse_args(argv=None):
     parser.add_argument("--video_decoder", action="store_true",
                         help="The temporal decoder produces less noise in the results but leads to longer inference times.")
     parser.add_argument("--output_dir", default="output", help="(addition) root of the dated output tree")
+    parser.add_argument("--sampler", choices=tuple(SAMPLERS), default="ddim",
+                        help="(addition) ddim (the reference's), dpmpp_2m or dpmpp_2m_sde (DPM-Solver++ 2M, ODE / SDE), all built from "
+                             "noise_scheduler_kwargs")
     return parser.parse_args(argv)
 
 
@@ -51,7 +62,12 @@ def _none(v):
     return v is None or v == "None"
 
 
-def build_pipeline(config, infer_config, weight_dtype, device="cuda", video_decoder=False):
+def build_scheduler(infer_config, sampler="ddim"):
+    """scripts/inference_video.py:101-102 (`--sampler ddim`), or the DPM-Solver++ 2M scheduler from the same keyword arguments."""
+    return SAMPLERS[sampler](to_container(infer_config.noise_scheduler_kwargs))
+
+
+def build_pipeline(config, infer_config, weight_dtype, device="cuda", video_decoder=False, sampler="ddim"):
     """scripts/inference_video.py:72-130."""
     if video_decoder:
         vae = AutoencoderKLTemporalDecoder.from_pretrained(config.pretrained_temporal_vae_path).to(device, dtype=weight_dtype)
@@ -64,7 +80,7 @@ def build_pipeline(config, infer_config, weight_dtype, device="cuda", video_deco
         config.pretrained_base_model_path, config.motion_module_path, subfolder="unet",
         unet_additional_kwargs=infer_config.unet_additional_kwargs).to(dtype=weight_dtype, device=device)
     image_enc = CLIPVisionModelWithProjection.from_pretrained(config.image_encoder_path).to(dtype=weight_dtype, device=device)
-    scheduler = DDIMScheduler(**to_container(infer_config.noise_scheduler_kwargs))
+    scheduler = build_scheduler(infer_config, sampler)
     denoising_unet.load_state_dict(torch.load(config.denoising_unet_path, map_location="cpu", weights_only=True), strict=False)
     reference_unet.load_state_dict(torch.load(config.reference_unet_path, map_location="cpu", weights_only=True))
     denoising_unet.eval()
@@ -88,7 +104,7 @@ def main(argv=None):
     generator = torch.manual_seed(args.seed)
     width, height = args.W, args.H
     assert width % 8 == 0 and height % 8 == 0      # the vae works at 1/8 resolution (scripts/inference_video.py:108)
-    pipe = build_pipeline(config, infer_config, weight_dtype, video_decoder=args.video_decoder)
+    pipe = build_pipeline(config, infer_config, weight_dtype, video_decoder=args.video_decoder, sampler=args.sampler)
 
     date_str = datetime.now().strftime("%Y%m%d")
     time_str = datetime.now().strftime("%H%M%S")

@@ -313,3 +313,22 @@ def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alph
         return
     _lib.call("md_cfg_ddim_step", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), ftot, hw, halves,
               float(guidance), float(alpha_t), float(alpha_prev), _st())
+
+
+def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, halves=2,
+                       variance_noise=None):
+    """DPM-Solver++ multistep update (md_cfg_multistep_step): `history` is the fp32 (ftot, hw, 4) data-prediction buffer the caller keeps
+    between steps; the coefficients are DPMSolverMultistepScheduler.multistep_coefficients(step_index).  c_z != 0: `variance_noise` is
+    the caller's N(0, 1) draw, fp16, laid out like `latents`."""
+    _chk(latents, "latents"); _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
+    _chk(history, "history", torch.float32)
+    n = ftot * hw * 4
+    assert halves in (1, 2) and latents.is_contiguous() and latents.numel() == n
+    assert noise_sum.is_contiguous() and noise_sum.numel() == halves * n and counter.numel() >= ftot
+    assert history.is_contiguous() and history.numel() == n
+    if c_z:
+        _chk(variance_noise, "variance_noise")
+        assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == n
+    _lib.call("md_cfg_multistep_step", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), history.data_ptr(),
+              _p(variance_noise) if c_z else 0, ftot, hw, halves, float(guidance), float(alpha_s), float(sigma_s), float(c_x), float(c_m0),
+              float(c_m1), float(c_z), _st())

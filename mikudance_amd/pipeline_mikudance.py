@@ -134,6 +134,8 @@ class MikuDanceVideoPipeline:
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
         ref_latents         (1, F, 22, h, w) 20 VAE-latent guidance channels + 2 scene-motion channels
         image_prompt_embeds (2, L, D) = [zeros, CLIP tokens] when guidance_scale > 1, else (1, L, D)
+        scheduler           self.scheduler: DDIMScheduler (md_cfg_ddim_step) or DPMSolverMultistepScheduler (md_cfg_multistep_step with a
+                            fp32 data-prediction history of (F, h*w, 4) for this call; its SDE variant draws z every step like eta below)
         eta, generator      DDIM's stochastic variant (reference :152-171 -> scheduler.step(eta=, generator=)): one N(0, 1) draw of
                             the latents' shape and dtype per step from `generator` (on ITS device, like diffusers' randn_tensor).
                             The kernels compute in fp16: the draw is ROUNDED TO fp16 on its way into md_cfg_ddim_step_eta, so an
@@ -149,6 +151,14 @@ class MikuDanceVideoPipeline:
         do_cfg = guidance_scale > 1.0
         nb = 2 if do_cfg else 1
         den, refu, sch = self.denoising_unet, self.reference_unet, self.scheduler
+        from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+        multistep = isinstance(sch, DPMSolverMultistepScheduler)
+        if not multistep and not isinstance(sch, DDIMScheduler):
+            raise TypeError(f"MikuDanceVideoPipeline.denoise: unsupported scheduler {type(sch).__name__}; the supported ones are "
+                            "mikudance_amd.DDIMScheduler and mikudance_amd.DPMSolverMultistepScheduler")
+        if multistep and eta > 0:
+            raise ValueError("eta applies to DDIMScheduler only; for stochastic DPM-Solver++ sampling use "
+                             "DPMSolverMultistepScheduler(algorithm_type='sde-dpmsolver++')")
         sch.set_timesteps(num_inference_steps)
         timesteps = [int(t) for t in sch.timesteps]
         _, c, F_, hh, ww = latents.shape
@@ -176,6 +186,8 @@ class MikuDanceVideoPipeline:
         win_long = [torch.tensor(w, dtype=torch.long, device=dev) for w in windows]     # gather indices: the real frames
         whole = len(windows) == 1 and windows[0] == list(range(F_))
         embeds = image_prompt_embeds
+        # DPM-Solver++: the previous step's data prediction, fp32, per call (under window_parallel every rank keeps its own identical copy)
+        history = torch.zeros((F_, HW, 4), device=dev, dtype=torch.float32) if multistep else None
         bank_cache = {}
         refu.skip_dead_tail = True
         den.clear_context_cache()
@@ -210,14 +222,16 @@ class MikuDanceVideoPipeline:
                     writer.clear()
                 if window_parallel is not None:
                     window_parallel.reduce(noise_sum, counter)
-                a_t, a_prev = sch.step_coefficients(t)
-                z = None
-                if eta > 0:
-                    from .scheduler import randn_tensor
-                    zn = randn_tensor(latents.shape, generator=generator, device=dev, dtype=latents.dtype)      # (1, 4, F, h, w)
-                    zs = zn.stride()
-                    z = ops.pack_nhwc(zn, F_, F_, (0, zs[2], zs[1], zs[3], zs[4]), 0, c, 4, hh, ww)
-                ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta), variance_noise=z)
+                if multistep:
+                    z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
+                    ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *sch.multistep_coefficients(step_i),
+                                           halves=nb, variance_noise=z)
+                else:
+                    a_t, a_prev = sch.step_coefficients(t)
+                    z = None
+                    if eta > 0:
+                        z = self._draw_noise(latents, generator)
+                    ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta), variance_noise=z)
                 if callback is not None and step_i % callback_steps == 0:
                     callback(step_i, t, self._latents_out(lat, latents))
         finally:
@@ -227,6 +241,16 @@ class MikuDanceVideoPipeline:
             den.clear_context_cache()
             refu.clear_context_cache()
         return self._latents_out(lat, latents)
+
+    @staticmethod
+    def _draw_noise(latents, generator):
+        """One N(0, 1) draw of the latents' shape and dtype from `generator` (on ITS device, diffusers randn_tensor), packed to the
+        (F, h, w, 4) fp16 layout of the internal latents."""
+        from .scheduler import randn_tensor
+        _, c, F_, hh, ww = latents.shape
+        zn = randn_tensor(latents.shape, generator=generator, device=latents.device, dtype=latents.dtype)      # (1, 4, F, h, w)
+        zs = zn.stride()
+        return ops.pack_nhwc(zn, F_, F_, (0, zs[2], zs[1], zs[3], zs[4]), 0, c, 4, hh, ww)
 
     def _latents_out(self, lat, like):
         out = torch.empty(like.shape, device=like.device, dtype=like.dtype)

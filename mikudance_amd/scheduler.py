@@ -2,7 +2,12 @@
 (reference configs/inference/mikudance_config.yaml:24-33; constructed at scripts/inference_video.py:101-102):
 linear betas rescaled to zero terminal SNR, v-prediction, trailing timestep spacing; eta = 0 (the script's default) or eta > 0.
 The table is 1000 fp32 scalars on the host; the per-step arithmetic on the latents is the HIP kernel
-md_cfg_ddim_step (fused with window averaging and classifier-free guidance)."""
+md_cfg_ddim_step (fused with window averaging and classifier-free guidance).
+
+DPMSolverMultistepScheduler -- DPM-Solver++ (Lu et al., arXiv 2211.01095) orders 1 / 2, ODE or SDE, restated on the same discrete
+table (not pinned to a diffusers version): every step is ONE linear update with host scalars, run by md_cfg_multistep_step."""
+import inspect
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -16,6 +21,18 @@ def randn_tensor(shape, generator=None, device=None, dtype=None):
     device = torch.device(device) if device is not None else torch.device("cpu")
     gdev = generator.device if generator is not None else device
     return torch.randn(tuple(shape), generator=generator, device=gdev, dtype=dtype).to(device)
+
+
+def _linear_betas(beta_start, beta_end, num_train_timesteps, rescale_betas_zero_snr):
+    """Linear betas in fp32, optionally rescaled to zero terminal SNR (alphas_cumprod[-1] == 0 exactly)."""
+    betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+    if rescale_betas_zero_snr:
+        s = torch.cumprod(1.0 - betas, dim=0).sqrt()
+        s0, sT = s[0].clone(), s[-1].clone()
+        s = (s - sT) * (s0 / (s0 - sT))
+        ab = s ** 2
+        betas = 1 - torch.cat([ab[0:1], ab[1:] / ab[:-1]])
+    return betas
 
 
 @dataclass
@@ -40,14 +57,7 @@ class DDIMScheduler:
                            beta_schedule=beta_schedule, clip_sample=clip_sample, set_alpha_to_one=set_alpha_to_one,
                            steps_offset=steps_offset, prediction_type=prediction_type, timestep_spacing=timestep_spacing,
                            rescale_betas_zero_snr=rescale_betas_zero_snr)
-        betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        if rescale_betas_zero_snr:
-            s = torch.cumprod(1.0 - betas, dim=0).sqrt()
-            s0, sT = s[0].clone(), s[-1].clone()
-            s = (s - sT) * (s0 / (s0 - sT))
-            ab = s ** 2
-            betas = 1 - torch.cat([ab[0:1], ab[1:] / ab[:-1]])
-        self.betas = betas
+        self.betas = betas = _linear_betas(beta_start, beta_end, num_train_timesteps, rescale_betas_zero_snr)
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.init_noise_sigma = 1.0
@@ -97,3 +107,167 @@ class DDIMScheduler:
         if not return_dict:
             return (prev,)
         return DDIMSchedulerOutput(prev_sample=prev)
+
+
+@dataclass
+class DPMSolverMultistepSchedulerOutput:
+    prev_sample: torch.Tensor
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++ multistep sampling on MikuDance's zero-terminal-SNR schedule (diffusers keyword names; the built subset is
+    solver_order 1 / 2, algorithm_type dpmsolver++ / sde-dpmsolver++, solver_type midpoint / heun, v-prediction, trailing spacing,
+    linear betas, final_sigmas_type "zero").
+
+    With alpha_i = sqrt(abar(t_i)), sigma_i = sqrt(1 - abar(t_i)), step i goes from s = t_i to t = t_{i+1} (the list's NEXT entry; the
+    last step to the clean sample, alpha = 1, sigma = 0) and reduces to
+        m0 = alpha_s x - sigma_s v,   x' = c_x x + c_m0 m0 + c_m1 m1 + c_z z     (m1 = the previous step's m0, z ~ N(0, 1))
+    The coefficients use e^-h = (alpha_s sigma_t) / (sigma_s alpha_t) in float64 -- exactly 0 at the first step (alpha_s = 0) and at the
+    last (sigma_t = 0) -- so lambda = log(alpha / sigma) is never formed where it is infinite.  Step 0 and the last step are order 1;
+    rho = h / h_0 is 0 when the previous point is the lambda = -inf endpoint (step 1), its order-1 limit."""
+    order = 1
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02, beta_schedule: str = "linear",
+                 trained_betas=None, solver_order: int = 2, prediction_type: str = "epsilon", thresholding: bool = False,
+                 dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0, algorithm_type: str = "dpmsolver++",
+                 solver_type: str = "midpoint", lower_order_final: bool = True, euler_at_final: bool = False, use_karras_sigmas: bool = False,
+                 use_lu_lambdas: bool = False, final_sigmas_type: str = "zero", lambda_min_clipped: float = -float("inf"),
+                 variance_type=None, timestep_spacing: str = "linspace", steps_offset: int = 0, rescale_betas_zero_snr: bool = False,
+                 clip_sample: bool = False, set_alpha_to_one: bool = True):
+        # clip_sample / set_alpha_to_one: DDIM keys of the MikuDance config (selftest.SCHED_KWARGS), accepted at their MikuDance values
+        if beta_schedule != "linear" or trained_betas is not None:
+            raise NotImplementedError("only beta_schedule='linear' (MikuDance config) is implemented")
+        if prediction_type != "v_prediction" or timestep_spacing != "trailing" or thresholding or clip_sample:
+            raise NotImplementedError("only v_prediction / trailing / no thresholding or clipping (MikuDance config) is implemented")
+        if solver_order not in (1, 2):
+            raise NotImplementedError(f"solver_order={solver_order}: only orders 1 and 2 are implemented")
+        if algorithm_type not in ("dpmsolver++", "sde-dpmsolver++"):
+            raise NotImplementedError(f"algorithm_type={algorithm_type!r}: only 'dpmsolver++' and 'sde-dpmsolver++' are implemented")
+        if solver_type not in ("midpoint", "heun"):
+            raise NotImplementedError(f"solver_type={solver_type!r}: only 'midpoint' and 'heun' are implemented")
+        if use_karras_sigmas or use_lu_lambdas:
+            raise NotImplementedError("Karras / Lu lambda spacing is not implemented: timesteps follow the trailing DDIM list")
+        if final_sigmas_type != "zero" or not set_alpha_to_one:
+            raise NotImplementedError("only final_sigmas_type='zero' (the last step lands on the clean sample) is implemented")
+        if lambda_min_clipped != -float("inf") or variance_type is not None:
+            raise NotImplementedError("lambda_min_clipped / variance_type are not implemented")
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                           solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
+                           dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value,
+                           algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final,
+                           euler_at_final=euler_at_final, use_karras_sigmas=use_karras_sigmas, use_lu_lambdas=use_lu_lambdas,
+                           final_sigmas_type=final_sigmas_type, lambda_min_clipped=lambda_min_clipped, variance_type=variance_type,
+                           timestep_spacing=timestep_spacing, steps_offset=steps_offset, rescale_betas_zero_snr=rescale_betas_zero_snr)
+        self.betas = _linear_betas(beta_start, beta_end, num_train_timesteps, rescale_betas_zero_snr)
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, dim=0)
+        self.init_noise_sigma = 1.0
+        self.num_train_timesteps = num_train_timesteps
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
+        self._coeffs = []
+        self._reset_state()
+
+    @classmethod
+    def from_config(cls, config, **kwargs):
+        """diffusers' from_config: keys this class does not take (e.g. a DDIMScheduler config's) are ignored."""
+        known = set(inspect.signature(cls.__init__).parameters) - {"self"}
+        kw = {k: v for k, v in dict(config, **kwargs).items() if k in known}
+        return cls(**kw)
+
+    @property
+    def is_sde(self):
+        return self.config["algorithm_type"] == "sde-dpmsolver++"
+
+    def _reset_state(self):
+        self._history = None          # fp32 data prediction of the last step taken by step()
+        self._last_index = None
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        """The trailing list of DDIMScheduler; resets all multistep state."""
+        self.num_inference_steps = num_inference_steps
+        ratio = self.num_train_timesteps / num_inference_steps
+        ts = np.round(np.arange(self.num_train_timesteps, 0, -ratio)).astype(np.int64) - 1
+        self.timesteps = torch.from_numpy(ts)
+        self._coeffs = self._coefficient_table([int(t) for t in ts])
+        self._reset_state()
+
+    def _coefficient_table(self, ts):
+        n = len(ts)
+        abar = [float(self.alphas_cumprod[t]) for t in ts] + [1.0]           # final_sigmas_type "zero": alpha = 1, sigma = 0
+        al = [math.sqrt(a) for a in abar]
+        sg = [math.sqrt(1.0 - a) for a in abar]
+        sde, heun = self.is_sde, self.config["solver_type"] == "heun"
+        out, prev_emh = [], None
+        for i in range(n):
+            a_s, s_s, a_t, s_t = al[i], sg[i], al[i + 1], sg[i + 1]
+            emh = (a_s * s_t) / (s_s * a_t)                                    # e^-h; 0 at both ends
+            second = self.config["solver_order"] == 2 and 0 < i < n - 1
+            rho = math.log(emh) / math.log(prev_emh) if second and prev_emh > 0.0 else 0.0    # h / h_0; 0 after the lambda = -inf point
+            if sde:
+                c_x = s_t / s_s * emh
+                g = 1.0 - emh * emh                                            # 1 - e^-2h
+                k = a_t * (1.0 - g / (-2.0 * math.log(emh))) if heun and rho else 0.0
+                c_z = s_t * math.sqrt(g)
+            else:
+                c_x = s_t / s_s
+                g = 1.0 - emh
+                k = a_t * (1.0 + math.expm1(math.log(emh)) / -math.log(emh)) if heun and rho else 0.0
+                c_z = 0.0
+            if heun:
+                c_m0, c_m1 = a_t * g + k * rho, -k * rho
+            else:
+                c_m0, c_m1 = a_t * g * (1.0 + 0.5 * rho), -a_t * g * 0.5 * rho
+            out.append((a_s, s_s, c_x, c_m0, c_m1 if rho else 0.0, c_z))
+            prev_emh = emh
+        return out
+
+    def multistep_coefficients(self, step_index: int):
+        """(alpha_s, sigma_s, c_x, c_m0, c_m1, c_z) of step `step_index` as Python floats (see the class docstring)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        return self._coeffs[step_index]
+
+    def index_for_timestep(self, timestep):
+        t = int(timestep)
+        hits = (self.timesteps == t).nonzero().flatten().tolist()
+        if not hits:
+            raise ValueError(f"timestep {t} is not in the current schedule ({self.num_inference_steps} steps)")
+        return hits[0]
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict: bool = True):
+        """API-compatible step on GPU tensors of any shape: md_cfg_multistep_step without window averaging and guidance (one clip-half,
+        counter 1, guidance 1).  The step index comes from `timestep`; the scheduler keeps the fp32 data-prediction history, so a
+        second-order step needs the previous step of the same schedule to have gone through this method."""
+        from . import ops
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if not sample.is_cuda or sample.numel() % 4:
+            raise RuntimeError("DPMSolverMultistepScheduler.step: tensors must live on the GPU (no CPU path)")
+        i = self.index_for_timestep(timestep)
+        co = self.multistep_coefficients(i)
+        n = sample.numel() // 4
+        if co[4] != 0.0 and (self._history is None or self._last_index != i - 1 or self._history.numel() != 4 * n):
+            raise RuntimeError(f"DPMSolverMultistepScheduler.step: step {i} is second order and needs step {i - 1} of the same schedule "
+                               "(and sample shape) to have been taken first")
+        if self._history is None or self._history.numel() != 4 * n or self._history.device != sample.device:
+            self._history = torch.empty((1, n, 4), device=sample.device, dtype=torch.float32)
+        lat = sample.detach().to(torch.float16).reshape(1, n, 4).contiguous().clone()
+        v = model_output.detach().to(torch.float32).reshape(1, 1, n, 4).contiguous()
+        one = torch.ones((1,), device=sample.device, dtype=torch.float32)
+        z = None
+        if self.is_sde:
+            if variance_noise is not None and generator is not None:
+                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                                 " `variance_noise` stays `None`.")
+            if variance_noise is None:                                        # drawn every step, the last one included
+                variance_noise = randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+            z = variance_noise.detach().to(device=sample.device, dtype=torch.float16).reshape(1, n, 4).contiguous()
+        ops.cfg_multistep_step(lat, v, one, self._history, 1, n, 1.0, *co, halves=1, variance_noise=z)
+        self._last_index = i
+        prev = lat.reshape(sample.shape).to(sample.dtype)
+        if not return_dict:
+            return (prev,)
+        return DPMSolverMultistepSchedulerOutput(prev_sample=prev)
