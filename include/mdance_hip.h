@@ -187,6 +187,29 @@ int md_cfg_multistep_step(void* latents, const void* noise_sum, const void* coun
                           int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
                           void* stream);
 
+/* Guidance rescale (rescaled classifier-free guidance, Lin et al. "Common Diffusion Noise Schedules and Sample Steps are Flawed",
+ * arXiv 2305.08891 section 3.4; diffusers rescale_noise_cfg), applied to the window-averaged guided output between
+ * src/pipelines/pipeline_mikudance.py:670-674 (CFG) and :678 (scheduler.step):
+ *   c = noise_sum[1] / counter, v = u + guidance (c - u) exactly as the step kernels form them, std over ALL Ftot HW 4 elements,
+ *   out_scale[0] = 1 - phi + phi std(c) / std(v), one fp32 in device memory (never read back by the library).
+ * One deviation from diffusers: std(v) == 0 gives out_scale = 1 (v left unscaled) where diffusers divides by zero; NaN / Inf inputs
+ * propagate as they would in the formula.  Deterministic (fixed grid, fixed per-workgroup slices, fixed combine order, no atomics): two
+ * calls on the same inputs give the same bits.  halves must be 2, 0 <= phi <= 1, guidance finite; noise_sum 16-byte, workspace 8-byte,
+ * counter / out_scale 4-byte aligned; workspace_bytes >= md_cfg_rescale_workspace_bytes(Ftot, HW) (at most 16 KiB).  MD_ERR_ARG otherwise. */
+size_t md_cfg_rescale_workspace_bytes(int Ftot, int HW);
+int md_cfg_guidance_rescale(const void* noise_sum, const void* counter, int Ftot, int HW, int halves, float guidance, float phi, void* workspace,
+                            size_t workspace_bytes, void* out_scale, void* stream);
+
+/* md_cfg_ddim_step (eta == 0) / md_cfg_ddim_step_eta (eta > 0) and md_cfg_multistep_step with the guided v multiplied by *vscale (the
+ * out_scale of md_cfg_guidance_rescale, read on the device) before the update: diffusers rescale_noise_cfg followed by scheduler.step
+ * (src/pipelines/pipeline_mikudance.py:670-678, arXiv 2305.08891 section 3.4).  halves must be 2; other arguments and alignment as the
+ * unscaled entries, vscale 4-byte aligned. */
+int md_cfg_ddim_step_scaled(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const float* vscale, int Ftot,
+                            int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
+int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                                 const float* vscale, int Ftot, int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x,
+                                 float c_m0, float c_m1, float c_z, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

@@ -49,6 +49,11 @@ SIGNATURES = {
     "md_cfg_ddim_step": (c_int, [P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, P]),
     "md_cfg_ddim_step_eta": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P]),
     "md_cfg_multistep_step": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),
+    "md_cfg_rescale_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "md_cfg_guidance_rescale": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, P, c_size_t, P, P]),
+    "md_cfg_ddim_step_scaled": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P]),
+    "md_cfg_multistep_step_scaled": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
+                                             c_float, P]),
 }
 
 _lib = None

@@ -103,10 +103,14 @@ extern "C" int md_window_accumulate(const void* pred, void* noise_sum, void* cou
 //   x0  = sqrt(a_t) x - sqrt(1-a_t) v ;  eps = sqrt(a_t) v + sqrt(1-a_t) x
 //   x'  = sqrt(a_prev) x0 + sqrt(1-a_prev) eps                                      DDIMScheduler.step
 // latents: [Ftot][HW][4] fp16, updated in place (fp32 arithmetic, one rounding).
+// SCALED (guidance rescale): v is multiplied by *vscale, the factor md_cfg_guidance_rescale left in device memory; the unscaled
+// instantiation has neither the load nor the multiply.
+template <bool SCALED>
 __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
                                 const half_t* __restrict__ variance_noise, int Ftot, int HW4, int halves, float guidance, float sa, float sb, float sap,
-                                float sdir, float sigma) {
+                                float sdir, float sigma, const float* __restrict__ vscale) {
   const long total = (long)Ftot * HW4;
+  const float vs = SCALED ? *vscale : 1.f;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int fr = (int)(idx / HW4);
     // without guidance the reference takes the window SUM as it is: its division by the counter sits inside
@@ -117,6 +121,7 @@ __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restric
       const float c = noise_sum[total + idx] * inv;
       v = v + guidance * (c - v);
     }
+    if constexpr (SCALED) v *= vs;
     const float x = (float)lat[idx];
     const float x0 = sa * x - sb * v;
     const float ep = sa * v + sb * x;
@@ -127,7 +132,7 @@ __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restric
 }
 
 static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW, int halves,
-                           float guidance, float alpha_t, float alpha_prev, float eta, void* stream, const char* who) {
+                           float guidance, float alpha_t, float alpha_prev, float eta, void* stream, const char* who, const float* vscale = nullptr) {
   MD_CHECK_ARG(Ftot > 0 && HW > 0 && (halves == 1 || halves == 2) && eta >= 0.f && (eta == 0.f || variance_noise), "md_cfg_ddim_step: bad arguments");
   // diffusers DDIMScheduler._get_variance: sigma_t^2 = eta^2 (1 - a_prev) / (1 - a_t) (1 - a_t / a_prev); a_t == 1 never occurs (t >= 0 of a
   // zero-terminal-SNR table has a_t < 1)
@@ -136,9 +141,14 @@ static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* cou
   const float dir2 = 1.f - alpha_prev - sigma * sigma;
   const long total = (long)Ftot * HW * 4;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum, (const float*)counter,
-                     eta > 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW * 4, halves, guidance, sqrtf(alpha_t), sqrtf(1.f - alpha_t),
-                     sqrtf(alpha_prev), sqrtf(dir2 > 0.f ? dir2 : 0.f), sigma);
+  if (vscale)
+    hipLaunchKernelGGL(cfg_ddim_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+                       (const float*)counter, eta > 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW * 4, halves, guidance, sqrtf(alpha_t),
+                       sqrtf(1.f - alpha_t), sqrtf(alpha_prev), sqrtf(dir2 > 0.f ? dir2 : 0.f), sigma, vscale);
+  else
+    hipLaunchKernelGGL(cfg_ddim_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+                       (const float*)counter, eta > 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW * 4, halves, guidance, sqrtf(alpha_t),
+                       sqrtf(1.f - alpha_t), sqrtf(alpha_prev), sqrtf(dir2 > 0.f ? dir2 : 0.f), sigma, nullptr);
   MD_CHECK_LAUNCH(who);
   return MD_OK;
 }
@@ -154,20 +164,33 @@ extern "C" int md_cfg_ddim_step_eta(void* latents, const void* noise_sum, const 
                          "md_cfg_ddim_step_eta");
 }
 
+extern "C" int md_cfg_ddim_step_scaled(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const float* vscale,
+                                       int Ftot, int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream) {
+  MD_CHECK_ARG(latents && noise_sum && counter && vscale && halves == 2, "md_cfg_ddim_step_scaled: bad arguments (guidance rescale needs halves == 2)");
+  MD_CHECK_ARG(((uintptr_t)vscale % 4) == 0, "md_cfg_ddim_step_scaled: vscale needs 4-byte alignment");
+  MD_CHECK_ARG(__builtin_isfinite(guidance) && __builtin_isfinite(alpha_t) && __builtin_isfinite(alpha_prev) && __builtin_isfinite(eta),
+               "md_cfg_ddim_step_scaled: non-finite coefficient");
+  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream,
+                         "md_cfg_ddim_step_scaled", vscale);
+}
+
 // ---- CFG combine + DPM-Solver++ multistep step (orders 1 / 2, ODE or SDE; Lu et al., arXiv 2211.01095) ------------------
 //   v   = window-averaged, guided v-output exactly as in cfg_ddim_kernel
 //   m0  = alpha_s x - sigma_s v                    data prediction (x0) of this step
 //   x'  = c_x x + c_m0 m0 + c_m1 m1 + c_z z        m1 = the previous step's m0 (history), z = variance noise
 // The coefficients are host scalars (DPMSolverMultistepScheduler.multistep_coefficients): every solver variant is this one update.
 // One thread per pixel (4 channels): 8-byte latents / noise, 16-byte noise_sum / history.  history is read (only when c_m1 != 0: on
-// the first step it is uninitialised) and then overwritten with m0 by the same thread at the same index.
+// the first step it is uninitialised) and then overwritten with m0 by the same thread at the same index.  SCALED as in cfg_ddim_kernel.
+template <bool SCALED>
 __global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
                                      float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, int halves,
-                                     float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z) {
+                                     float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
+                                     const float* __restrict__ vscale) {
   const long total = (long)Ftot * HW;  // pixels
   const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
   floatx4* hist = reinterpret_cast<floatx4*>(history);
   half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
+  const float vs = SCALED ? *vscale : 1.f;
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const int fr = (int)(p / HW);
     const float inv = halves == 2 ? 1.f / counter[fr] : 1.f;  // no division without guidance (see cfg_ddim_kernel)
@@ -176,6 +199,7 @@ __global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __re
       const floatx4 c = ns[total + p] * inv;
       v = v + guidance * (c - v);
     }
+    if constexpr (SCALED) v *= vs;
     const floatx4 x = __builtin_convertvector(lat4[p], floatx4);
     const floatx4 m0 = alpha_s * x - sigma_s * v;
     floatx4 out = c_x * x + c_m0 * m0;
@@ -200,10 +224,143 @@ extern "C" int md_cfg_multistep_step(void* latents, const void* noise_sum, const
   MD_CHECK_ARG(c_z == 0.f || variance_noise, "md_cfg_multistep_step: c_z != 0 needs variance_noise");
   const long total = (long)Ftot * HW;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(cfg_multistep_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+  hipLaunchKernelGGL(cfg_multistep_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
                      (const float*)counter, (float*)history, c_z != 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW, halves, guidance, alpha_s,
-                     sigma_s, c_x, c_m0, c_m1, c_z);
+                     sigma_s, c_x, c_m0, c_m1, c_z, nullptr);
   MD_CHECK_LAUNCH("md_cfg_multistep_step");
+  return MD_OK;
+}
+
+extern "C" int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                                            const float* vscale, int Ftot, int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x,
+                                            float c_m0, float c_m1, float c_z, void* stream) {
+  MD_CHECK_ARG(latents && noise_sum && counter && history && vscale && Ftot > 0 && HW > 0 && halves == 2,
+               "md_cfg_multistep_step_scaled: bad arguments (guidance rescale needs halves == 2)");
+  MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
+                   ((uintptr_t)variance_noise % 8) == 0 && ((uintptr_t)vscale % 4) == 0,
+               "md_cfg_multistep_step_scaled: latents / variance_noise need 8-byte, noise_sum / history 16-byte, vscale 4-byte alignment");
+  MD_CHECK_ARG(__builtin_isfinite(guidance) && __builtin_isfinite(alpha_s) && __builtin_isfinite(sigma_s) && __builtin_isfinite(c_x) &&
+                   __builtin_isfinite(c_m0) && __builtin_isfinite(c_m1) && __builtin_isfinite(c_z),
+               "md_cfg_multistep_step_scaled: non-finite coefficient");
+  MD_CHECK_ARG(c_z == 0.f || variance_noise, "md_cfg_multistep_step_scaled: c_z != 0 needs variance_noise");
+  const long total = (long)Ftot * HW;
+  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(cfg_multistep_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+                     (const float*)counter, (float*)history, c_z != 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW, halves, guidance, alpha_s,
+                     sigma_s, c_x, c_m0, c_m1, c_z, vscale);
+  MD_CHECK_LAUNCH("md_cfg_multistep_step_scaled");
+  return MD_OK;
+}
+
+// ---- guidance rescale factor (Lin et al., arXiv 2305.08891 section 3.4; diffusers rescale_noise_cfg) ----------------------------------
+//   c = sum_c / cnt, v = u + s (c - u)              formed on the fly exactly as the step kernels form them (never materialised)
+//   out_scale = 1 - phi + phi std(c) / std(v)      std over all Ftot HW 4 elements; the (N - 1) of torch.std cancels in the ratio
+//   std(v) == 0 -> out_scale = 1                  (diffusers would give inf / NaN; NaN / Inf inputs still propagate)
+// Deterministic, no float atomics, no host sync: rescale_blocks(Ftot, HW) <= 512 workgroups, each over a FIXED contiguous slice of
+// pixels, reduce shifted sums in fp64 (pilot = element 0 of c and of v, so that a large common offset does not cancel; differences and
+// squares are formed in fp64) through a fixed butterfly and a fixed wave order into workspace partials; ONE small launch then adds the
+// partials in a fixed order and writes the factor.  A separate finalize launch (~2 us) instead of a combine in every workgroup of the step
+// kernel's prologue: the step kernels run up to 4096 workgroups, each would re-read all partials, and the factor would never exist on its own
+// (the tests compare it against float64 directly).
+#define RS_THREADS 256
+#define RS_MAX_BLOCKS 512
+
+static int rescale_blocks(int Ftot, int HW) {
+  const long b = ((long)Ftot * HW + RS_THREADS - 1) / RS_THREADS;
+  return (int)(b < RS_MAX_BLOCKS ? b : RS_MAX_BLOCKS);
+}
+
+__device__ __forceinline__ void rescale_cv(const floatx4* __restrict__ ns, const float* __restrict__ counter, long p, long total, int HW,
+                                           float guidance, floatx4& c, floatx4& v) {
+  const float inv = 1.f / counter[(int)(p / HW)];
+  v = ns[p] * inv;
+  c = ns[total + p] * inv;
+  v = v + guidance * (c - v);
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// part[b] = (sum dc, sum dc^2, sum dv, sum dv^2) of workgroup b's slice, dc = c - c[0], dv = v - v[0]
+__global__ void __launch_bounds__(RS_THREADS) cfg_rescale_partials_kernel(const float* __restrict__ noise_sum, const float* __restrict__ counter,
+                                                                          double* __restrict__ part, int Ftot, int HW, float guidance, long chunk) {
+  const long total = (long)Ftot * HW;
+  const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
+  floatx4 c, v;
+  rescale_cv(ns, counter, 0, total, HW, guidance, c, v);
+  const double kc = c.x, kv = v.x;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  const long p1 = min(((long)blockIdx.x + 1) * chunk, total);
+  for (long p = (long)blockIdx.x * chunk + threadIdx.x; p < p1; p += RS_THREADS) {
+    rescale_cv(ns, counter, p, total, HW, guidance, c, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double dc = (double)c[e] - kc, dv = (double)v[e] - kv;
+      s[0] += dc;
+      s[1] += dc * dc;
+      s[2] += dv;
+      s[3] += dv * dv;
+    }
+  }
+  __shared__ double red[RS_THREADS / 64][4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    s[q] = wave_sum_f64(s[q]);
+    if (lane == 0) red[wave][q] = s[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    double a = 0.0;
+    for (int w = 0; w < RS_THREADS / 64; ++w) a += red[w][threadIdx.x];
+    part[(size_t)blockIdx.x * 4 + threadIdx.x] = a;
+  }
+}
+
+// One wave: lane l adds partials l, l + 64, ... in that order, then the fixed butterfly; lane 0 writes the factor.
+__global__ void __launch_bounds__(64) cfg_rescale_finalize_kernel(const double* __restrict__ part, int nblocks, double n, float phi,
+                                                                  float* __restrict__ out_scale) {
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < nblocks; b += 64)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] += part[(size_t)b * 4 + q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) s[q] = wave_sum_f64(s[q]);
+  if (threadIdx.x == 0) {
+    double m2c = s[1] - s[0] * s[0] / n, m2v = s[3] - s[2] * s[2] / n;  // n * biased variance; NaN stays NaN
+    m2c = m2c < 0.0 ? 0.0 : m2c;
+    m2v = m2v < 0.0 ? 0.0 : m2v;
+    const double phid = (double)phi;
+    out_scale[0] = m2v == 0.0 ? 1.f : (float)(1.0 - phid + phid * sqrt(m2c / m2v));
+  }
+}
+
+extern "C" size_t md_cfg_rescale_workspace_bytes(int Ftot, int HW) {
+  return Ftot > 0 && HW > 0 ? (size_t)rescale_blocks(Ftot, HW) * 4 * sizeof(double) : 0;
+}
+
+extern "C" int md_cfg_guidance_rescale(const void* noise_sum, const void* counter, int Ftot, int HW, int halves, float guidance, float phi,
+                                       void* workspace, size_t workspace_bytes, void* out_scale, void* stream) {
+  MD_CHECK_ARG(noise_sum && counter && workspace && out_scale && Ftot > 0 && HW > 0 && halves == 2,
+               "md_cfg_guidance_rescale: bad arguments (guidance rescale needs halves == 2)");
+  MD_CHECK_ARG(((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)counter % 4) == 0 && ((uintptr_t)workspace % 8) == 0 &&
+                   ((uintptr_t)out_scale % 4) == 0,
+               "md_cfg_guidance_rescale: noise_sum needs 16-byte, workspace 8-byte, counter / out_scale 4-byte alignment");
+  MD_CHECK_ARG(__builtin_isfinite(guidance) && __builtin_isfinite(phi) && phi >= 0.f && phi <= 1.f,
+               "md_cfg_guidance_rescale: guidance must be finite and phi finite in [0, 1]");
+  MD_CHECK_ARG(workspace_bytes >= md_cfg_rescale_workspace_bytes(Ftot, HW), "md_cfg_guidance_rescale: workspace too small");
+  const long total = (long)Ftot * HW;
+  const int nb = rescale_blocks(Ftot, HW);
+  const long chunk = (total + nb - 1) / nb;
+  hipLaunchKernelGGL(cfg_rescale_partials_kernel, dim3(nb), dim3(RS_THREADS), 0, (hipStream_t)stream, (const float*)noise_sum, (const float*)counter,
+                     (double*)workspace, Ftot, HW, guidance, chunk);
+  MD_CHECK_LAUNCH("md_cfg_guidance_rescale");
+  hipLaunchKernelGGL(cfg_rescale_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, nb, (double)total * 4.0, phi,
+                     (float*)out_scale);
+  MD_CHECK_LAUNCH("md_cfg_guidance_rescale");
   return MD_OK;
 }
 

@@ -12,6 +12,7 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
     image_enc      = CLIPVisionModelWithProjection.from_pretrained(config.image_encoder_path)      (:97-99)
     scheduler      = DDIMScheduler(**infer_config.noise_scheduler_kwargs)                          (:101-102)
                      (--sampler dpmpp_2m / dpmpp_2m_sde: DPMSolverMultistepScheduler from the same kwargs; an addition)
+    pipe(..., guidance_rescale=--guidance_rescale)                                                 (an addition; default 0.0 = off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -55,6 +56,9 @@ def parse_args(argv=None):
     parser.add_argument("--sampler", choices=tuple(SAMPLERS), default="ddim",
                         help="(addition) ddim (the reference's), dpmpp_2m or dpmpp_2m_sde (DPM-Solver++ 2M, ODE / SDE), all built from "
                              "noise_scheduler_kwargs")
+    parser.add_argument("--guidance_rescale", type=float, default=0.0,
+                        help="(addition) phi of rescaled classifier-free guidance (arXiv 2305.08891 section 3.4, diffusers guidance_rescale), "
+                             "in [0, 1]; 0.0 = off (the reference's behaviour), 0.7 the paper's value.  Works with every --sampler")
     return parser.parse_args(argv)
 
 
@@ -138,7 +142,7 @@ def main(argv=None):
     ref_image_tensor = frames_to_tensor([ref_image_pil], height, width).repeat(1, 1, num_frames, 1, 1)
 
     out = pipe(ref_image_pil, ref_skel_pil, pose_pils, face_pils, hand_pils, scene_motion_npy, width, height, num_frames,
-               args.steps, args.cfg, generator=generator)
+               args.steps, args.cfg, generator=generator, guidance_rescale=args.guidance_rescale)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

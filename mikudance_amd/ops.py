@@ -302,9 +302,41 @@ def window_accumulate(pred, noise_sum, counter, window, f, ftot, hw, halves=2):
               hw, halves, _st())
 
 
-def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alpha_prev, halves=2, eta=0.0, variance_noise=None):
-    """eta > 0: `variance_noise` is the caller's N(0, 1) draw, fp16, laid out like `latents` (ftot, hw, 4)."""
+_rs_ws = {}
+
+
+def cfg_guidance_rescale(noise_sum, counter, ftot, hw, guidance, phi, out=None):
+    """Guidance rescale factor (md_cfg_guidance_rescale): fp32 (1,) device tensor 1 - phi + phi std(c) / std(v) of the guided output
+    v = u + guidance (c - u) of a CFG noise_sum (2, ftot, hw, 4); 1 when std(v) == 0.  Stays on the device: pass it as `vscale=` to
+    cfg_ddim_step / cfg_multistep_step.  The workspace is kept per (device, stream) and reused."""
+    _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
+    assert noise_sum.is_contiguous() and noise_sum.numel() == 2 * ftot * hw * 4 and counter.numel() >= ftot
+    need = _lib.load().md_cfg_rescale_workspace_bytes(ftot, hw)
+    key = (noise_sum.device, torch.cuda.current_stream().cuda_stream)
+    ws = _rs_ws.get(key)
+    if ws is None or ws.numel() * 8 < need:
+        ws = torch.empty((max(need, 1 << 14) + 7) // 8, device=noise_sum.device, dtype=torch.float64)
+        _rs_ws[key] = ws
+    if out is None:
+        out = torch.empty((1,), device=noise_sum.device, dtype=torch.float32)
+    _chk(out, "out", torch.float32)
+    _lib.call("md_cfg_guidance_rescale", noise_sum.data_ptr(), counter.data_ptr(), ftot, hw, 2, float(guidance), float(phi), ws.data_ptr(),
+              ws.numel() * 8, out.data_ptr(), _st(), meta=(f"cfg_guidance_rescale F={ftot} HW={hw}", 0.0, 8.0 * ftot * hw * 4))
+    return out
+
+
+def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alpha_prev, halves=2, eta=0.0, variance_noise=None, vscale=None):
+    """eta > 0: `variance_noise` is the caller's N(0, 1) draw, fp16, laid out like `latents` (ftot, hw, 4).
+    vscale: the fp32 device factor of cfg_guidance_rescale (md_cfg_ddim_step_scaled, any eta); None: the unscaled entry points."""
     _chk(latents, "latents"); _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
+    if vscale is not None:
+        _chk(vscale, "vscale", torch.float32)
+        if eta:
+            _chk(variance_noise, "variance_noise")
+            assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == latents.numel()
+        _lib.call("md_cfg_ddim_step_scaled", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), _p(variance_noise) if eta else 0,
+                  vscale.data_ptr(), ftot, hw, halves, float(guidance), float(alpha_t), float(alpha_prev), float(eta), _st())
+        return
     if eta:
         _chk(variance_noise, "variance_noise")
         assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == latents.numel()
@@ -316,10 +348,10 @@ def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alph
 
 
 def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, halves=2,
-                       variance_noise=None):
+                       variance_noise=None, vscale=None):
     """DPM-Solver++ multistep update (md_cfg_multistep_step): `history` is the fp32 (ftot, hw, 4) data-prediction buffer the caller keeps
     between steps; the coefficients are DPMSolverMultistepScheduler.multistep_coefficients(step_index).  c_z != 0: `variance_noise` is
-    the caller's N(0, 1) draw, fp16, laid out like `latents`."""
+    the caller's N(0, 1) draw, fp16, laid out like `latents`.  vscale: as in cfg_ddim_step (md_cfg_multistep_step_scaled)."""
     _chk(latents, "latents"); _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
     _chk(history, "history", torch.float32)
     n = ftot * hw * 4
@@ -329,6 +361,12 @@ def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance,
     if c_z:
         _chk(variance_noise, "variance_noise")
         assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == n
+    if vscale is not None:
+        _chk(vscale, "vscale", torch.float32)
+        _lib.call("md_cfg_multistep_step_scaled", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), history.data_ptr(),
+                  _p(variance_noise) if c_z else 0, vscale.data_ptr(), ftot, hw, halves, float(guidance), float(alpha_s), float(sigma_s),
+                  float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
+        return
     _lib.call("md_cfg_multistep_step", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), history.data_ptr(),
               _p(variance_noise) if c_z else 0, ftot, hw, halves, float(guidance), float(alpha_s), float(sigma_s), float(c_x), float(c_m0),
               float(c_m1), float(c_z), _st())

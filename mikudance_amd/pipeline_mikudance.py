@@ -15,6 +15,7 @@ Result-preserving reductions (proven identical on the
   * unconditional rows ignore the bank -> one attention pass with a per-row K/V source replaces two.
 `reference_reuse=False` restores the literal per-step evaluation (same results, for A/B timing).
 """
+import math
 import os
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Union
@@ -128,7 +129,7 @@ class MikuDanceVideoPipeline:
     @torch.no_grad()
     def denoise(self, latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule="uniform",
                 context_frames=None, context_stride=1, context_overlap=8, callback=None, callback_steps=1, eta=0.0, generator=None,
-                window_parallel=None):
+                window_parallel=None, guidance_rescale=0.0):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -143,8 +144,17 @@ class MikuDanceVideoPipeline:
         window_parallel     mikudance_amd.dp.WindowParallel or None: the context windows of a step (:625-668, independent UNet evaluations)
                             are shared out over the ranks of a process group, ONE all_reduce(sum) of the per-frame accumulators per step
                             (:662-674) and the CFG + DDIM update replicated on every rank; every rank returns the full latents
+        guidance_rescale    phi of rescaled classifier-free guidance (Lin et al., arXiv 2305.08891 section 3.4; diffusers `guidance_rescale` /
+                            rescale_noise_cfg), finite, in [0, 1], applied only under CFG (guidance_scale > 1): every step, after all windows
+                            (and the all_reduce) have accumulated, md_cfg_guidance_rescale takes std(c) and std(v) over the whole clip on the
+                            device and the step runs on v * (1 - phi + phi std(c) / std(v)) (md_cfg_*_step_scaled; a clip with std(v) == 0
+                            keeps v unscaled, where diffusers divides by zero).  0.0 (the default) calls the unscaled entry points: the
+                            output is bitwise that of a call without the keyword
         returns latents (1, 4, F, h, w) in the input dtype.
         """
+        phi = float(guidance_rescale)
+        if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
+            raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale}")
         dev = latents.device
         ops.require_gpu(latents, "MikuDanceVideoPipeline.denoise")
         context_frames = context_frames or self.default_context_frames
@@ -188,6 +198,10 @@ class MikuDanceVideoPipeline:
         embeds = image_prompt_embeds
         # DPM-Solver++: the previous step's data prediction, fp32, per call (under window_parallel every rank keeps its own identical copy)
         history = torch.zeros((F_, HW, 4), device=dev, dtype=torch.float32) if multistep else None
+        # guidance rescale: one fp32 factor per step, computed and consumed on the device (no host sync); phi = 0 or no CFG: the unscaled
+        # entry points, called exactly as without the keyword
+        rescale = do_cfg and phi > 0.0
+        scaled = dict(vscale=torch.empty((1,), device=dev, dtype=torch.float32)) if rescale else {}
         bank_cache = {}
         refu.skip_dead_tail = True
         den.clear_context_cache()
@@ -222,16 +236,19 @@ class MikuDanceVideoPipeline:
                     writer.clear()
                 if window_parallel is not None:
                     window_parallel.reduce(noise_sum, counter)
+                if rescale:                                              # the same factor on every rank: same buffer, same arithmetic
+                    ops.cfg_guidance_rescale(noise_sum, counter, F_, HW, guidance_scale, phi, out=scaled["vscale"])
                 if multistep:
                     z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
                     ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *sch.multistep_coefficients(step_i),
-                                           halves=nb, variance_noise=z)
+                                           halves=nb, variance_noise=z, **scaled)
                 else:
                     a_t, a_prev = sch.step_coefficients(t)
                     z = None
                     if eta > 0:
                         z = self._draw_noise(latents, generator)
-                    ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta), variance_noise=z)
+                    ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta), variance_noise=z,
+                                      **scaled)
                 if callback is not None and step_i % callback_steps == 0:
                     callback(step_i, t, self._latents_out(lat, latents))
         finally:
@@ -405,7 +422,7 @@ class MikuDanceVideoPipeline:
                  generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, output_type: Optional[str] = "tensor",
                  return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                  callback_steps: Optional[int] = 1, context_schedule="uniform", context_frames=None, context_stride=1,
-                 context_overlap=8, context_batch_size=1, interpolation_factor=1, **kwargs):
+                 context_overlap=8, context_batch_size=1, interpolation_factor=1, guidance_rescale: float = 0.0, **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -441,7 +458,8 @@ class MikuDanceVideoPipeline:
         tracker = torch.from_numpy(np.asarray(scene_motion_npy)).to(dtype=ref_image_latents.dtype, device=ref_image_latents.device)
         ref_latents = torch.cat([ref_image_latents, pose_ref_latents, pose_tgt, face_tgt, hand_tgt, tracker], dim=1)[None]
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
-                               context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator)
+                               context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
+                               guidance_rescale=guidance_rescale)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Per-clip denoising-loop time of each sampler at BASELINE.json configs[1] (768 x 768, 16 frames, CFG 3.5, full-width UNets, seeded
 weights): DDIM-20 (the headline), DPM-Solver++ 2M-10 and 2M-20.  One warm-up loop per sampler, then --reps timed loops, each bracketed
-by HIP events on the current stream; prints one JSON line.
+by HIP events on the current stream; prints one JSON line.  --guidance_rescale PHI (> 0) times every sampler with and without guidance
+rescale, the two alternated rep by rep after one warm-up loop each, and adds the cost of the rescale per clip and per step.
 
-    python tools/time_samplers.py [--reps 2] [--out FILE]
+    python tools/time_samplers.py [--reps 2] [--guidance_rescale 0.7] [--out FILE]
 """
 import argparse
 import json
@@ -23,6 +24,7 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--size", type=int, default=768)
+    ap.add_argument("--guidance_rescale", type=float, default=0.0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
@@ -36,22 +38,47 @@ def main():
                                   keep_state_dicts=False)
     h = a.size // 8
     lat, rl, emb = (t.half().to(dev) for t in synth_inputs(a.frames, h, h, ctx_len=257, ctx_dim=768, seed=100))
-    rec = {"config": {"frames": a.frames, "size": a.size, "guidance": 3.5, "reps": a.reps}, "ms_per_clip": {}}
+    phis = (0.0, a.guidance_rescale) if a.guidance_rescale > 0 else (0.0,)
+    rec = {"config": {"frames": a.frames, "size": a.size, "guidance": 3.5, "reps": a.reps, "guidance_rescale": a.guidance_rescale},
+           "ms_per_clip": {}}
+
+    def timed(pipe, steps, phi):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        pipe.denoise(lat, rl, emb, steps, 3.5, guidance_rescale=phi)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
     for name, steps in SAMPLERS:
         sch = DDIMScheduler(**SCHED_KWARGS) if name == "ddim" else DPMSolverMultistepScheduler(**SCHED_KWARGS)
         pipe = MikuDanceVideoPipeline(None, None, ref, den, sch)
-        pipe.denoise(lat, rl, emb, steps, 3.5)                      # warm-up
+        for phi in phis:
+            pipe.denoise(lat, rl, emb, steps, 3.5, guidance_rescale=phi)          # warm-up
         torch.cuda.synchronize()
-        times = []
+        times = {phi: [] for phi in phis}
         for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            pipe.denoise(lat, rl, emb, steps, 3.5)
-            e1.record()
-            torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1))
-        rec["ms_per_clip"][f"{name}-{steps}"] = {"min": min(times), "all": times}
-        print(f"{name}-{steps}: {times}", file=sys.stderr, flush=True)
+            for phi in phis:                                                         # alternated: drift hits both alike
+                times[phi].append(timed(pipe, steps, phi))
+        for phi in phis:
+            key = f"{name}-{steps}" + (f"-rescale{phi:g}" if phi else "")
+            rec["ms_per_clip"][key] = {"min": min(times[phi]), "all": times[phi]}
+            print(f"{key}: {times[phi]}", file=sys.stderr, flush=True)
+        if len(phis) == 2:
+            d = min(times[phis[1]]) - min(times[0.0])
+            rec.setdefault("rescale_cost", {})[f"{name}-{steps}"] = {"ms_per_clip": d, "ms_per_step": d / steps}
+    if len(phis) == 2:                                                               # the statistics launches alone, on this clip's shape
+        from mikudance_amd import ops
+        ns = torch.randn((2, a.frames, h * h, 4), device=dev)
+        cnt = torch.ones((a.frames,), device=dev)
+        f = ops.cfg_guidance_rescale(ns, cnt, a.frames, h * h, 3.5, a.guidance_rescale)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(200):
+            ops.cfg_guidance_rescale(ns, cnt, a.frames, h * h, 3.5, a.guidance_rescale, out=f)
+        e1.record()
+        torch.cuda.synchronize()
+        rec["rescale_statistics_us_per_step"] = e0.elapsed_time(e1) * 1000.0 / 200
     base = rec["ms_per_clip"]["ddim-20"]["min"]
     rec["ratio_to_ddim20"] = {k: v["min"] / base for k, v in rec["ms_per_clip"].items()}
     rec["device"] = torch.cuda.get_device_name(0)
