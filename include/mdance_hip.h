@@ -210,6 +210,14 @@ int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const voi
                                  const float* vscale, int Ftot, int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x,
                                  float c_m0, float c_m1, float c_z, void* stream);
 
+/* Forward noising of a clean latent, the start of video-to-video sampling (`strength` < 1): latents = fp16(a x0 + b latents), computed in
+ * fp32, in place, over n fp16 elements.  latents holds the N(0, 1) noise on entry; x0 is the clean VAE latent (already scaled by 0.18215),
+ * both packed to the (F, h*w, 4) layout of md_pack_nhwc_f16.  a = sqrt(abar_t), b = sqrt(1 - abar_t) of the first kept timestep, computed by
+ * the caller in float64.  Restates diffusers DDIMScheduler.add_noise as the img2img pipelines' prepare_latents call it.  a == 0 never reads
+ * x0: the output is then exactly b * noise even where x0 holds Inf or NaN (t = 999 of the zero-terminal-SNR table has abar = 0, so strength
+ * 1.0 starts from the noise itself).  n > 0, a and b finite and >= 0, both pointers 2-byte aligned; MD_ERR_ARG otherwise. */
+int md_add_noise_f16(void* latents, const void* x0, long n, float a, float b, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

@@ -54,6 +54,7 @@ SIGNATURES = {
     "md_cfg_ddim_step_scaled": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P]),
     "md_cfg_multistep_step_scaled": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
                                              c_float, P]),
+    "md_add_noise_f16": (c_int, [P, P, c_long, c_float, c_float, P]),
 }
 
 _lib = None

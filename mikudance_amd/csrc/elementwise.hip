@@ -364,6 +364,27 @@ extern "C" int md_cfg_guidance_rescale(const void* noise_sum, const void* counte
   return MD_OK;
 }
 
+// ---- forward noising of a clean latent (video-to-video start; diffusers DDIMScheduler.add_noise) ----------------------------------
+//   latents = fp16(a x0 + b latents)      a = sqrt(abar_t), b = sqrt(1 - abar_t) from the host; fp32 arithmetic, one rounding
+// latents holds the noise on entry and is updated in place.  a == 0 (t = 999 of the zero-terminal-SNR table) never reads x0: the output is
+// then b * noise exactly, whatever x0 holds (0 * Inf would be NaN).  Runs once per clip: a plain grid-stride loop over fp16 elements.
+__global__ void add_noise_kernel(half_t* __restrict__ lat, const half_t* __restrict__ x0, long n, float a, float b) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float z = (float)lat[i];
+    lat[i] = (half_t)(a != 0.f ? a * (float)x0[i] + b * z : b * z);
+  }
+}
+
+extern "C" int md_add_noise_f16(void* latents, const void* x0, long n, float a, float b, void* stream) {
+  MD_CHECK_ARG(latents && x0 && n > 0, "md_add_noise_f16: bad arguments");
+  MD_CHECK_ARG(((uintptr_t)latents % 2) == 0 && ((uintptr_t)x0 % 2) == 0, "md_add_noise_f16: latents / x0 need 2-byte alignment");
+  MD_CHECK_ARG(__builtin_isfinite(a) && __builtin_isfinite(b) && a >= 0.f && b >= 0.f, "md_add_noise_f16: a and b must be finite and >= 0");
+  const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+  hipLaunchKernelGGL(add_noise_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const half_t*)x0, n, a, b);
+  MD_CHECK_LAUNCH("md_add_noise_f16");
+  return MD_OK;
+}
+
 // ---- generic strided scatter of NHWC fp16 -> any layout/dtype (API boundary: UNet.forward returns NCFHW) ---------------
 template <typename T>
 __global__ void unpack_nhwc_kernel(const half_t* __restrict__ src, T* __restrict__ dst, long total, int F, long sB, long sF, long sC, long sY, long sX,

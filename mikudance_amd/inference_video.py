@@ -13,6 +13,7 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
     scheduler      = DDIMScheduler(**infer_config.noise_scheduler_kwargs)                          (:101-102)
                      (--sampler dpmpp_2m / dpmpp_2m_sde: DPMSolverMultistepScheduler from the same kwargs; an addition)
     pipe(..., guidance_rescale=--guidance_rescale)                                                 (an addition; default 0.0 = off)
+    pipe(..., video=read_frames(--init_video), strength=--strength)                                (an addition: video-to-video)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -59,7 +60,17 @@ def parse_args(argv=None):
     parser.add_argument("--guidance_rescale", type=float, default=0.0,
                         help="(addition) phi of rescaled classifier-free guidance (arXiv 2305.08891 section 3.4, diffusers guidance_rescale), "
                              "in [0, 1]; 0.0 = off (the reference's behaviour), 0.7 the paper's value.  Works with every --sampler")
-    return parser.parse_args(argv)
+    parser.add_argument("--init_video",
+                        help="(addition) video-to-video: a clip to start from, read like the pose video (a frame directory, .npy / .npz, .gif / "
+                             ".png, or an .mp4 of this package's own writer; convert H.264 first with `python -m mikudance_amd.io_utils "
+                             "convert`).  Its frame count must equal the pose video's")
+    parser.add_argument("--strength", type=float, default=1.0,
+                        help="(addition) with --init_video: the share of the schedule that is run, in (0, 1] (diffusers img2img strength); "
+                             "1.0 starts from pure noise")
+    args = parser.parse_args(argv)
+    if args.strength != 1.0 and args.init_video is None:
+        parser.error(f"--strength {args.strength} needs --init_video")
+    return args
 
 
 def _none(v):
@@ -133,6 +144,11 @@ def main(argv=None):
     scene_motion_npy = camera_to_scene_motion([w2c_npy[k] for k in range(w2c_npy.shape[0])], [c2w_npy[k] for k in range(c2w_npy.shape[0])],
                                               [3.2, 3.2, 1.6, 1.6], depth_map, width // 8, height // 8, False)
     print("Total frames: {}".format(num_frames))
+    init_pils = None
+    if args.init_video is not None:
+        init_pils = read_frames(args.init_video)
+        if len(init_pils) != num_frames:
+            raise ValueError(f"--init_video has {len(init_pils)} frames, the pose video {num_frames}: they must be equal")
 
     skel_name = os.path.splitext(os.path.basename(config.tgt_pose_path))[0]
     ref_name = os.path.splitext(os.path.basename(config.ref_image_path))[0]
@@ -142,7 +158,8 @@ def main(argv=None):
     ref_image_tensor = frames_to_tensor([ref_image_pil], height, width).repeat(1, 1, num_frames, 1, 1)
 
     out = pipe(ref_image_pil, ref_skel_pil, pose_pils, face_pils, hand_pils, scene_motion_npy, width, height, num_frames,
-               args.steps, args.cfg, generator=generator, guidance_rescale=args.guidance_rescale)
+               args.steps, args.cfg, generator=generator, guidance_rescale=args.guidance_rescale,
+               video=init_pils, strength=args.strength)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

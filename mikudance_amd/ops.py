@@ -325,6 +325,15 @@ def cfg_guidance_rescale(noise_sum, counter, ftot, hw, guidance, phi, out=None):
     return out
 
 
+def add_noise(latents, x0, a, b):
+    """In place: latents = fp16(a * x0 + b * latents) (md_add_noise_f16), both contiguous fp16 tensors of the same size; a = sqrt(abar_t),
+    b = sqrt(1 - abar_t).  a == 0 leaves exactly b * latents, whatever x0 holds."""
+    _chk(latents, "latents"); _chk(x0, "x0")
+    assert latents.is_contiguous() and x0.is_contiguous() and latents.numel() == x0.numel() and latents.numel() > 0
+    _lib.call("md_add_noise_f16", latents.data_ptr(), x0.data_ptr(), latents.numel(), float(a), float(b), _st())
+    return latents
+
+
 def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alpha_prev, halves=2, eta=0.0, variance_noise=None, vscale=None):
     """eta > 0: `variance_noise` is the caller's N(0, 1) draw, fp16, laid out like `latents` (ftot, hw, 4).
     vscale: the fp32 device factor of cfg_guidance_rescale (md_cfg_ddim_step_scaled, any eta); None: the unscaled entry points."""

@@ -129,7 +129,7 @@ class MikuDanceVideoPipeline:
     @torch.no_grad()
     def denoise(self, latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule="uniform",
                 context_frames=None, context_stride=1, context_overlap=8, callback=None, callback_steps=1, eta=0.0, generator=None,
-                window_parallel=None, guidance_rescale=0.0):
+                window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -150,11 +150,20 @@ class MikuDanceVideoPipeline:
                             device and the step runs on v * (1 - phi + phi std(c) / std(v)) (md_cfg_*_step_scaled; a clip with std(v) == 0
                             keeps v unscaled, where diffusers divides by zero).  0.0 (the default) calls the unscaled entry points: the
                             output is bitwise that of a call without the keyword
+        init_latents        video-to-video (diffusers img2img / video2video `strength`): a clean VAE latent of latents' shape, already scaled by
+                            0.18215.  The loop starts at the first timestep kept by scheduler.get_timesteps(num_inference_steps, strength)
+                            from md_add_noise_f16(x0 = init_latents, noise = latents) and runs the kept steps only (callback's step_i counts
+                            them from 0; DPM-Solver++ starts first order there, set_begin_index).  No new collective or host sync per step.
+                            strength 1.0 starts at t = 999 where abar = 0: bitwise the plain loop, whatever init_latents holds
+        strength            finite, in (0, 1]; < 1 needs init_latents.  None of it is read without init_latents
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         phi = float(guidance_rescale)
         if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
             raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale}")
+        self._check_strength(strength, init_latents is not None, num_inference_steps)
+        if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
+            raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         dev = latents.device
         ops.require_gpu(latents, "MikuDanceVideoPipeline.denoise")
         context_frames = context_frames or self.default_context_frames
@@ -171,6 +180,10 @@ class MikuDanceVideoPipeline:
                              "DPMSolverMultistepScheduler(algorithm_type='sde-dpmsolver++')")
         sch.set_timesteps(num_inference_steps)
         timesteps = [int(t) for t in sch.timesteps]
+        t_start = 0
+        if init_latents is not None:                                     # video-to-video: the tail of the schedule (DPM: begin index set)
+            timesteps = [int(t) for t in sch.get_timesteps(num_inference_steps, strength)[0]]
+            t_start = num_inference_steps - len(timesteps)
         _, c, F_, hh, ww = latents.shape
         HW = hh * ww
         writer = ReferenceAttentionControl(refu, do_classifier_free_guidance=do_cfg, mode="write", batch_size=1, fusion_blocks="full")
@@ -180,6 +193,10 @@ class MikuDanceVideoPipeline:
         # internal latents: (F, h, w, 4) fp16 NHWC frames
         st = latents.stride()
         lat = ops.pack_nhwc(latents, F_, F_, (0, st[2], st[1], st[3], st[4]), 0, c, 4, hh, ww)
+        if init_latents is not None:                                     # noise x0 to the first kept timestep, every rank the same
+            x0 = init_latents.to(dev)
+            sx = x0.stride()
+            ops.add_noise(lat, ops.pack_nhwc(x0, F_, F_, (0, sx[2], sx[1], sx[3], sx[4]), 0, c, 4, hh, ww), *sch.noise_coefficients(timesteps[0]))
         noise_sum = torch.zeros((nb, F_, HW, 4), device=dev, dtype=torch.float32)
         counter = torch.zeros((F_,), device=dev, dtype=torch.float32)
         windows = [list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
@@ -240,7 +257,7 @@ class MikuDanceVideoPipeline:
                     ops.cfg_guidance_rescale(noise_sum, counter, F_, HW, guidance_scale, phi, out=scaled["vscale"])
                 if multistep:
                     z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
-                    ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *sch.multistep_coefficients(step_i),
+                    ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *sch.multistep_coefficients(t_start + step_i),
                                            halves=nb, variance_noise=z, **scaled)
                 else:
                     a_t, a_prev = sch.step_coefficients(t)
@@ -258,6 +275,18 @@ class MikuDanceVideoPipeline:
             den.clear_context_cache()
             refu.clear_context_cache()
         return self._latents_out(lat, latents)
+
+    @staticmethod
+    def _check_strength(strength, has_init, num_inference_steps):
+        """The video-to-video argument checks (diffusers' wording for a schedule with no step left)."""
+        s = float(strength)
+        if not (math.isfinite(s) and 0.0 < s <= 1.0):
+            raise ValueError(f"strength must be a finite number in (0, 1], got {strength}")
+        if s < 1.0 and not has_init:
+            raise ValueError(f"strength={strength} < 1 needs a clip to start from: pass init_latents (denoise) or video (__call__)")
+        if has_init and min(int(num_inference_steps * strength), num_inference_steps) < 1:
+            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
+                             f"{min(int(num_inference_steps * strength), num_inference_steps)} which is < 1 and not appropriate for this pipeline.")
 
     @staticmethod
     def _draw_noise(latents, generator):
@@ -422,13 +451,18 @@ class MikuDanceVideoPipeline:
                  generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, output_type: Optional[str] = "tensor",
                  return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                  callback_steps: Optional[int] = 1, context_schedule="uniform", context_frames=None, context_stride=1,
-                 context_overlap=8, context_batch_size=1, interpolation_factor=1, guidance_rescale: float = 0.0, **kwargs):
+                 context_overlap=8, context_batch_size=1, interpolation_factor=1, guidance_rescale: float = 0.0, video=None, strength: float = 1.0,
+                 **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
         # no behaviour to reproduce: the windows are evaluated one at a time here, which is what the sum over a batch would be.
         if context_batch_size < 1:
             raise ValueError(f"context_batch_size must be >= 1, got {context_batch_size}")
+        # video / strength: video-to-video (denoise's init_latents), `video` = video_length PIL frames preprocessed like the reference image
+        if video is not None and len(video) != video_length:
+            raise ValueError(f"video has {len(video)} frames, video_length is {video_length}: they must be equal")
+        self._check_strength(strength, video is not None, num_inference_steps)
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -447,19 +481,22 @@ class MikuDanceVideoPipeline:
         f = video_length
         rep = lambda z: z.unsqueeze(1).repeat(1, f, 1, 1, 1).reshape((-1,) + tuple(z.shape[1:]))
         # all 3F + 2 condition images in ONE pass through the VAE (reference :456-549 encodes them one by one, same arithmetic per image)
+        # (and the video-to-video frames after them, in the same pass; the noise above was drawn first, so the generator stream is unchanged)
         groups = [list(tgt_pose_images), list(tgt_face_images), list(tgt_hand_images)]
         lat_all = self._encode_many([_pil_to_tensor(ref_image, height, width, True), _pil_to_tensor(ref_skel_image, height, width, False)]
-                                    + [_pil_to_tensor(im, height, width, False) for grp in groups for im in grp])
+                                    + [_pil_to_tensor(im, height, width, False) for grp in groups for im in grp]
+                                    + [_pil_to_tensor(im, height, width, True) for im in ([] if video is None else video)])
         ref_image_latents, pose_ref_latents = rep(lat_all[0:1]), rep(lat_all[1:2])
         o = [2]
         for grp in groups:
             o.append(o[-1] + len(grp))
         pose_tgt, face_tgt, hand_tgt = (lat_all[a:b] for a, b in zip(o[:-1], o[1:]))
+        init_latents = None if video is None else lat_all[o[-1]:o[-1] + f].permute(1, 0, 2, 3)[None]     # (1, 4, F, h, w)
         tracker = torch.from_numpy(np.asarray(scene_motion_npy)).to(dtype=ref_image_latents.dtype, device=ref_image_latents.device)
         ref_latents = torch.cat([ref_image_latents, pose_ref_latents, pose_tgt, face_tgt, hand_tgt, tracker], dim=1)[None]
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
                                context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
-                               guidance_rescale=guidance_rescale)
+                               guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)

@@ -5,7 +5,10 @@ The table is 1000 fp32 scalars on the host; the per-step arithmetic on the laten
 md_cfg_ddim_step (fused with window averaging and classifier-free guidance).
 
 DPMSolverMultistepScheduler -- DPM-Solver++ (Lu et al., arXiv 2211.01095) orders 1 / 2, ODE or SDE, restated on the same discrete
-table (not pinned to a diffusers version): every step is ONE linear update with host scalars, run by md_cfg_multistep_step."""
+table (not pinned to a diffusers version): every step is ONE linear update with host scalars, run by md_cfg_multistep_step.
+
+Both take diffusers' video-to-video / img2img entry points: get_timesteps(num_inference_steps, strength) keeps the tail of the schedule and
+add_noise(original_samples, noise, timesteps) noises a clean latent to its first timestep (md_add_noise_f16)."""
 import inspect
 import math
 from dataclasses import dataclass
@@ -35,13 +38,59 @@ def _linear_betas(beta_start, beta_end, num_train_timesteps, rescale_betas_zero_
     return betas
 
 
+class _StrengthMixin:
+    """The video-to-video start shared by both schedulers (diffusers img2img / video2video pipelines): keep only the tail of the schedule
+    and noise the clean latent to its first timestep."""
+
+    def get_timesteps(self, num_inference_steps: int, strength: float):
+        """diffusers StableDiffusionImg2ImgPipeline.get_timesteps, literally: init = min(int(N * strength), N), t_start = max(N - init, 0),
+        the kept list is timesteps[t_start * order:] (and a scheduler with set_begin_index is told t_start * order).  The float product and
+        int() stay as diffusers writes them (0.57 * 100 -> 56 steps).  Call after set_timesteps(num_inference_steps).
+        Returns (timesteps, num_inference_steps - t_start)."""
+        if self.num_inference_steps != num_inference_steps:
+            raise ValueError(f"get_timesteps({num_inference_steps}, ...): call set_timesteps({num_inference_steps}) first "
+                             f"(the schedule has {self.num_inference_steps} steps)")
+        init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+        t_start = max(num_inference_steps - init_timestep, 0)
+        timesteps = self.timesteps[t_start * self.order:]
+        if hasattr(self, "set_begin_index") and len(timesteps):
+            self.set_begin_index(t_start * self.order)
+        return timesteps, num_inference_steps - t_start
+
+    def noise_coefficients(self, timestep):
+        """(sqrt(abar_t), sqrt(1 - abar_t)) as Python floats, computed in float64 from the fp32 table: the (a, b) of md_add_noise_f16."""
+        abar = float(self.alphas_cumprod[int(timestep)])
+        return math.sqrt(abar), math.sqrt(1.0 - abar)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' add_noise(original_samples, noise, timesteps) = sqrt(abar_t) x0 + sqrt(1 - abar_t) noise on GPU tensors of any shape,
+        run by md_add_noise_f16 (fp32 arithmetic, fp16 operands and result, returned in original_samples' dtype).  `timesteps`: one timestep,
+        or one per entry of original_samples' first dimension.  t = 999 (abar = 0) returns the noise exactly."""
+        from . import ops
+        if not original_samples.is_cuda or not noise.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.add_noise: tensors must live on the GPU (no CPU path)")
+        if noise.shape != original_samples.shape:
+            raise ValueError(f"add_noise: noise {tuple(noise.shape)} and original_samples {tuple(original_samples.shape)} differ in shape")
+        ts = [int(t) for t in torch.as_tensor(timesteps).reshape(-1).tolist()]
+        if len(ts) != 1 and (original_samples.dim() == 0 or len(ts) != original_samples.shape[0]):
+            raise ValueError(f"add_noise: {len(ts)} timesteps for original_samples of shape {tuple(original_samples.shape)}")
+        out = noise.detach().to(torch.float16).contiguous().clone()
+        x0 = original_samples.detach().to(device=out.device, dtype=torch.float16).contiguous()
+        if len(ts) == 1:
+            ops.add_noise(out, x0, *self.noise_coefficients(ts[0]))
+        else:
+            for k, t in enumerate(ts):
+                ops.add_noise(out[k], x0[k], *self.noise_coefficients(t))
+        return out.to(original_samples.dtype)
+
+
 @dataclass
 class DDIMSchedulerOutput:
     prev_sample: torch.Tensor
     pred_original_sample: torch.Tensor = None
 
 
-class DDIMScheduler:
+class DDIMScheduler(_StrengthMixin):
     order = 1
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
@@ -114,7 +163,7 @@ class DPMSolverMultistepSchedulerOutput:
     prev_sample: torch.Tensor
 
 
-class DPMSolverMultistepScheduler:
+class DPMSolverMultistepScheduler(_StrengthMixin):
     """DPM-Solver++ multistep sampling on MikuDance's zero-terminal-SNR schedule (diffusers keyword names; the built subset is
     solver_order 1 / 2, algorithm_type dpmsolver++ / sde-dpmsolver++, solver_type midpoint / heun, v-prediction, trailing spacing,
     linear betas, final_sigmas_type "zero").
@@ -124,7 +173,8 @@ class DPMSolverMultistepScheduler:
         m0 = alpha_s x - sigma_s v,   x' = c_x x + c_m0 m0 + c_m1 m1 + c_z z     (m1 = the previous step's m0, z ~ N(0, 1))
     The coefficients use e^-h = (alpha_s sigma_t) / (sigma_s alpha_t) in float64 -- exactly 0 at the first step (alpha_s = 0) and at the
     last (sigma_t = 0) -- so lambda = log(alpha / sigma) is never formed where it is infinite.  Step 0 and the last step are order 1;
-    rho = h / h_0 is 0 when the previous point is the lambda = -inf endpoint (step 1), its order-1 limit."""
+    rho = h / h_0 is 0 when the previous point is the lambda = -inf endpoint (step 1), its order-1 limit.  After set_begin_index(b) step b
+    is order 1 too (sampling starts there)."""
     order = 1
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02, beta_schedule: str = "linear",
@@ -165,6 +215,7 @@ class DPMSolverMultistepScheduler:
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
         self._coeffs = []
+        self._begin_index = 0
         self._reset_state()
 
     @classmethod
@@ -188,10 +239,28 @@ class DPMSolverMultistepScheduler:
         ratio = self.num_train_timesteps / num_inference_steps
         ts = np.round(np.arange(self.num_train_timesteps, 0, -ratio)).astype(np.int64) - 1
         self.timesteps = torch.from_numpy(ts)
+        self._begin_index = 0
         self._coeffs = self._coefficient_table([int(t) for t in ts])
         self._reset_state()
 
-    def _coefficient_table(self, ts):
+    @property
+    def begin_index(self):
+        return self._begin_index
+
+    def set_begin_index(self, begin_index: int = 0):
+        """diffusers' name: sampling starts at step `begin_index` of the current schedule (video-to-video, get_timesteps).  That step is
+        first order -- there is no history before it -- and every other row, the final-step rule included (it stays keyed on the full
+        schedule), is the full table's.  multistep_coefficients keeps absolute indices; set_timesteps resets the index to 0."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        begin_index = int(begin_index)
+        if not 0 <= begin_index < len(self.timesteps):
+            raise ValueError(f"begin_index {begin_index} is outside the schedule of {len(self.timesteps)} steps")
+        self._begin_index = begin_index
+        self._coeffs = self._coefficient_table([int(t) for t in self.timesteps], begin_index)
+        self._reset_state()
+
+    def _coefficient_table(self, ts, begin=0):
         n = len(ts)
         abar = [float(self.alphas_cumprod[t]) for t in ts] + [1.0]           # final_sigmas_type "zero": alpha = 1, sigma = 0
         al = [math.sqrt(a) for a in abar]
@@ -201,7 +270,7 @@ class DPMSolverMultistepScheduler:
         for i in range(n):
             a_s, s_s, a_t, s_t = al[i], sg[i], al[i + 1], sg[i + 1]
             emh = (a_s * s_t) / (s_s * a_t)                                    # e^-h; 0 at both ends
-            second = self.config["solver_order"] == 2 and 0 < i < n - 1
+            second = self.config["solver_order"] == 2 and 0 < i < n - 1 and i != begin          # begin: no history yet
             rho = math.log(emh) / math.log(prev_emh) if second and prev_emh > 0.0 else 0.0    # h / h_0; 0 after the lambda = -inf point
             if sde:
                 c_x = s_t / s_s * emh

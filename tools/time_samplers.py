@@ -2,9 +2,11 @@
 """Per-clip denoising-loop time of each sampler at BASELINE.json configs[1] (768 x 768, 16 frames, CFG 3.5, full-width UNets, seeded
 weights): DDIM-20 (the headline), DPM-Solver++ 2M-10 and 2M-20.  One warm-up loop per sampler, then --reps timed loops, each bracketed
 by HIP events on the current stream; prints one JSON line.  --guidance_rescale PHI (> 0) times every sampler with and without guidance
-rescale, the two alternated rep by rep after one warm-up loop each, and adds the cost of the rescale per clip and per step.
+rescale, the two alternated rep by rep after one warm-up loop each, and adds the cost of the rescale per clip and per step.  --strength S
+(< 1) does the same for video-to-video (denoise(init_latents=, strength=S) against the plain loop) and adds the VAE encode of the F extra
+frames that __call__(video=) puts in front of the loop (sd-vae-ft-mse geometry, seeded weights, median of three after a warm-up).
 
-    python tools/time_samplers.py [--reps 2] [--guidance_rescale 0.7] [--out FILE]
+    python tools/time_samplers.py [--reps 2] [--guidance_rescale 0.7 | --strength 0.5] [--out FILE]
 """
 import argparse
 import json
@@ -25,8 +27,11 @@ def main():
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--size", type=int, default=768)
     ap.add_argument("--guidance_rescale", type=float, default=0.0)
+    ap.add_argument("--strength", type=float, default=1.0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.guidance_rescale > 0 and a.strength < 1:
+        ap.error("--guidance_rescale and --strength: one at a time")
     assert torch.cuda.is_available(), "needs an MI355X"
     from mikudance_amd import DDIMScheduler, DPMSolverMultistepScheduler, MikuDanceVideoPipeline, _lib
     from mikudance_amd.selftest import SCHED_KWARGS, build_models
@@ -39,13 +44,19 @@ def main():
     h = a.size // 8
     lat, rl, emb = (t.half().to(dev) for t in synth_inputs(a.frames, h, h, ctx_len=257, ctx_dim=768, seed=100))
     phis = (0.0, a.guidance_rescale) if a.guidance_rescale > 0 else (0.0,)
-    rec = {"config": {"frames": a.frames, "size": a.size, "guidance": 3.5, "reps": a.reps, "guidance_rescale": a.guidance_rescale},
-           "ms_per_clip": {}}
+    if a.strength < 1:                                                               # a clean latent to start from
+        init = (torch.randn(lat.shape, generator=torch.Generator().manual_seed(101)) * 0.8).half().to(dev)
+        phis = (0.0, ("strength", a.strength))
+    rec = {"config": {"frames": a.frames, "size": a.size, "guidance": 3.5, "reps": a.reps, "guidance_rescale": a.guidance_rescale,
+                      "strength": a.strength}, "ms_per_clip": {}}
+
+    def kwargs(phi):
+        return dict(init_latents=init, strength=phi[1]) if isinstance(phi, tuple) else dict(guidance_rescale=phi)
 
     def timed(pipe, steps, phi):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        pipe.denoise(lat, rl, emb, steps, 3.5, guidance_rescale=phi)
+        pipe.denoise(lat, rl, emb, steps, 3.5, **kwargs(phi))
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1)
@@ -54,20 +65,44 @@ def main():
         sch = DDIMScheduler(**SCHED_KWARGS) if name == "ddim" else DPMSolverMultistepScheduler(**SCHED_KWARGS)
         pipe = MikuDanceVideoPipeline(None, None, ref, den, sch)
         for phi in phis:
-            pipe.denoise(lat, rl, emb, steps, 3.5, guidance_rescale=phi)          # warm-up
+            pipe.denoise(lat, rl, emb, steps, 3.5, **kwargs(phi))                   # warm-up
         torch.cuda.synchronize()
         times = {phi: [] for phi in phis}
         for _ in range(a.reps):
             for phi in phis:                                                         # alternated: drift hits both alike
                 times[phi].append(timed(pipe, steps, phi))
         for phi in phis:
-            key = f"{name}-{steps}" + (f"-rescale{phi:g}" if phi else "")
+            key = f"{name}-{steps}" + (f"-strength{phi[1]:g}" if isinstance(phi, tuple) else f"-rescale{phi:g}" if phi else "")
             rec["ms_per_clip"][key] = {"min": min(times[phi]), "all": times[phi]}
             print(f"{key}: {times[phi]}", file=sys.stderr, flush=True)
         if len(phis) == 2:
             d = min(times[phis[1]]) - min(times[0.0])
-            rec.setdefault("rescale_cost", {})[f"{name}-{steps}"] = {"ms_per_clip": d, "ms_per_step": d / steps}
-    if len(phis) == 2:                                                               # the statistics launches alone, on this clip's shape
+            if isinstance(phis[1], tuple):
+                rec.setdefault("strength_ratio", {})[f"{name}-{steps}"] = min(times[phis[1]]) / min(times[0.0])
+            else:
+                rec.setdefault("rescale_cost", {})[f"{name}-{steps}"] = {"ms_per_clip": d, "ms_per_step": d / steps}
+    if a.strength < 1:                                                               # __call__(video=): F more images through the VAE
+        import time
+        from mikudance_amd import AutoencoderKL
+        from mikudance_amd.synth import synth_state_dict
+        vae = AutoencoderKL()
+        vae.load_state_dict(synth_state_dict({k: tuple(v.shape) for k, v in vae.state_dict().items()}, seed=77), strict=True)
+        vae = vae.half().to(dev).eval()
+        vpipe = MikuDanceVideoPipeline(vae, None, None, None, None)
+        g = torch.Generator(device=dev).manual_seed(7)
+        imgs = (torch.rand(a.frames, 3, a.size, a.size, device=dev, generator=g) * 2 - 1).half()
+        views = [imgs[i:i + 1] for i in range(a.frames)]
+        times = []
+        with torch.no_grad():
+            for _ in range(4):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                vpipe._encode_many(views)
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) * 1e3)
+        rec["video_encode_ms_per_clip"] = sorted(times[1:])[1]
+        del vae, vpipe
+    if len(phis) == 2 and not isinstance(phis[1], tuple):                                                               # the statistics launches alone, on this clip's shape
         from mikudance_amd import ops
         ns = torch.randn((2, a.frames, h * h, 4), device=dev)
         cnt = torch.ones((a.frames,), device=dev)
