@@ -164,6 +164,18 @@ int md_concat_channels_f16(const void* a, int Ca, const void* b, int Cb, void* o
 int md_window_accumulate(const void* pred, void* noise_sum, void* counter, const int* window, int f, int Ftot, int HW,
                          int halves, void* stream);
 
+/* Weighted window fusion (context_fuse="pyramid"; the triangular per-slot weights of diffusers' FreeNoise weighting_scheme="pyramid" and
+ * AnimateDiff-Evolved's pyramid fuse): noise_pred[:, :, window[i]] += weights[i] * pred[:, :, i]; counter[window[i]] += weights[i].
+ * weights: f fp32 in device memory, one per slot, already divided by the frame's total weight over every window of the step, so that
+ * noise_sum ends as the weighted mean and counter as 1 up to rounding; every consumer of md_window_accumulate's buffers works unchanged.
+ * Buffers and slot rule as md_window_accumulate (slots unique or -1 = skipped; a slot >= Ftot is skipped too).  fp32 arithmetic, the
+ * product and the sum rounded separately (no fma), so a window's share is the same number on every rank of a window-parallel run; with
+ * every weight 1.0 the result is md_window_accumulate's bit for bit.  No pointer may be NULL; pred 8-byte, noise_sum 16-byte, counter /
+ * window / weights 4-byte aligned; f > 0, Ftot >= f, HW > 0, halves 1 or 2; MD_ERR_ARG otherwise.
+ * The place of src/pipelines/pipeline_mikudance.py:662-664 when the caller asks for weighted fusion (an addition). */
+int md_window_accumulate_weighted(const void* pred, void* noise_sum, void* counter, const int* window, const float* weights, int f,
+                                  int Ftot, int HW, int halves, void* stream);
+
 /* (noise_pred / counter) -> classifier-free guidance -> DDIM v-prediction step (eta 0), latents updated in place.
  * src/pipelines/pipeline_mikudance.py:670-678 + diffusers DDIMScheduler.step. */
 int md_cfg_ddim_step(void* latents, const void* noise_sum, const void* counter, int Ftot, int HW, int halves,

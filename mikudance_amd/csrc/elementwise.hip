@@ -98,6 +98,65 @@ extern "C" int md_window_accumulate(const void* pred, void* noise_sum, void* cou
   return MD_OK;
 }
 
+// ---- weighted window accumulate: noise_sum[half][win[i]] += w[i] * pred[half*f + i], counter[win[i]] += w[i] ------------------
+// The pyramid fuse (context_fuse="pyramid"): w[i] is slot i's triangular weight already divided by the frame's total over every window
+// of the step (the host normalises, float64 -> fp32), so noise_sum ends up as the weighted MEAN and counter as 1 up to rounding.
+// Same buffers, same slot rule (unique or -1) and therefore the same no-atomics argument as window_accumulate_kernel.
+// One thread owns one pixel of one slot: 4 fp16 = one 8-byte load per clip-half, 4 fp32 = one 16-byte load and one 16-byte store per
+// clip-half, block row blockIdx.y = slot; the loads of both halves are issued before the first store.
+// The product and the sum are rounded SEPARATELY (fp contraction is switched off in the kernel body: no fma): a window's share w * p then has
+// the same fp32 value whether it lands on this rank's accumulator or arrives through WindowParallel's all-reduce, so a frame that lies in
+// at most two windows gets the same bits on one rank and on many (a + b is commutative; fma(w2, p2, w1 p1) is not fl(w1 p1) + fl(w2 p2)).
+// With w == 1 the product is exact and the update is window_accumulate_kernel's s + p, bit for bit.
+template <int HALVES>
+__global__ __launch_bounds__(256) void window_accumulate_weighted_kernel(const half4_t* __restrict__ pred, floatx4* __restrict__ noise_sum,
+                                                                         float* __restrict__ counter, const int* __restrict__ win,
+                                                                         const float* __restrict__ weights, int f, int Ftot, int HW) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.y;  // frame slot inside the window
+  const int fr = win[i];
+  if (fr < 0 || fr >= Ftot) return;  // -1: an earlier duplicate (last occurrence wins); >= Ftot never leaves the host, and is not followed
+  const float w = weights[i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) counter[fr] += w;
+  const int px = blockIdx.x * blockDim.x + threadIdx.x;
+  if (px >= HW) return;
+  half4_t p[HALVES];
+  floatx4 s[HALVES];
+#pragma unroll
+  for (int h = 0; h < HALVES; ++h) {
+    p[h] = pred[(size_t)(h * f + i) * HW + px];
+    s[h] = noise_sum[((size_t)h * Ftot + fr) * HW + px];
+  }
+#pragma unroll
+  for (int h = 0; h < HALVES; ++h) {
+    floatx4 o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float share = w * (float)p[h][c];
+      o[c] = s[h][c] + share;
+    }
+    noise_sum[((size_t)h * Ftot + fr) * HW + px] = o;
+  }
+}
+
+extern "C" int md_window_accumulate_weighted(const void* pred, void* noise_sum, void* counter, const int* window, const float* weights, int f,
+                                             int Ftot, int HW, int halves, void* stream) {
+  MD_CHECK_ARG(pred && noise_sum && counter && window && weights, "md_window_accumulate_weighted: null pointer");
+  MD_CHECK_ARG(f > 0 && f <= 65535 && Ftot >= f && HW > 0 && (halves == 1 || halves == 2), "md_window_accumulate_weighted: bad arguments");
+  MD_CHECK_ARG((uintptr_t)pred % 8 == 0 && (uintptr_t)noise_sum % 16 == 0 && (uintptr_t)counter % 4 == 0 && (uintptr_t)window % 4 == 0 &&
+                   (uintptr_t)weights % 4 == 0,
+               "md_window_accumulate_weighted: pred must be 8-byte, noise_sum 16-byte, counter / window / weights 4-byte aligned");
+  const dim3 grid(cdiv(HW, 256), f);
+  if (halves == 2)
+    hipLaunchKernelGGL(window_accumulate_weighted_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, (const half4_t*)pred, (floatx4*)noise_sum,
+                       (float*)counter, window, weights, f, Ftot, HW);
+  else
+    hipLaunchKernelGGL(window_accumulate_weighted_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, (const half4_t*)pred, (floatx4*)noise_sum,
+                       (float*)counter, window, weights, f, Ftot, HW);
+  MD_CHECK_LAUNCH("md_window_accumulate_weighted");
+  return MD_OK;
+}
+
 // ---- CFG combine + DDIM v-prediction step (eta = 0) --------------------------------------------------------------------
 //   v   = u + s (c - u),  u = sum_u / cnt, c = sum_c / cnt                         pipeline_mikudance.py:670-674
 //   x0  = sqrt(a_t) x - sqrt(1-a_t) v ;  eps = sqrt(a_t) v + sqrt(1-a_t) x

@@ -14,6 +14,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      (--sampler dpmpp_2m / dpmpp_2m_sde: DPMSolverMultistepScheduler from the same kwargs; an addition)
     pipe(..., guidance_rescale=--guidance_rescale)                                                 (an addition; default 0.0 = off)
     pipe(..., video=read_frames(--init_video), strength=--strength)                                (an addition: video-to-video)
+    pipe(..., context_schedule=, context_fuse=, context_frames=, context_overlap=)                 (additions: how a clip longer than the
+                     temporal context is cut into windows and how their overlaps are merged; defaults = the reference's call)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -67,6 +69,15 @@ def parse_args(argv=None):
     parser.add_argument("--strength", type=float, default=1.0,
                         help="(addition) with --init_video: the share of the schedule that is run, in (0, 1] (diffusers img2img strength); "
                              "1.0 starts from pure noise")
+    parser.add_argument("--context_schedule", choices=("uniform", "uniform_open"), default="uniform",
+                        help="(addition) windows of a clip longer than --context_frames: uniform (the reference's: a closed loop, windows "
+                             "wrap round the end of the clip) or uniform_open (no window wraps; fewer windows)")
+    parser.add_argument("--context_fuse", choices=("flat", "pyramid"), default="flat",
+                        help="(addition) how overlapping windows are merged per frame: flat (the reference's plain average) or pyramid "
+                             "(triangular weight per window slot, diffusers FreeNoise weighting_scheme='pyramid')")
+    parser.add_argument("--context_frames", type=int, default=None,
+                        help="(addition) frames per window; default: the pipeline's (30, the motion module's temporal context)")
+    parser.add_argument("--context_overlap", type=int, default=8, help="(addition) frames shared by neighbouring windows")
     args = parser.parse_args(argv)
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
@@ -159,7 +170,8 @@ def main(argv=None):
 
     out = pipe(ref_image_pil, ref_skel_pil, pose_pils, face_pils, hand_pils, scene_motion_npy, width, height, num_frames,
                args.steps, args.cfg, generator=generator, guidance_rescale=args.guidance_rescale,
-               video=init_pils, strength=args.strength)
+               video=init_pils, strength=args.strength, context_schedule=args.context_schedule, context_fuse=args.context_fuse,
+               context_frames=args.context_frames, context_overlap=args.context_overlap)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

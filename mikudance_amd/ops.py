@@ -302,6 +302,18 @@ def window_accumulate(pred, noise_sum, counter, window, f, ftot, hw, halves=2):
               hw, halves, _st())
 
 
+def window_accumulate_weighted(pred, noise_sum, counter, window, weights, f, ftot, hw, halves=2):
+    """noise_sum[:, window[i]] += weights[i] * pred[:, i]; counter[window[i]] += weights[i] (md_window_accumulate_weighted).  `weights`:
+    fp32 (f,) on the device, the normalised per-slot weights of windows.fuse_weights; the other arguments as window_accumulate."""
+    _chk(pred, "pred"); _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
+    _chk(window, "window", torch.int32); _chk(weights, "weights", torch.float32)
+    assert halves in (1, 2) and pred.is_contiguous() and pred.numel() == halves * f * hw * 4
+    assert noise_sum.is_contiguous() and noise_sum.numel() == halves * ftot * hw * 4 and counter.numel() >= ftot
+    assert window.is_contiguous() and weights.is_contiguous() and window.numel() == f and weights.numel() == f
+    _lib.call("md_window_accumulate_weighted", pred.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), window.data_ptr(),
+              weights.data_ptr(), f, ftot, hw, halves, _st())
+
+
 _rs_ws = {}
 
 

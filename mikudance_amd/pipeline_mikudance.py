@@ -26,6 +26,7 @@ import torch
 from . import ops
 from .context import get_context_scheduler
 from .mutual_mix_attention import ReferenceAttentionControl
+from .windows import accumulate_slots, fuse_weights
 
 
 # ---- latent interpolation helpers: API mirror of reference src/pipelines/utils.py (a module-level method switch that the
@@ -129,7 +130,7 @@ class MikuDanceVideoPipeline:
     @torch.no_grad()
     def denoise(self, latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule="uniform",
                 context_frames=None, context_stride=1, context_overlap=8, callback=None, callback_steps=1, eta=0.0, generator=None,
-                window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0):
+                window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0, context_fuse="flat"):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -156,8 +157,20 @@ class MikuDanceVideoPipeline:
                             them from 0; DPM-Solver++ starts first order there, set_begin_index).  No new collective or host sync per step.
                             strength 1.0 starts at t = 999 where abar = 0: bitwise the plain loop, whatever init_latents holds
         strength            finite, in (0, 1]; < 1 needs init_latents.  None of it is read without init_latents
+        context_schedule    "uniform" (the reference's windows: every schedule a closed loop, windows wrap round the end of the clip) or
+                            "uniform_open" (windows.WindowLayout.open_windows: the same levels and advance, no window wraps, the last one of
+                            a level ends on the last frame; fewer windows for the same clip)
+        context_fuse        how the predictions of overlapping windows are merged per frame: "flat" (the reference: every window counts the
+                            same, md_window_accumulate) or "pyramid" (slot j of an L-frame window weighs min(j + 1, L - j), diffusers'
+                            FreeNoise pyramid; normalised per frame over ALL windows of the step on the host, windows.fuse_weights, and
+                            accumulated by md_window_accumulate_weighted, so the buffers hold the weighted mean and a counter of 1 and every
+                            step kernel, the guidance rescale and window_parallel's all-reduce work on them unchanged).  One difference:
+                            WITHOUT classifier-free guidance the reference, and "flat", hand the scheduler the window SUM
+                            (src/pipelines/pipeline_mikudance.py:670-674 divides under CFG only); "pyramid" always hands it the mean.
+                            "flat" is bitwise the loop without the keyword; a clip of one window is the same bits under both
         returns latents (1, 4, F, h, w) in the input dtype.
         """
+        self._check_fuse(context_fuse)
         phi = float(guidance_rescale)
         if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
             raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale}")
@@ -208,8 +221,11 @@ class MikuDanceVideoPipeline:
         # A wrapped, dilated window (context_stride >= 2, F < 2*size) can name a frame twice.  The reference's
         # `noise_pred[:, :, c] = noise_pred[:, :, c] + pred` (:662-666) is an index_put with duplicate indices: the LAST
         # occurrence's value lands and the counter grows by one.  Earlier occurrences get slot -1 = "do not accumulate".
-        win_dev = [torch.tensor([fr if fr not in w[j + 1:] else -1 for j, fr in enumerate(w)], dtype=torch.int32, device=dev)
-                   for w in windows]
+        win_dev = [torch.tensor(accumulate_slots(w), dtype=torch.int32, device=dev) for w in windows]
+        # pyramid fuse: every rank normalises over ALL windows of the step, its own or not (float64 on the host, fp32 on the device)
+        wts_dev = None
+        if context_fuse == "pyramid":
+            wts_dev = [torch.tensor(w, dtype=torch.float64).to(device=dev, dtype=torch.float32) for w in fuse_weights(windows, F_, "pyramid")]
         win_long = [torch.tensor(w, dtype=torch.long, device=dev) for w in windows]     # gather indices: the real frames
         whole = len(windows) == 1 and windows[0] == list(range(F_))
         embeds = image_prompt_embeds
@@ -248,7 +264,10 @@ class MikuDanceVideoPipeline:
                     # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
                     pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
                                             two_queues=self.two_queues)
-                    ops.window_accumulate(pred, noise_sum, counter, win_dev[wi], f, F_, HW, halves=nb)
+                    if wts_dev is None:
+                        ops.window_accumulate(pred, noise_sum, counter, win_dev[wi], f, F_, HW, halves=nb)
+                    else:
+                        ops.window_accumulate_weighted(pred, noise_sum, counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=nb)
                     reader.clear()
                     writer.clear()
                 if window_parallel is not None:
@@ -275,6 +294,11 @@ class MikuDanceVideoPipeline:
             den.clear_context_cache()
             refu.clear_context_cache()
         return self._latents_out(lat, latents)
+
+    @staticmethod
+    def _check_fuse(context_fuse):
+        if context_fuse not in ("flat", "pyramid"):
+            raise ValueError(f"context_fuse must be 'flat' or 'pyramid', got {context_fuse!r}")
 
     @staticmethod
     def _check_strength(strength, has_init, num_inference_steps):
@@ -452,13 +476,16 @@ class MikuDanceVideoPipeline:
                  return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                  callback_steps: Optional[int] = 1, context_schedule="uniform", context_frames=None, context_stride=1,
                  context_overlap=8, context_batch_size=1, interpolation_factor=1, guidance_rescale: float = 0.0, video=None, strength: float = 1.0,
-                 **kwargs):
+                 context_fuse="flat", **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
         # no behaviour to reproduce: the windows are evaluated one at a time here, which is what the sum over a batch would be.
         if context_batch_size < 1:
             raise ValueError(f"context_batch_size must be >= 1, got {context_batch_size}")
+        # context_schedule / context_fuse: see denoise(); both names are checked here, before the CLIP tower and the VAE run
+        self._check_fuse(context_fuse)
+        get_context_scheduler(context_schedule)
         # video / strength: video-to-video (denoise's init_latents), `video` = video_length PIL frames preprocessed like the reference image
         if video is not None and len(video) != video_length:
             raise ValueError(f"video has {len(video)} frames, video_length is {video_length}: they must be equal")
@@ -496,7 +523,8 @@ class MikuDanceVideoPipeline:
         ref_latents = torch.cat([ref_image_latents, pose_ref_latents, pose_tgt, face_tgt, hand_tgt, tracker], dim=1)[None]
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
                                context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
-                               guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength)
+                               guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength,
+                               context_fuse=context_fuse)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)

@@ -19,6 +19,73 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SAMPLERS = (("ddim", 20), ("dpmpp_2m", 10), ("dpmpp_2m", 20))
+WINDOW_MODES = (("uniform", "flat"), ("uniform_open", "flat"), ("uniform_open", "pyramid"))
+
+
+def time_windows(a):
+    """configs[4] per clip under each (context_schedule, context_fuse) of WINDOW_MODES; one JSON record."""
+    from mikudance_amd import DDIMScheduler, MikuDanceVideoPipeline, _lib, ops
+    from mikudance_amd.context import get_context_scheduler
+    from mikudance_amd.selftest import SCHED_KWARGS, build_models
+    from mikudance_amd.synth import synth_inputs
+    _lib.load()
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    frames, size, steps, ctx, overlap = a.window_frames, a.window_size, a.window_steps, 30, 8
+    ref, den, _, _ = build_models(geom=dict(block_out_channels=(320, 640, 1280, 1280), cross_attention_dim=768), device=dev,
+                                  keep_state_dicts=False)
+    h = size // 8
+    lat, rl, emb = (t.half().to(dev) for t in synth_inputs(frames, h, h, ctx_len=257, ctx_dim=768, seed=100))
+    pipe = MikuDanceVideoPipeline(None, None, ref, den, DDIMScheduler(**SCHED_KWARGS))
+    kw = lambda m: dict(context_schedule=m[0], context_fuse=m[1], context_frames=ctx, context_stride=1, context_overlap=overlap)
+    rec = {"config": {"frames": frames, "size": size, "steps": steps, "guidance": 3.5, "context_frames": ctx, "context_overlap": overlap,
+                      "reps": a.reps},
+           "windows": {name: len(list(get_context_scheduler(name)(0, steps, frames, ctx, 1, overlap))) for name in ("uniform", "uniform_open")},
+           "ms_per_clip": {}}
+
+    def timed(m):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        pipe.denoise(lat, rl, emb, steps, 3.5, **kw(m))
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    for m in WINDOW_MODES:
+        pipe.denoise(lat, rl, emb, steps, 3.5, **kw(m))                             # warm-up
+    torch.cuda.synchronize()
+    times = {m: [] for m in WINDOW_MODES}
+    for _ in range(a.reps):
+        for m in WINDOW_MODES:                                                       # alternated: drift hits all alike
+            times[m].append(timed(m))
+    for m in WINDOW_MODES:
+        rec["ms_per_clip"]["/".join(m)] = {"min": min(times[m]), "all": times[m]}
+        print(f"{m}: {times[m]}", file=sys.stderr, flush=True)
+    best = {m: min(times[m]) for m in WINDOW_MODES}
+    rec["open_over_closed"] = best[WINDOW_MODES[1]] / best[WINDOW_MODES[0]]
+    rec["pyramid_over_flat"] = best[WINDOW_MODES[2]] / best[WINDOW_MODES[1]]
+    # the two accumulate launches alone: one window of `ctx` slots, both clip-halves, on this clip's buffers
+    hw = h * h
+    pred = torch.randn((2 * ctx, hw, 4), device=dev).half()
+    ns, cnt = torch.zeros((2, frames, hw, 4), device=dev), torch.zeros((frames,), device=dev)
+    win = torch.arange(ctx, dtype=torch.int32, device=dev)
+    wts = torch.full((ctx,), 0.5, device=dev)
+    launch = {"md_window_accumulate": lambda: ops.window_accumulate(pred, ns, cnt, win, ctx, frames, hw),
+              "md_window_accumulate_weighted": lambda: ops.window_accumulate_weighted(pred, ns, cnt, win, wts, ctx, frames, hw)}
+    rec["accumulate_us_per_launch"] = {}
+    for _ in range(2):                                                               # the second pass is the one kept
+        for name, fn in launch.items():
+            fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(200):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            rec["accumulate_us_per_launch"][name] = e0.elapsed_time(e1) * 1000.0 / 200
+    rec["accumulate_bytes_per_launch"] = 2 * ctx * hw * 4 * (2 + 4 + 4)
+    rec["device"] = torch.cuda.get_device_name(0)
+    return rec
 
 
 def main():
@@ -28,8 +95,21 @@ def main():
     ap.add_argument("--size", type=int, default=768)
     ap.add_argument("--guidance_rescale", type=float, default=0.0)
     ap.add_argument("--strength", type=float, default=1.0)
+    ap.add_argument("--windows", action="store_true", help="time one long clip under the three window schedule / fuse pairs instead")
+    ap.add_argument("--window_frames", type=int, default=48)
+    ap.add_argument("--window_size", type=int, default=1024)
+    ap.add_argument("--window_steps", type=int, default=30)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.windows:
+        assert torch.cuda.is_available(), "needs an MI355X"
+        rec = time_windows(a)
+        print(json.dumps(rec))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                json.dump(rec, fh, indent=1)
+        return
     if a.guidance_rescale > 0 and a.strength < 1:
         ap.error("--guidance_rescale and --strength: one at a time")
     assert torch.cuda.is_available(), "needs an MI355X"
