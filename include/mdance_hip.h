@@ -138,10 +138,22 @@ int md_instnorm_spade_ld_f16(const void* x, int ldx, const void* gamma_beta, voi
 /* O = softmax(Q K^T * scale) V per (batch, head); Vt is V transposed ([H*D][ldvt], md_gemm_f16 transpose_out);
  * kv_index (device int[B], may be NULL) maps a query batch to its K/V batch; kv_stride = tokens between K/V batches.
  * D in {8,16,32,40,64,80,160}.  Replaces F.scaled_dot_product_attention under diffusers AttnProcessor2_0 as
- * called at src/models/mutual_mix_attention.py:141-148,173-200,213-220,257-263. */
+ * called at src/models/mutual_mix_attention.py:141-148,173-200,213-220,257-263.
+ * The pad: with ldvt, kv_stride multiples of 8, Vt 16-byte aligned and roundup8(Lk) <= kv_stride (the fast kernels), rows [Lk, roundup8(Lk))
+ * of every K batch and the same columns of Vt must be readable; the V^T columns are fetched.  Pad contents may be any FINITE values and do
+ * not influence the result (the scores of keys >= Lk are masked, P is exactly +0 there and 0 x finite = 0: two runs that differ only in
+ * the pad give the same bits, tests/test_attention_flavours_gpu.py).  Non-finite pad values are not supported: 0 x Inf is NaN in the
+ * matrix core.  The pipeline's pad is exact zeros (zero context rows through a bias-free to_v: V = 0 . W). */
 int md_attention_fwd_f16(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O, int ldo,
                          const int* kv_index, int B, int H, int D, int Lq, int Lk, int kv_stride, float scale,
                          void* stream);
+
+/* Which kernel md_attention_fwd_f16 selects; no device access, nothing launched.  vt_align16: whether Vt is 16-byte aligned (the other
+ * operands are taken as valid: the choice does not depend on them).  Returns 400 the generic kernel (ldvt % 8, kv_stride % 8, Vt not
+ * 16-byte aligned or roundup8(Lk) > kv_stride), 414 / 418 the DMA ring kernel with 4 / 8 waves per workgroup (8: D <= 40 and Lq >= 1024),
+ * 420 the kernel that keeps K / V^T of a (batch, head) pair resident in LDS (D = 40, Lq >= 2048, 8 <= Lk <= 320), or MD_ERR_ARG
+ * (unsupported D, empty problem, kv_stride < Lk).  Pins the dispatch in CPU tests and lets a GPU test state which kernel it runs. */
+int md_attention_plan(int D, int Lq, int Lk, int kv_stride, int ldvt, int vt_align16);
 
 /* Attention over FRAMES for every (clip-half, pixel, head); rows are (b*F + frame)*HW + pixel.  F <= 32.  O must not overlap Q, K or V
  * (column-sliced siblings of one wider row-major buffer, e.g. q | k | v of one GEMM, are fine): checked, MD_ERR_ARG otherwise.

@@ -215,7 +215,9 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
 #include "attention_v2s.h"
 #include <stdlib.h>
 
-template <int D>
+// Plan codes (md_attention_plan exposes them so that the dispatch is testable without a GPU): 400 attn_kernel (generic), 414 / 418
+// attn2_kernel with 4 / 8 waves, 420 attn2s_kernel.  DRY: return the code of the kernel the same conditions would launch.
+template <int D, bool DRY>
 static int launch_attn(const AttnParams& p, hipStream_t stream) {
   // fast path: 16-byte aligned K / V^T key chunks (DMA granularity) and a readable pad up to the next multiple of 8 keys
   const bool fast = p.ldvt % 8 == 0 && p.kv_stride % 8 == 0 && (reinterpret_cast<uintptr_t>(p.Vt) & 15) == 0 &&
@@ -224,39 +226,61 @@ static int launch_attn(const AttnParams& p, hipStream_t stream) {
     // cross-attention at d = 40 (257 CLIP tokens = a handful of key tiles, Lq >= 2048): K / V^T resident in LDS, persistent walk
     // over the q-blocks (attention_v2s.h).  Same-box A/B on MI355X (profiles/r03_ab_attention_small.log): Lq = 9216 0.33-0.34 ->
     // 0.25-0.27 ms; d = 80 / 160 measured 2 % slower than the ring kernel and stay there.
-    if (fast && attn2s_eligible<D>(p)) return launch_attn2s<D>(p, stream);
+    if (fast && attn2s_eligible<D>(p)) {
+      if constexpr (DRY) return 420;
+      else return launch_attn2s<D>(p, stream);
+    }
   }
-  if (fast) return launch_attn2<D>(p, stream);
-  constexpr int KS = (D + 15) / 16, DQ = KS * 16, DVT = (D + 31) / 32;
-  constexpr int smem = 2 * (KT * (DQ + 8) * 2 + DVT * 32 * (KT + 4) * 2);
-  md_ensure_dynamic_lds<attn_kernel<D>>(smem);
-  dim3 grid(cdiv(p.Lq, 128), p.H, p.B);
-  hipLaunchKernelGGL(attn_kernel<D>, grid, dim3(256), smem, stream, p);
-  MD_CHECK_LAUNCH("md_attention_fwd");
-  return MD_OK;
+  if (fast) return launch_attn2<D, DRY>(p, stream);
+  if constexpr (DRY) return 400;
+  else {
+    constexpr int KS = (D + 15) / 16, DQ = KS * 16, DVT = (D + 31) / 32;
+    constexpr int smem = 2 * (KT * (DQ + 8) * 2 + DVT * 32 * (KT + 4) * 2);
+    md_ensure_dynamic_lds<attn_kernel<D>>(smem);
+    dim3 grid(cdiv(p.Lq, 128), p.H, p.B);
+    hipLaunchKernelGGL(attn_kernel<D>, grid, dim3(256), smem, stream, p);
+    MD_CHECK_LAUNCH("md_attention_fwd");
+    return MD_OK;
+  }
+}
+
+// argument checks and the head-dim switch shared by the launch and by the dispatch query
+template <bool DRY>
+static int attn_dispatch(const AttnParams& p, int D, hipStream_t st) {
+  MD_CHECK_ARG(p.B > 0 && p.H > 0 && p.Lq > 0 && p.Lk > 0, "md_attention_fwd: empty problem");
+  MD_CHECK_ARG(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldo % 4 == 0, "md_attention_fwd: ldq/ldk must be multiples of 8, ldo of 4");
+  MD_CHECK_ARG((reinterpret_cast<uintptr_t>(p.Q) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.K) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.O) & 7) == 0,
+               "md_attention_fwd: Q/K must be 16-byte aligned, O 8-byte aligned");
+  MD_CHECK_ARG(p.kv_stride >= p.Lk, "md_attention_fwd: kv_stride < Lk");
+  switch (D) {
+    case 8: return launch_attn<8, DRY>(p, st);
+    case 16: return launch_attn<16, DRY>(p, st);
+    case 32: return launch_attn<32, DRY>(p, st);
+    case 40: return launch_attn<40, DRY>(p, st);
+    case 64: return launch_attn<64, DRY>(p, st);
+    case 80: return launch_attn<80, DRY>(p, st);
+    case 160: return launch_attn<160, DRY>(p, st);
+    default: md_set_error("md_attention_fwd: unsupported head dim %d (8,16,32,40,64,80,160)", D); return MD_ERR_ARG;
+  }
 }
 
 extern "C" int md_attention_fwd_f16(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O, int ldo, const int* kv_index,
                                     int B, int H, int D, int Lq, int Lk, int kv_stride, float scale, void* stream) {
-  MD_CHECK_ARG(B > 0 && H > 0 && Lq > 0 && Lk > 0, "md_attention_fwd: empty problem");
-  MD_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0, "md_attention_fwd: ldq/ldk must be multiples of 8, ldo of 4");
-  MD_CHECK_ARG((reinterpret_cast<uintptr_t>(Q) & 15) == 0 && (reinterpret_cast<uintptr_t>(K) & 15) == 0 && (reinterpret_cast<uintptr_t>(O) & 7) == 0,
-               "md_attention_fwd: Q/K must be 16-byte aligned, O 8-byte aligned");
-  MD_CHECK_ARG(kv_stride >= Lk, "md_attention_fwd: kv_stride < Lk");
   AttnParams p;
   p.Q = (const half_t*)Q; p.K = (const half_t*)K; p.Vt = (const half_t*)Vt; p.O = (half_t*)O; p.kv_index = kv_index;
   p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo;
   p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.kv_stride = kv_stride;
   p.scale_log2 = scale * 1.4426950408889634f;
-  hipStream_t st = (hipStream_t)stream;
-  switch (D) {
-    case 8: return launch_attn<8>(p, st);
-    case 16: return launch_attn<16>(p, st);
-    case 32: return launch_attn<32>(p, st);
-    case 40: return launch_attn<40>(p, st);
-    case 64: return launch_attn<64>(p, st);
-    case 80: return launch_attn<80>(p, st);
-    case 160: return launch_attn<160>(p, st);
-    default: md_set_error("md_attention_fwd: unsupported head dim %d (8,16,32,40,64,80,160)", D); return MD_ERR_ARG;
-  }
+  return attn_dispatch<false>(p, D, (hipStream_t)stream);
+}
+
+// Which kernel md_attention_fwd_f16 selects (400 / 414 / 418 / 420 above); nothing is launched and no device is touched, so the table is
+// pinned by CPU tests (tests/test_host_cpu.py).  The choice depends on D, Lq, Lk, kv_stride, ldvt and the alignment of Vt only: the other
+// operands are taken as dense and aligned, B = H = 1.
+extern "C" int md_attention_plan(int D, int Lq, int Lk, int kv_stride, int ldvt, int vt_align16) {
+  AttnParams p = {};
+  p.Vt = reinterpret_cast<const half_t*>((uintptr_t)0x100000 + (vt_align16 ? 0 : 8));
+  p.ldq = p.ldk = p.ldo = 8; p.ldvt = ldvt;
+  p.B = 1; p.H = 1; p.Lq = Lq; p.Lk = Lk; p.kv_stride = kv_stride;
+  return attn_dispatch<true>(p, D, nullptr);
 }

@@ -502,13 +502,18 @@ static int launch_attn2_qt(const AttnParams& p, hipStream_t stream) {
   return MD_OK;
 }
 
-template <int D>
+// DRY (md_attention_plan): the same decision, returning the plan code (418 = 8 waves, 414 = 4 waves) instead of launching
+template <int D, bool DRY = false>
 static int launch_attn2(const AttnParams& p, hipStream_t stream) {
   // Measured on MI355X (profiles/r02_ab_attention_*.log) and settled: ONE 32-row q-tile per wave (two tiles per wave leave one wave
   // per SIMD and the compiler does not interleave the two softmax chains: -4 %); at d <= 40 long self-attention runs 8 waves per
   // workgroup, which share each K / V^T tile (L = 9216: 8 waves 802-810 TFLOP/s, 16 waves 803, 4 waves 782).
   if constexpr (D <= 40) {
-    if (p.Lq >= 1024) return launch_attn2_qt<D, 1, 8>(p, stream);
+    if (p.Lq >= 1024) {
+      if constexpr (DRY) return 418;
+      else return launch_attn2_qt<D, 1, 8>(p, stream);
+    }
   }
-  return launch_attn2_qt<D, 1>(p, stream);
+  if constexpr (DRY) return 414;
+  else return launch_attn2_qt<D, 1>(p, stream);
 }

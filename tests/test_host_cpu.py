@@ -216,6 +216,48 @@ def test_gemm_and_conv_dispatch_table_of_the_benchmark_shapes():
     assert lib.md_gemm_plan(18432, 1280, 1280, 0, 0, 5, 192) in (2134, 2135, 2124)
 
 
+def test_attention_dispatch_table():
+    """md_attention_plan runs the decision code of md_attention_fwd_f16 (launch_attn / launch_attn2 / attn2s_eligible) without touching a
+    device: 400 = generic attn_kernel, 414 / 418 = attn2 DMA ring with 4 / 8 waves, 420 = attn2s (K / V^T resident in LDS).  Pinned: the
+    shapes of BASELINE configs[1] (profiles/r02_ab_attention_*.log, r03_ab_attention_small.log) and both sides of every threshold, so that a
+    change of a threshold shows here and in the flavour each case of tests/test_attention_flavours_gpu.py states."""
+    from mikudance_amd import _lib
+    plan = _lib.load().md_attention_plan
+    GENERIC, RING4, RING8, RESIDENT = 400, 414, 418, 420
+    table = {  # (D, Lq, Lk, kv_stride, ldvt, vt_align16)
+        # configs[1], 32-frame batches: self-attention at the 96 x 96 / 48 x 48 / 24 x 24 levels (ldvt = every token of the batch)
+        (40, 9216, 9216, 9216, 32 * 9216, 1): RING8, (80, 2304, 2304, 2304, 32 * 2304, 1): RING4, (160, 576, 576, 576, 32 * 576, 1): RING4,
+        # cross-attention: 257 CLIP tokens, two context batches padded to a stride of 264
+        (40, 9216, 257, 264, 528, 1): RESIDENT, (80, 2304, 257, 264, 528, 1): RING4, (160, 576, 257, 264, 528, 1): RING4,
+        # Lq 1023 | 1024: 8 waves from 1024 on at D <= 40 only
+        (40, 1023, 1024, 1024, 1024, 1): RING4, (40, 1024, 1024, 1024, 1024, 1): RING8,
+        (80, 1023, 1024, 1024, 1024, 1): RING4, (80, 1024, 1024, 1024, 1024, 1): RING4,
+        (8, 1024, 1024, 1024, 1024, 1): RING8, (16, 1023, 1024, 1024, 1024, 1): RING4, (32, 1024, 64, 64, 64, 1): RING8, (64, 4096, 64, 64, 64, 1): RING4,
+        # Lq 2047 | 2048 with the cross-attention keys: residency needs the long query side
+        (40, 2047, 257, 264, 528, 1): RING8, (40, 2048, 257, 264, 528, 1): RESIDENT,
+        # Lk 320 | 328: a key tile of attn2s is STAGE = 64 * 40 * 2 + 2 * 32 * 128 = 13312 bytes of LDS; five tiles + the 2576 bytes of the folded
+        # constants are 69136 <= 72 KiB, six are 82448: at most 5 tiles = 320 keys stay resident
+        (40, 2048, 320, 320, 320, 1): RESIDENT, (40, 2048, 321, 328, 328, 1): RING8, (40, 2048, 328, 328, 328, 1): RING8,
+        (40, 9216, 384, 384, 384, 1): RING8,
+        # Lk = 8 | Lk < 8: the clamped V^T load of attn2s needs one whole 8-key chunk
+        (40, 2048, 8, 8, 8, 1): RESIDENT, (40, 2048, 7, 8, 8, 1): RING8, (40, 2048, 1, 8, 8, 1): RING8,
+        # resident at D = 40 only
+        (8, 4096, 257, 264, 528, 1): RING8, (32, 4096, 257, 264, 528, 1): RING8, (80, 4096, 257, 264, 528, 1): RING4,
+        # not "fast", one reason at a time: ldvt % 8, kv_stride % 8 (Lk = 256 keeps roundup8(Lk) <= kv_stride), V^T not 16-byte aligned
+        (40, 2048, 257, 264, 532, 1): GENERIC, (40, 2048, 256, 260, 520, 1): GENERIC, (40, 2048, 257, 264, 528, 0): GENERIC,
+        (80, 100, 257, 264, 532, 1): GENERIC, (160, 1024, 256, 260, 520, 1): GENERIC, (8, 2048, 257, 264, 528, 0): GENERIC,
+        # the fourth, roundup8(Lk) > kv_stride, cannot stand alone: kv_stride % 8 == 0 and kv_stride >= Lk (checked before) imply
+        # kv_stride >= roundup8(Lk).  With the smallest stride that misses the pad it comes with kv_stride % 8:
+        (40, 2048, 257, 260, 520, 1): GENERIC, (40, 2048, 257, 257, 520, 1): GENERIC, (40, 200, 333, 333, 666, 1): GENERIC,
+    }
+    for args, want in table.items():
+        assert plan(*args) == want, (args, plan(*args), want)
+    # errors are reported, not guessed around: unsupported head dims, empty problems, kv_stride < Lk
+    for args in [(24, 2048, 257, 264, 528, 1), (48, 64, 64, 64, 64, 1), (0, 64, 64, 64, 64, 1), (320, 64, 64, 64, 64, 1),
+                 (40, 0, 64, 64, 64, 1), (40, 64, 0, 64, 64, 1), (40, 2048, 257, 256, 528, 1)]:
+        assert plan(*args) < 0, (args, plan(*args))
+
+
 def test_fused_normalisation_plans_are_the_measured_table():
     """md_gemm_ln_plan / md_gemm_affine_plan (no device touched): the fused normalisations exist exactly where they won their same-box A/B
     (profiles/r05_ab_fused_norms*.log) -- K = 320, plain epilogue, N a multiple of 320, >= 32768 rows in whole 16-row tiles -- and nowhere
