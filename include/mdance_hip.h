@@ -189,14 +189,17 @@ int md_window_accumulate_weighted(const void* pred, void* noise_sum, void* count
                                   int Ftot, int HW, int halves, void* stream);
 
 /* (noise_pred / counter) -> classifier-free guidance -> DDIM v-prediction step (eta 0), latents updated in place.
- * src/pipelines/pipeline_mikudance.py:670-678 + diffusers DDIMScheduler.step. */
+ * src/pipelines/pipeline_mikudance.py:670-678 + diffusers DDIMScheduler.step.
+ * Like every step entry below: latents / noise_sum (and counter when halves == 2) must not be NULL, Ftot > 0, HW > 0, halves 1 or 2,
+ * guidance / alpha_t / alpha_prev finite; MD_ERR_ARG otherwise, with the latents untouched. */
 int md_cfg_ddim_step(void* latents, const void* noise_sum, const void* counter, int Ftot, int HW, int halves,
                      float guidance, float alpha_t, float alpha_prev, void* stream);
 
 /* The same step for eta > 0 (DDIM's stochastic variant; `eta` of MikuDanceVideoPipeline.__call__,
  * src/pipelines/pipeline_mikudance.py:152-171,375 -> scheduler.step(..., eta=, generator=)): sigma_t = eta * sqrt((1 - a_prev) /
  * (1 - a_t) * (1 - a_t / a_prev)), prev = sqrt(a_prev) x0 + sqrt(1 - a_prev - sigma_t^2) eps + sigma_t z with z = variance_noise,
- * fp16, laid out like the latents (Ftot, HW, 4) -- the caller draws it from ITS generator (diffusers randn_tensor). */
+ * fp16, laid out like the latents (Ftot, HW, 4) -- the caller draws it from ITS generator (diffusers randn_tensor).
+ * The refusals of md_cfg_ddim_step, and: eta finite and >= 0, variance_noise not NULL when eta != 0. */
 int md_cfg_ddim_step_eta(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW,
                          int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
 
@@ -214,7 +217,7 @@ int md_cfg_multistep_step(void* latents, const void* noise_sum, const void* coun
 /* Guidance rescale (rescaled classifier-free guidance, Lin et al. "Common Diffusion Noise Schedules and Sample Steps are Flawed",
  * arXiv 2305.08891 section 3.4; diffusers rescale_noise_cfg), applied to the window-averaged guided output between
  * src/pipelines/pipeline_mikudance.py:670-674 (CFG) and :678 (scheduler.step):
- *   c = noise_sum[1] / counter, v = u + guidance (c - u) exactly as the step kernels form them, std over ALL Ftot HW 4 elements,
+ *   c = noise_sum[1] / counter, v = u + guidance (c - u) formed by the step kernels' own device function, std over ALL Ftot HW 4 elements,
  *   out_scale[0] = 1 - phi + phi std(c) / std(v), one fp32 in device memory (never read back by the library).
  * One deviation from diffusers: std(v) == 0 gives out_scale = 1 (v left unscaled) where diffusers divides by zero; NaN / Inf inputs
  * propagate as they would in the formula.  Deterministic (fixed grid, fixed per-workgroup slices, fixed combine order, no atomics): two

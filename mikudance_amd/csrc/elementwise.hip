@@ -4,6 +4,7 @@
 // multistep step (the same call site's scheduler.step with a DPMSolverMultistepScheduler).
 #include "common.h"
 #include <stdarg.h>
+#include <initializer_list>
 
 static thread_local char g_err[512] = "";
 void md_set_error(const char* fmt, ...) {
@@ -157,13 +158,45 @@ extern "C" int md_window_accumulate_weighted(const void* pred, void* noise_sum, 
   return MD_OK;
 }
 
-// ---- CFG combine + DDIM v-prediction step (eta = 0) --------------------------------------------------------------------
-//   v   = u + s (c - u),  u = sum_u / cnt, c = sum_c / cnt                         pipeline_mikudance.py:670-674
+// ---- the guided v every kernel of the step tail forms ----------------------------------------------------------------------------
+//   u = sum_u / cnt, c = sum_c / cnt, v = u + s (c - u)                              pipeline_mikudance.py:670-674
+// as  inv = 1 / cnt;  v = sum_u inv;  c = sum_c inv;  v = v + s (c - v)  in exactly this order.  Without guidance (halves == 1) the
+// reference takes the window SUM as it is: its division by the counter sits inside `if do_classifier_free_guidance:`, so neither the
+// counter nor the second half is read.  T = float (one element at index i of `total`) or floatx4 (one pixel).  c_out, where given,
+// receives c (the rescale statistics; halves == 2 only).
+// SCALED in the step kernels (guidance rescale): they multiply this v by *vscale, the factor md_cfg_guidance_rescale left in device
+// memory; the unscaled instantiation has neither the load nor the multiply.
+template <typename T>
+__device__ __forceinline__ T guided_v(const T* __restrict__ ns, const float* __restrict__ counter, long i, long total, int fr, int halves,
+                                      float guidance, T* c_out = nullptr) {
+  const float inv = halves == 2 ? 1.f / counter[fr] : 1.f;
+  T v = ns[i] * inv;
+  if (halves == 2) {
+    const T c = ns[total + i] * inv;
+    v = v + guidance * (c - v);
+    if (c_out) *c_out = c;
+  }
+  return v;
+}
+
+// The argument rules all five step entry points share.  Alignment and a kernel's own buffers are its launcher's business.
+// noise_coeff: the factor of variance_noise (eta / c_z).  scaled: the *_scaled entries, which need CFG and the factor.
+static int cfg_step_check(const char* who, const void* latents, const void* noise_sum, const void* counter, const void* variance_noise,
+                          bool scaled, const float* vscale, int Ftot, int HW, int halves, float noise_coeff, std::initializer_list<float> coeffs) {
+  MD_CHECK_ARG(Ftot > 0 && HW > 0 && (halves == 1 || halves == 2), "%s: bad arguments", who);
+  MD_CHECK_ARG(latents && noise_sum && (halves == 1 || counter), "%s: null pointer", who);
+  MD_CHECK_ARG(!scaled || (halves == 2 && vscale && ((uintptr_t)vscale % 4) == 0),
+               "%s: guidance rescale needs halves == 2 and a 4-byte aligned vscale", who);
+  for (const float c : coeffs) MD_CHECK_ARG(__builtin_isfinite(c), "%s: non-finite coefficient", who);
+  MD_CHECK_ARG(noise_coeff == 0.f || variance_noise, "%s: a non-zero noise coefficient needs variance_noise", who);
+  return MD_OK;
+}
+
+// ---- CFG combine + DDIM v-prediction step -------------------------------------------------------------------------------
+//   v   = guided_v
 //   x0  = sqrt(a_t) x - sqrt(1-a_t) v ;  eps = sqrt(a_t) v + sqrt(1-a_t) x
 //   x'  = sqrt(a_prev) x0 + sqrt(1-a_prev) eps                                      DDIMScheduler.step
 // latents: [Ftot][HW][4] fp16, updated in place (fp32 arithmetic, one rounding).
-// SCALED (guidance rescale): v is multiplied by *vscale, the factor md_cfg_guidance_rescale left in device memory; the unscaled
-// instantiation has neither the load nor the multiply.
 template <bool SCALED>
 __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
                                 const half_t* __restrict__ variance_noise, int Ftot, int HW4, int halves, float guidance, float sa, float sb, float sap,
@@ -171,15 +204,7 @@ __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restric
   const long total = (long)Ftot * HW4;
   const float vs = SCALED ? *vscale : 1.f;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int fr = (int)(idx / HW4);
-    // without guidance the reference takes the window SUM as it is: its division by the counter sits inside
-    // `if do_classifier_free_guidance:` (src/pipelines/pipeline_mikudance.py:670-674)
-    const float inv = halves == 2 ? 1.f / counter[fr] : 1.f;
-    float v = noise_sum[idx] * inv;
-    if (halves == 2) {
-      const float c = noise_sum[total + idx] * inv;
-      v = v + guidance * (c - v);
-    }
+    float v = guided_v(noise_sum, counter, idx, total, (int)(idx / HW4), halves, guidance);
     if constexpr (SCALED) v *= vs;
     const float x = (float)lat[idx];
     const float x0 = sa * x - sb * v;
@@ -191,8 +216,11 @@ __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restric
 }
 
 static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW, int halves,
-                           float guidance, float alpha_t, float alpha_prev, float eta, void* stream, const char* who, const float* vscale = nullptr) {
-  MD_CHECK_ARG(Ftot > 0 && HW > 0 && (halves == 1 || halves == 2) && eta >= 0.f && (eta == 0.f || variance_noise), "md_cfg_ddim_step: bad arguments");
+                           float guidance, float alpha_t, float alpha_prev, float eta, void* stream, bool scaled, const float* vscale,
+                           const char* who) {
+  if (cfg_step_check(who, latents, noise_sum, counter, variance_noise, scaled, vscale, Ftot, HW, halves, eta, {guidance, alpha_t, alpha_prev, eta}))
+    return MD_ERR_ARG;
+  MD_CHECK_ARG(eta >= 0.f, "%s: eta must be >= 0", who);
   // diffusers DDIMScheduler._get_variance: sigma_t^2 = eta^2 (1 - a_prev) / (1 - a_t) (1 - a_t / a_prev); a_t == 1 never occurs (t >= 0 of a
   // zero-terminal-SNR table has a_t < 1)
   const float var = eta > 0.f ? (1.f - alpha_prev) / (1.f - alpha_t) * (1.f - alpha_t / alpha_prev) : 0.f;
@@ -200,46 +228,38 @@ static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* cou
   const float dir2 = 1.f - alpha_prev - sigma * sigma;
   const long total = (long)Ftot * HW * 4;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  if (vscale)
-    hipLaunchKernelGGL(cfg_ddim_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
-                       (const float*)counter, eta > 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW * 4, halves, guidance, sqrtf(alpha_t),
-                       sqrtf(1.f - alpha_t), sqrtf(alpha_prev), sqrtf(dir2 > 0.f ? dir2 : 0.f), sigma, vscale);
-  else
-    hipLaunchKernelGGL(cfg_ddim_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
-                       (const float*)counter, eta > 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW * 4, halves, guidance, sqrtf(alpha_t),
-                       sqrtf(1.f - alpha_t), sqrtf(alpha_prev), sqrtf(dir2 > 0.f ? dir2 : 0.f), sigma, nullptr);
+  hipLaunchKernelGGL(scaled ? cfg_ddim_kernel<true> : cfg_ddim_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents,
+                     (const float*)noise_sum, (const float*)counter, eta > 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW * 4, halves,
+                     guidance, sqrtf(alpha_t), sqrtf(1.f - alpha_t), sqrtf(alpha_prev), sqrtf(dir2 > 0.f ? dir2 : 0.f), sigma, vscale);
   MD_CHECK_LAUNCH(who);
   return MD_OK;
 }
 
 extern "C" int md_cfg_ddim_step(void* latents, const void* noise_sum, const void* counter, int Ftot, int HW, int halves, float guidance, float alpha_t,
                                 float alpha_prev, void* stream) {
-  return cfg_ddim_launch(latents, noise_sum, counter, nullptr, Ftot, HW, halves, guidance, alpha_t, alpha_prev, 0.f, stream, "md_cfg_ddim_step");
+  return cfg_ddim_launch(latents, noise_sum, counter, nullptr, Ftot, HW, halves, guidance, alpha_t, alpha_prev, 0.f, stream, false, nullptr,
+                         "md_cfg_ddim_step");
 }
 
 extern "C" int md_cfg_ddim_step_eta(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW, int halves,
                                     float guidance, float alpha_t, float alpha_prev, float eta, void* stream) {
-  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream,
+  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream, false, nullptr,
                          "md_cfg_ddim_step_eta");
 }
 
 extern "C" int md_cfg_ddim_step_scaled(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const float* vscale,
                                        int Ftot, int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream) {
-  MD_CHECK_ARG(latents && noise_sum && counter && vscale && halves == 2, "md_cfg_ddim_step_scaled: bad arguments (guidance rescale needs halves == 2)");
-  MD_CHECK_ARG(((uintptr_t)vscale % 4) == 0, "md_cfg_ddim_step_scaled: vscale needs 4-byte alignment");
-  MD_CHECK_ARG(__builtin_isfinite(guidance) && __builtin_isfinite(alpha_t) && __builtin_isfinite(alpha_prev) && __builtin_isfinite(eta),
-               "md_cfg_ddim_step_scaled: non-finite coefficient");
-  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream,
-                         "md_cfg_ddim_step_scaled", vscale);
+  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream, true, vscale,
+                         "md_cfg_ddim_step_scaled");
 }
 
 // ---- CFG combine + DPM-Solver++ multistep step (orders 1 / 2, ODE or SDE; Lu et al., arXiv 2211.01095) ------------------
-//   v   = window-averaged, guided v-output exactly as in cfg_ddim_kernel
+//   v   = guided_v
 //   m0  = alpha_s x - sigma_s v                    data prediction (x0) of this step
 //   x'  = c_x x + c_m0 m0 + c_m1 m1 + c_z z        m1 = the previous step's m0 (history), z = variance noise
 // The coefficients are host scalars (DPMSolverMultistepScheduler.multistep_coefficients): every solver variant is this one update.
 // One thread per pixel (4 channels): 8-byte latents / noise, 16-byte noise_sum / history.  history is read (only when c_m1 != 0: on
-// the first step it is uninitialised) and then overwritten with m0 by the same thread at the same index.  SCALED as in cfg_ddim_kernel.
+// the first step it is uninitialised) and then overwritten with m0 by the same thread at the same index.
 template <bool SCALED>
 __global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
                                      float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, int halves,
@@ -251,13 +271,7 @@ __global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __re
   half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
   const float vs = SCALED ? *vscale : 1.f;
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-    const int fr = (int)(p / HW);
-    const float inv = halves == 2 ? 1.f / counter[fr] : 1.f;  // no division without guidance (see cfg_ddim_kernel)
-    floatx4 v = ns[p] * inv;
-    if (halves == 2) {
-      const floatx4 c = ns[total + p] * inv;
-      v = v + guidance * (c - v);
-    }
+    floatx4 v = guided_v(ns, counter, p, total, (int)(p / HW), halves, guidance);
     if constexpr (SCALED) v *= vs;
     const floatx4 x = __builtin_convertvector(lat4[p], floatx4);
     const floatx4 m0 = alpha_s * x - sigma_s * v;
@@ -269,50 +283,41 @@ __global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __re
   }
 }
 
+static int cfg_multistep_launch(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise, int Ftot, int HW,
+                                int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream,
+                                bool scaled, const float* vscale, const char* who) {
+  if (cfg_step_check(who, latents, noise_sum, counter, variance_noise, scaled, vscale, Ftot, HW, halves, c_z,
+                     {guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z}))
+    return MD_ERR_ARG;
+  MD_CHECK_ARG(history, "%s: null history", who);
+  MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
+                   ((uintptr_t)variance_noise % 8) == 0,
+               "%s: latents / variance_noise need 8-byte, noise_sum / history 16-byte alignment", who);
+  const long total = (long)Ftot * HW;
+  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(scaled ? cfg_multistep_kernel<true> : cfg_multistep_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                     (half_t*)latents, (const float*)noise_sum, (const float*)counter, (float*)history,
+                     c_z != 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, vscale);
+  MD_CHECK_LAUNCH(who);
+  return MD_OK;
+}
+
 extern "C" int md_cfg_multistep_step(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise, int Ftot,
                                      int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
                                      void* stream) {
-  MD_CHECK_ARG(latents && noise_sum && history && Ftot > 0 && HW > 0 && (halves == 1 || (halves == 2 && counter)),
-               "md_cfg_multistep_step: bad arguments");
-  MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
-                   ((uintptr_t)variance_noise % 8) == 0,
-               "md_cfg_multistep_step: latents / variance_noise need 8-byte, noise_sum / history 16-byte alignment");
-  MD_CHECK_ARG(__builtin_isfinite(guidance) && __builtin_isfinite(alpha_s) && __builtin_isfinite(sigma_s) && __builtin_isfinite(c_x) &&
-                   __builtin_isfinite(c_m0) && __builtin_isfinite(c_m1) && __builtin_isfinite(c_z),
-               "md_cfg_multistep_step: non-finite coefficient");
-  MD_CHECK_ARG(c_z == 0.f || variance_noise, "md_cfg_multistep_step: c_z != 0 needs variance_noise");
-  const long total = (long)Ftot * HW;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(cfg_multistep_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
-                     (const float*)counter, (float*)history, c_z != 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW, halves, guidance, alpha_s,
-                     sigma_s, c_x, c_m0, c_m1, c_z, nullptr);
-  MD_CHECK_LAUNCH("md_cfg_multistep_step");
-  return MD_OK;
+  return cfg_multistep_launch(latents, noise_sum, counter, history, variance_noise, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
+                              stream, false, nullptr, "md_cfg_multistep_step");
 }
 
 extern "C" int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
                                             const float* vscale, int Ftot, int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x,
                                             float c_m0, float c_m1, float c_z, void* stream) {
-  MD_CHECK_ARG(latents && noise_sum && counter && history && vscale && Ftot > 0 && HW > 0 && halves == 2,
-               "md_cfg_multistep_step_scaled: bad arguments (guidance rescale needs halves == 2)");
-  MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
-                   ((uintptr_t)variance_noise % 8) == 0 && ((uintptr_t)vscale % 4) == 0,
-               "md_cfg_multistep_step_scaled: latents / variance_noise need 8-byte, noise_sum / history 16-byte, vscale 4-byte alignment");
-  MD_CHECK_ARG(__builtin_isfinite(guidance) && __builtin_isfinite(alpha_s) && __builtin_isfinite(sigma_s) && __builtin_isfinite(c_x) &&
-                   __builtin_isfinite(c_m0) && __builtin_isfinite(c_m1) && __builtin_isfinite(c_z),
-               "md_cfg_multistep_step_scaled: non-finite coefficient");
-  MD_CHECK_ARG(c_z == 0.f || variance_noise, "md_cfg_multistep_step_scaled: c_z != 0 needs variance_noise");
-  const long total = (long)Ftot * HW;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(cfg_multistep_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
-                     (const float*)counter, (float*)history, c_z != 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW, halves, guidance, alpha_s,
-                     sigma_s, c_x, c_m0, c_m1, c_z, vscale);
-  MD_CHECK_LAUNCH("md_cfg_multistep_step_scaled");
-  return MD_OK;
+  return cfg_multistep_launch(latents, noise_sum, counter, history, variance_noise, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
+                              stream, true, vscale, "md_cfg_multistep_step_scaled");
 }
 
 // ---- guidance rescale factor (Lin et al., arXiv 2305.08891 section 3.4; diffusers rescale_noise_cfg) ----------------------------------
-//   c = sum_c / cnt, v = u + s (c - u)              formed on the fly exactly as the step kernels form them (never materialised)
+//   c = sum_c / cnt, v = u + s (c - u)              formed on the fly by guided_v, the step kernels' own code (never materialised)
 //   out_scale = 1 - phi + phi std(c) / std(v)      std over all Ftot HW 4 elements; the (N - 1) of torch.std cancels in the ratio
 //   std(v) == 0 -> out_scale = 1                  (diffusers would give inf / NaN; NaN / Inf inputs still propagate)
 // Deterministic, no float atomics, no host sync: rescale_blocks(Ftot, HW) <= 512 workgroups, each over a FIXED contiguous slice of
@@ -329,14 +334,6 @@ static int rescale_blocks(int Ftot, int HW) {
   return (int)(b < RS_MAX_BLOCKS ? b : RS_MAX_BLOCKS);
 }
 
-__device__ __forceinline__ void rescale_cv(const floatx4* __restrict__ ns, const float* __restrict__ counter, long p, long total, int HW,
-                                           float guidance, floatx4& c, floatx4& v) {
-  const float inv = 1.f / counter[(int)(p / HW)];
-  v = ns[p] * inv;
-  c = ns[total + p] * inv;
-  v = v + guidance * (c - v);
-}
-
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -348,13 +345,13 @@ __global__ void __launch_bounds__(RS_THREADS) cfg_rescale_partials_kernel(const 
                                                                           double* __restrict__ part, int Ftot, int HW, float guidance, long chunk) {
   const long total = (long)Ftot * HW;
   const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
-  floatx4 c, v;
-  rescale_cv(ns, counter, 0, total, HW, guidance, c, v);
+  floatx4 c;
+  floatx4 v = guided_v(ns, counter, 0, total, 0, 2, guidance, &c);
   const double kc = c.x, kv = v.x;
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   const long p1 = min(((long)blockIdx.x + 1) * chunk, total);
   for (long p = (long)blockIdx.x * chunk + threadIdx.x; p < p1; p += RS_THREADS) {
-    rescale_cv(ns, counter, p, total, HW, guidance, c, v);
+    v = guided_v(ns, counter, p, total, (int)(p / HW), 2, guidance, &c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const double dc = (double)c[e] - kc, dv = (double)v[e] - kv;

@@ -346,26 +346,31 @@ def add_noise(latents, x0, a, b):
     return latents
 
 
+def _step_buffers(latents, noise_sum, counter, ftot, hw, halves, noise_coeff, variance_noise, vscale):
+    """The checks cfg_ddim_step and cfg_multistep_step share -> (the three buffer pointers, the variance_noise pointer or 0)."""
+    _chk(latents, "latents"); _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
+    n = ftot * hw * 4
+    assert halves in (1, 2) and latents.is_contiguous() and latents.numel() == n
+    assert noise_sum.is_contiguous() and noise_sum.numel() == halves * n and counter.numel() >= ftot
+    if noise_coeff:
+        _chk(variance_noise, "variance_noise")
+        assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == n
+    if vscale is not None:
+        _chk(vscale, "vscale", torch.float32)
+    return (latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr()), _p(variance_noise) if noise_coeff else 0
+
+
 def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alpha_prev, halves=2, eta=0.0, variance_noise=None, vscale=None):
     """eta > 0: `variance_noise` is the caller's N(0, 1) draw, fp16, laid out like `latents` (ftot, hw, 4).
     vscale: the fp32 device factor of cfg_guidance_rescale (md_cfg_ddim_step_scaled, any eta); None: the unscaled entry points."""
-    _chk(latents, "latents"); _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
+    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, eta, variance_noise, vscale)
     if vscale is not None:
-        _chk(vscale, "vscale", torch.float32)
-        if eta:
-            _chk(variance_noise, "variance_noise")
-            assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == latents.numel()
-        _lib.call("md_cfg_ddim_step_scaled", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), _p(variance_noise) if eta else 0,
-                  vscale.data_ptr(), ftot, hw, halves, float(guidance), float(alpha_t), float(alpha_prev), float(eta), _st())
-        return
-    if eta:
-        _chk(variance_noise, "variance_noise")
-        assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == latents.numel()
-        _lib.call("md_cfg_ddim_step_eta", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), variance_noise.data_ptr(), ftot,
-                  hw, halves, float(guidance), float(alpha_t), float(alpha_prev), float(eta), _st())
-        return
-    _lib.call("md_cfg_ddim_step", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), ftot, hw, halves,
-              float(guidance), float(alpha_t), float(alpha_prev), _st())
+        name, ptrs, tail = "md_cfg_ddim_step_scaled", (z, vscale.data_ptr()), (float(eta),)
+    elif eta:
+        name, ptrs, tail = "md_cfg_ddim_step_eta", (z,), (float(eta),)
+    else:
+        name, ptrs, tail = "md_cfg_ddim_step", (), ()
+    _lib.call(name, *bufs, *ptrs, ftot, hw, halves, float(guidance), float(alpha_t), float(alpha_prev), *tail, _st())
 
 
 def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, halves=2,
@@ -373,21 +378,9 @@ def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance,
     """DPM-Solver++ multistep update (md_cfg_multistep_step): `history` is the fp32 (ftot, hw, 4) data-prediction buffer the caller keeps
     between steps; the coefficients are DPMSolverMultistepScheduler.multistep_coefficients(step_index).  c_z != 0: `variance_noise` is
     the caller's N(0, 1) draw, fp16, laid out like `latents`.  vscale: as in cfg_ddim_step (md_cfg_multistep_step_scaled)."""
-    _chk(latents, "latents"); _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
+    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, c_z, variance_noise, vscale)
     _chk(history, "history", torch.float32)
-    n = ftot * hw * 4
-    assert halves in (1, 2) and latents.is_contiguous() and latents.numel() == n
-    assert noise_sum.is_contiguous() and noise_sum.numel() == halves * n and counter.numel() >= ftot
-    assert history.is_contiguous() and history.numel() == n
-    if c_z:
-        _chk(variance_noise, "variance_noise")
-        assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == n
-    if vscale is not None:
-        _chk(vscale, "vscale", torch.float32)
-        _lib.call("md_cfg_multistep_step_scaled", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), history.data_ptr(),
-                  _p(variance_noise) if c_z else 0, vscale.data_ptr(), ftot, hw, halves, float(guidance), float(alpha_s), float(sigma_s),
-                  float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
-        return
-    _lib.call("md_cfg_multistep_step", latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr(), history.data_ptr(),
-              _p(variance_noise) if c_z else 0, ftot, hw, halves, float(guidance), float(alpha_s), float(sigma_s), float(c_x), float(c_m0),
-              float(c_m1), float(c_z), _st())
+    assert history.is_contiguous() and history.numel() == ftot * hw * 4
+    _lib.call("md_cfg_multistep_step" if vscale is None else "md_cfg_multistep_step_scaled", *bufs, history.data_ptr(), z,
+              *(() if vscale is None else (vscale.data_ptr(),)), ftot, hw, halves, float(guidance), float(alpha_s), float(sigma_s), float(c_x),
+              float(c_m0), float(c_m1), float(c_z), _st())

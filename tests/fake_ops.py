@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 F16 = torch.float16
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GEGLU, ACT_QUICKGELU = 0, 1, 2, 3, 4
-CALLS = []          # (name, detail) log, inspected by the tests
+CALLS = []          # (name, detail) log, inspected by the tests; cleared by install / install_process
 
 
 def _pitch(x, align=8):
@@ -262,7 +262,24 @@ def concat_channels(a, b):
     return torch.cat([a, b], dim=-1).contiguous()
 
 
+# ------------------------------------------------------------------ the sampling-step tail: accumulate -> rescale -> CFG + scheduler step
+# The complete CPU emulation of the tail (md_window_accumulate[_weighted], md_cfg_guidance_rescale, md_cfg_ddim_step*, md_cfg_multistep_step*,
+# md_add_noise_f16): fp32 arithmetic, one rounding of the latents.  Each call is logged as (name, dict): the scalar arguments and, under
+# "keywords", the names of the optional tensors (variance_noise, vscale) that were given.
+TAIL = ("window_accumulate", "window_accumulate_weighted", "cfg_guidance_rescale", "cfg_ddim_step", "cfg_multistep_step", "add_noise")
+
+
+def tail_calls(*names):
+    """The records of the named tail operators (all of them without names), in call order."""
+    return [(n, d) for n, d in CALLS if n in (names or TAIL)]
+
+
+def _log(name, optional=None, **scalars):
+    CALLS.append((name, dict(scalars, keywords=tuple(k for k, v in (optional or {}).items() if v is not None))))
+
+
 def window_accumulate(pred, noise_sum, counter, window, f, ftot, hw, halves=2):
+    _log("window_accumulate", f=f, ftot=ftot, hw=hw, halves=halves)
     p = pred.float().view(halves, f, hw, 4)
     for i, fr in enumerate(window.tolist()):
         if fr < 0:
@@ -271,12 +288,42 @@ def window_accumulate(pred, noise_sum, counter, window, f, ftot, hw, halves=2):
         counter[fr] += 1
 
 
-def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alpha_prev, halves=2, eta=0.0, variance_noise=None):
+def window_accumulate_weighted(pred, noise_sum, counter, window, weights, f, ftot, hw, halves=2):
+    """fp32: the share w * p rounded, then added -- the order of md_window_accumulate_weighted."""
+    _log("window_accumulate_weighted", f=f, ftot=ftot, hw=hw, halves=halves)
+    p = pred.float().view(halves, f, hw, 4)
+    for i, (fr, w) in enumerate(zip(window.tolist(), weights.tolist())):
+        if fr < 0:
+            continue
+        wt = torch.tensor(w, dtype=torch.float32)
+        noise_sum[:, fr] += wt * p[:, i]
+        counter[fr] += wt
+
+
+def _guided(noise_sum, counter, guidance, halves, vscale=None):
+    """(v, c): the window-averaged guided output [times vscale] and the conditional half; without CFG the window SUM as it is, and no c."""
     if halves == 2:
         u, c = (noise_sum / counter.view(1, -1, 1, 1)).unbind(0)
         v = u + guidance * (c - u)
     else:
-        v = noise_sum[0]
+        v, c = noise_sum[0], None
+    return (v if vscale is None else v * vscale), c
+
+
+def cfg_guidance_rescale(noise_sum, counter, ftot, hw, guidance, phi, out=None):
+    _log("cfg_guidance_rescale", ftot=ftot, hw=hw, guidance=guidance, phi=phi)
+    v, c = _guided(noise_sum, counter, guidance, 2)
+    sc, sv = float(c.double().std()), float(v.double().std())
+    if out is None:
+        out = torch.empty((1,), dtype=torch.float32)
+    out.fill_(1.0 if sv == 0.0 else 1.0 - phi + phi * sc / sv)
+    return out
+
+
+def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alpha_prev, halves=2, eta=0.0, variance_noise=None, vscale=None):
+    _log("cfg_ddim_step", dict(variance_noise=variance_noise, vscale=vscale), ftot=ftot, hw=hw, halves=halves, guidance=guidance, alpha_t=alpha_t,
+         alpha_prev=alpha_prev, eta=eta)
+    v, _ = _guided(noise_sum, counter, guidance, halves, vscale)
     x = latents.float().view(ftot, hw, 4)
     x0 = alpha_t ** 0.5 * x - (1 - alpha_t) ** 0.5 * v
     ep = alpha_t ** 0.5 * v + (1 - alpha_t) ** 0.5 * x
@@ -285,6 +332,29 @@ def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alph
     if eta:
         out = out + std * variance_noise.float().view(ftot, hw, 4)
     latents.copy_(out.view(latents.shape).to(F16))
+
+
+def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, halves=2,
+                       variance_noise=None, vscale=None):
+    _log("cfg_multistep_step", dict(variance_noise=variance_noise, vscale=vscale), ftot=ftot, hw=hw, halves=halves, guidance=guidance,
+         alpha_s=alpha_s, sigma_s=sigma_s, c_x=c_x, c_m0=c_m0, c_m1=c_m1, c_z=c_z)
+    v, _ = _guided(noise_sum, counter, guidance, halves, vscale)
+    x = latents.float().view(ftot, hw, 4)
+    m0 = alpha_s * x - sigma_s * v
+    out = c_x * x + c_m0 * m0
+    if c_m1 != 0.0:                                                # the kernel never reads the history then (uninitialised on step 0)
+        out = out + c_m1 * history.view(ftot, hw, 4)
+    history.view(ftot, hw, 4).copy_(m0)
+    if c_z != 0.0:
+        out = out + c_z * variance_noise.float().view(ftot, hw, 4)
+    latents.copy_(out.view(latents.shape).to(F16))
+
+
+def add_noise(latents, x0, a, b):
+    _log("add_noise", a=a, b=b)
+    z = latents.float()
+    latents.copy_((b * z if a == 0.0 else a * x0.float() + b * z).to(F16))
+    return latents
 
 
 # ------------------------------------------------------------------ duck-typed modules either side of the loop
@@ -329,8 +399,7 @@ def require_gpu(t, who):
 
 
 _NAMES = ("gemm", "gemm_ln_plan", "gemm_ln", "gemm_affine_plan", "groupnorm_table", "gemm_affine", "conv3x3", "groupnorm", "layernorm", "instnorm_spade",
-          "attention", "softmax_rows_", "temporal_attention", "pack_nhwc", "unpack_nhwc", "concat_channels", "window_accumulate", "cfg_ddim_step",
-          "require_gpu")
+          "attention", "softmax_rows_", "temporal_attention", "pack_nhwc", "unpack_nhwc", "concat_channels", "require_gpu") + TAIL
 
 
 def install_process():
@@ -344,7 +413,6 @@ def install_process():
 def install(monkeypatch):
     """Replace the functions of mikudance_amd.ops by the emulations above for the duration of a test."""
     from mikudance_amd import ops
-    for name in ("gemm", "gemm_ln_plan", "gemm_ln", "gemm_affine_plan", "groupnorm_table", "gemm_affine", "conv3x3", "groupnorm", "layernorm", "instnorm_spade", "attention", "softmax_rows_", "temporal_attention", "pack_nhwc",
-                 "unpack_nhwc", "concat_channels", "window_accumulate", "cfg_ddim_step", "require_gpu"):
+    for name in _NAMES:
         monkeypatch.setattr(ops, name, globals()[name])
     del CALLS[:]

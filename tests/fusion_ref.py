@@ -5,7 +5,7 @@
     slots(win), shares(windows, F)   which slots accumulate (the reference's last-occurrence rule) and the float64 per-frame-normalised weights
     denoise_loop(..., schedule=, fuse=)  the loop of tests/rescale_ref.py (itself the oracle's loop rebuilt from the oracle's parts) taking a
                                      window list and a weight rule; with the oracle's uniform windows and fuse="flat" it is that loop op for op
-    fake_window_accumulate_weighted  PyTorch emulation of ops.window_accumulate_weighted, installed beside tests/fake_ops.py's set
+The operator's CPU emulation is tests/fake_ops.window_accumulate_weighted.
 """
 import math
 
@@ -156,18 +156,3 @@ def denoise_loop(ref_sd, den_sd, latents, ref_latents, embeds, num_steps, guidan
             on_step(int(t), latents)
     return latents
 
-
-# ---- the operator
-WEIGHTED_CALLS = []
-
-
-def fake_window_accumulate_weighted(pred, noise_sum, counter, window, weights, f, ftot, hw, halves=2):
-    """fp32: the share w * p rounded, then added -- the order of md_window_accumulate_weighted."""
-    WEIGHTED_CALLS.append((f, ftot, hw, halves))
-    p = pred.float().view(halves, f, hw, 4)
-    for i, (fr, w) in enumerate(zip(window.tolist(), weights.tolist())):
-        if fr < 0:
-            continue
-        wt = torch.tensor(w, dtype=torch.float32)
-        noise_sum[:, fr] += wt * p[:, i]
-        counter[fr] += wt

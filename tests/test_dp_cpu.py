@@ -2,22 +2,15 @@
 independent per-rank work, gather of the results.  The per-rank 'work' is a stand-in arithmetic op: the kernels need a GPU,
 the communication pattern does not."""
 import os
-import socket
 import sys
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from loop_helpers import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q):
@@ -48,7 +41,7 @@ def test_scatter_gather_world2():
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -125,7 +118,7 @@ def test_window_parallel_world3_matches_one_rank_and_the_oracle():
     world = 3
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_wp_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()

@@ -4,25 +4,18 @@ dp.scatter_clips -> MikuDanceVideoPipeline.denoise -> dp.gather_latents on two D
 against the CPU oracle, and the gathered list on rank 0 checked again.  The RCCL transport itself (device tensors over xGMI)
 is run by the driver's multi-GPU bench only -- stated in DESIGN.md."""
 import os
-import socket
 import sys
 
 import pytest
 import torch
 import torch.multiprocessing as mp
 
+from loop_helpers import free_port
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS, GUIDANCE = 2, 3.5
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q):
@@ -81,7 +74,7 @@ def test_two_ranks_real_denoise_each_rank_vs_oracle():
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -152,7 +145,7 @@ def test_window_parallel_two_ranks_real_kernels():
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_wp_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()

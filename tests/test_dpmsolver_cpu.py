@@ -2,23 +2,20 @@
 restatement of tests/dpmpp_ref.py, the order-1 / DDIM identity, convergence on an analytic model, the host loop of
 MikuDanceVideoPipeline.denoise() on an emulated operator layer (one rank and three gloo ranks) against the oracle, and the refusals."""
 import math
-import os
-import socket
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import mikudance_amd as M
 from mikudance_amd.selftest import SCHED_KWARGS
 
 import dpmpp_ref as R
+import fake_ops
+from loop_helpers import CountingUNet, rel_l2, run_world, small_cpu, small_inputs, worker_setup, zero_inputs  # noqa: F401 (small_cpu: fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = [dict(solver_order=1), dict(solver_type="midpoint"), dict(solver_type="heun"),
          dict(algorithm_type="sde-dpmsolver++", solver_type="midpoint"), dict(algorithm_type="sde-dpmsolver++", solver_type="heun"),
          dict(solver_order=1, algorithm_type="sde-dpmsolver++")]
@@ -30,36 +27,6 @@ def _sched(**kw):
 
 def _ref_coeffs(n, kw):
     return R.coefficients(n, kw.get("solver_order", 2), kw.get("algorithm_type", "dpmsolver++"), kw.get("solver_type", "midpoint"))
-
-
-# ---- the operator of md_cfg_multistep_step, emulated in PyTorch (fp32 arithmetic, one rounding of the latents)
-def fake_cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, halves=2,
-                            variance_noise=None):
-    if halves == 2:
-        u, c = (noise_sum / counter.view(1, -1, 1, 1)).unbind(0)
-        v = u + guidance * (c - u)
-    else:
-        v = noise_sum[0]
-    x = latents.float().view(ftot, hw, 4)
-    m0 = alpha_s * x - sigma_s * v
-    out = c_x * x + c_m0 * m0
-    if c_m1 != 0.0:                                                # the kernel never reads the history then (uninitialised on step 0)
-        out = out + c_m1 * history.view(ftot, hw, 4)
-    history.view(ftot, hw, 4).copy_(m0)
-    if c_z != 0.0:
-        out = out + c_z * variance_noise.float().view(ftot, hw, 4)
-    latents.copy_(out.view(latents.shape).to(torch.float16))
-
-
-def _install(monkeypatch):
-    import fake_ops
-    from mikudance_amd import ops
-    fake_ops.install(monkeypatch)
-    monkeypatch.setattr(ops, "cfg_multistep_step", fake_cfg_multistep_step)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
 
 
 # ---- 1. timesteps
@@ -188,19 +155,12 @@ def test_second_order_converges_faster_on_an_analytic_model():
 
 
 # ---- 5. the host loop of denoise() on the emulated operators, against the oracle
-@pytest.fixture(scope="module")
-def small_cpu():
-    from mikudance_amd.selftest import build_models
-    return build_models(device="cpu")
-
-
 @pytest.mark.parametrize("mode", [dict(solver_type="midpoint"), dict(algorithm_type="sde-dpmsolver++")], ids=["2m", "2m-sde"])
 def test_host_loop_matches_oracle(monkeypatch, small_cpu, mode):
-    from mikudance_amd.synth import synth_inputs
     from oracle import cpu_ref as O
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, ref_sd, den_sd = small_cpu
-    lat, rl, emb = (t.half().float() for t in synth_inputs(4, 16, 16, ctx_len=5, ctx_dim=64, seed=7))
+    lat, rl, emb = small_inputs(4, 7)
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _sched(**mode))
     steps = []
     out = pipe.denoise(lat.half(), rl.half(), emb.half(), 4, 3.5, generator=torch.Generator().manual_seed(11),
@@ -209,31 +169,16 @@ def test_host_loop_matches_oracle(monkeypatch, small_cpu, mode):
     rs = R.Restated(2, mode.get("algorithm_type", "dpmsolver++"), mode.get("solver_type", "midpoint"), generator=torch.Generator().manual_seed(11))
     with torch.no_grad():
         want = O.denoise_loop(ref_sd, den_sd, lat, rl, emb, 4, guidance_scale=3.5, reduced=True, scheduler=rs)
-    r = _rel(out.float(), want)
+    r = rel_l2(out.float(), want)
     print(f"\nDPM_HOST_LOOP {mode} rel_l2 {r:.3e}")
     assert torch.isfinite(out).all() and r < 2e-2, r
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _wp_worker(rank, world, port, q):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.set_num_threads(2)
-    import fake_ops
-    from mikudance_amd import MikuDanceVideoPipeline, dp, ops
+    worker_setup(rank, world, port)
+    from mikudance_amd import MikuDanceVideoPipeline, dp
     from mikudance_amd.selftest import build_models
     from mikudance_amd.synth import synth_inputs
-    fake_ops.install_process()
-    ops.cfg_multistep_step = fake_cfg_multistep_step
-    dp.init(backend="gloo")
     ref, den, _, _ = build_models(device="cpu", keep_state_dicts=False)
     lat, rl, emb = (t.half() for t in synth_inputs(16, 16, 16, ctx_len=5, ctx_dim=64, seed=321))
     kw = dict(context_frames=8, context_stride=1, context_overlap=2)             # 3 windows, the last one wraps
@@ -250,17 +195,7 @@ def _wp_worker(rank, world, port, q):
 def test_window_parallel_world3_equals_one_rank():
     """Three gloo ranks, one window each per step, every rank keeping its own history: the 2M loop (4 steps, two of them second
     order) is bit-identical on every rank and to the one-rank loop."""
-    world = 3
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_wp_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = q.get(timeout=600)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = run_world(3, _wp_worker)
     assert res["identical_on_all_ranks"] and res["equals_one_rank"] and res["finite"], res
 
 
@@ -299,40 +234,24 @@ class _DuckScheduler:                                                 # has ever
         return self._d.step_coefficients(t)
 
 
-class _CountingUNet:
-    def __init__(self):
-        self.calls = 0
-
-    def __getattr__(self, name):
-        if name.startswith("__"):
-            raise AttributeError(name)
-        def f(*a, **k):
-            self.calls += 1
-        return f
-
-
 def _refusal_pipe(monkeypatch, sch):
-    _install(monkeypatch)
-    refu, den = _CountingUNet(), _CountingUNet()
+    fake_ops.install(monkeypatch)
+    refu, den = CountingUNet(), CountingUNet()
     return M.MikuDanceVideoPipeline(None, None, refu, den, sch), refu, den
-
-
-def _cpu_inputs():
-    return torch.zeros(1, 4, 2, 2, 2, dtype=torch.float16), torch.zeros(1, 2, 22, 2, 2, dtype=torch.float16), torch.zeros(2, 5, 64, dtype=torch.float16)
 
 
 @pytest.mark.parametrize("sch", [_DuckScheduler(), types.SimpleNamespace(init_noise_sigma=1.0, order=1)], ids=["ddim-lookalike", "other"])
 def test_foreign_scheduler_raises_type_error_before_any_unet(monkeypatch, sch):
     pipe, refu, den = _refusal_pipe(monkeypatch, sch)
     with pytest.raises(TypeError, match="DDIMScheduler.*DPMSolverMultistepScheduler"):
-        pipe.denoise(*_cpu_inputs(), 4, 3.5)
+        pipe.denoise(*zero_inputs(), 4, 3.5)
     assert refu.calls == 0 and den.calls == 0
 
 
 def test_eta_with_the_solver_raises_value_error(monkeypatch):
     pipe, refu, den = _refusal_pipe(monkeypatch, _sched())
     with pytest.raises(ValueError, match="sde-dpmsolver"):
-        pipe.denoise(*_cpu_inputs(), 4, 3.5, eta=0.5)
+        pipe.denoise(*zero_inputs(), 4, 3.5, eta=0.5)
     assert refu.calls == 0 and den.calls == 0
 
 

@@ -3,115 +3,32 @@ to the oracle at phi = 0 and to diffusers' formula on an analytic case, the host
 operators against it (one rank and three gloo ranks), the argument checks, and the script's --guidance_rescale."""
 import math
 import os
-import socket
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import mikudance_amd as M
 from mikudance_amd.selftest import SCHED_KWARGS
 
 import dpmpp_ref as R
+import fake_ops
 import rescale_ref as RR
+from loop_helpers import (CountingUNet, fake_pipeline_builder, rel_l2, run_world, script_tree, small_cpu, small_inputs,  # noqa: F401 (small_cpu: fixture)
+                          worker_setup, zero_inputs)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WRAP12 = dict(context_frames=8, context_stride=1, context_overlap=4)      # f = 12: two windows, the second wraps
 
 
-# ---- the operators of md_cfg_guidance_rescale / md_cfg_*_step_scaled, emulated in PyTorch (fp32 arithmetic, one rounding of the latents)
-CALLS = []
-
-
-def _guided(noise_sum, counter, guidance, halves):
-    if halves == 2:
-        u, c = (noise_sum / counter.view(1, -1, 1, 1)).unbind(0)
-        return u + guidance * (c - u), c
-    return noise_sum[0], None
-
-
-def fake_cfg_guidance_rescale(noise_sum, counter, ftot, hw, guidance, phi, out=None):
-    v, c = _guided(noise_sum, counter, guidance, 2)
-    sc, sv = float(c.double().std()), float(v.double().std())
-    f = 1.0 if sv == 0.0 else 1.0 - phi + phi * sc / sv
-    CALLS.append(("rescale", phi))
-    if out is None:
-        out = torch.empty((1,), dtype=torch.float32)
-    out.fill_(f)
-    return out
-
-
-def fake_cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alpha_prev, halves=2, eta=0.0, variance_noise=None, **kw):
-    CALLS.append(("ddim", tuple(kw)))
-    v, _ = _guided(noise_sum, counter, guidance, halves)
-    if "vscale" in kw:
-        v = v * kw["vscale"]
-    x = latents.float().view(ftot, hw, 4)
-    x0 = alpha_t ** 0.5 * x - (1 - alpha_t) ** 0.5 * v
-    ep = alpha_t ** 0.5 * v + (1 - alpha_t) ** 0.5 * x
-    std = eta * ((1 - alpha_prev) / (1 - alpha_t) * (1 - alpha_t / alpha_prev)) ** 0.5 if eta else 0.0
-    out = alpha_prev ** 0.5 * x0 + max(1 - alpha_prev - std ** 2, 0.0) ** 0.5 * ep
-    if eta:
-        out = out + std * variance_noise.float().view(ftot, hw, 4)
-    latents.copy_(out.view(latents.shape).to(torch.float16))
-
-
-def fake_cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, halves=2,
-                            variance_noise=None, **kw):
-    CALLS.append(("multistep", tuple(kw)))
-    v, _ = _guided(noise_sum, counter, guidance, halves)
-    if "vscale" in kw:
-        v = v * kw["vscale"]
-    x = latents.float().view(ftot, hw, 4)
-    m0 = alpha_s * x - sigma_s * v
-    out = c_x * x + c_m0 * m0
-    if c_m1 != 0.0:
-        out = out + c_m1 * history.view(ftot, hw, 4)
-    history.view(ftot, hw, 4).copy_(m0)
-    if c_z != 0.0:
-        out = out + c_z * variance_noise.float().view(ftot, hw, 4)
-    latents.copy_(out.view(latents.shape).to(torch.float16))
-
-
-def _install_process():
-    import fake_ops
-    from mikudance_amd import ops
-    fake_ops.install_process()
-    ops.cfg_guidance_rescale, ops.cfg_ddim_step, ops.cfg_multistep_step = fake_cfg_guidance_rescale, fake_cfg_ddim_step, fake_cfg_multistep_step
-    del CALLS[:]
-
-
-def _install(monkeypatch):
-    import fake_ops
-    from mikudance_amd import ops
-    fake_ops.install(monkeypatch)
-    monkeypatch.setattr(ops, "cfg_guidance_rescale", fake_cfg_guidance_rescale)
-    monkeypatch.setattr(ops, "cfg_ddim_step", fake_cfg_ddim_step)
-    monkeypatch.setattr(ops, "cfg_multistep_step", fake_cfg_multistep_step)
-    del CALLS[:]
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
+def _steps():
+    """(operator, optional tensors given) of every rescale / step call so far."""
+    return [(n, d["keywords"]) for n, d in fake_ops.tail_calls("cfg_guidance_rescale", "cfg_ddim_step", "cfg_multistep_step")]
 
 
 def _dpm():
     return M.DPMSolverMultistepScheduler(**SCHED_KWARGS)
-
-
-@pytest.fixture(scope="module")
-def small_cpu():
-    from mikudance_amd.selftest import build_models
-    return build_models(device="cpu")
-
-
-def _inputs(frames, seed):
-    from mikudance_amd.synth import synth_inputs
-    return tuple(t.half().float() for t in synth_inputs(frames, 16, 16, ctx_len=5, ctx_dim=64, seed=seed))
 
 
 # ---- 1. the restatement is the oracle's loop at phi = 0
@@ -119,7 +36,7 @@ def _inputs(frames, seed):
 def test_restatement_equals_oracle_at_phi_0(small_cpu, frames, win):
     from oracle import cpu_ref as O
     _, _, ref_sd, den_sd = small_cpu
-    lat, rl, emb = _inputs(frames, 40 + frames)
+    lat, rl, emb = small_inputs(frames, 40 + frames)
     with torch.no_grad():
         want = O.denoise_loop(ref_sd, den_sd, lat, rl, emb, 2, guidance_scale=3.5, reduced=True, **win)
         got = RR.denoise_loop(ref_sd, den_sd, lat, rl, emb, 2, guidance_scale=3.5, reduced=True, guidance_rescale=0.0, **win)
@@ -154,21 +71,20 @@ def test_rescale_formula_analytic():
 # ---- 3. the host loop of denoise() on the emulated operators, against the restatement
 @pytest.mark.parametrize("sampler", ["ddim", "2m"])
 def test_host_loop_matches_restatement(monkeypatch, small_cpu, sampler):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, ref_sd, den_sd = small_cpu
-    lat, rl, emb = _inputs(4, 7)
+    lat, rl, emb = small_inputs(4, 7)
     sch = M.DDIMScheduler(**SCHED_KWARGS) if sampler == "ddim" else _dpm()
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, sch)
     out = pipe.denoise(lat.half(), rl.half(), emb.half(), 4, 3.5, guidance_rescale=0.7)
-    kinds = [k for k, _ in CALLS]
-    step = "ddim" if sampler == "ddim" else "multistep"
-    assert kinds == ["rescale", step] * 4, kinds
-    assert all(kw == ("vscale",) for k, kw in CALLS if k == step)
+    step = "cfg_ddim_step" if sampler == "ddim" else "cfg_multistep_step"
+    assert _steps() == [("cfg_guidance_rescale", ()), (step, ("vscale",))] * 4, _steps()
+    assert all(d["phi"] == 0.7 for _, d in fake_ops.tail_calls("cfg_guidance_rescale"))
     rs = None if sampler == "ddim" else R.Restated(2, "dpmsolver++", "midpoint")
     with torch.no_grad():
         want = RR.denoise_loop(ref_sd, den_sd, lat, rl, emb, 4, guidance_scale=3.5, reduced=True, scheduler=rs, guidance_rescale=0.7)
         plain = RR.denoise_loop(ref_sd, den_sd, lat, rl, emb, 4, guidance_scale=3.5, reduced=True, scheduler=rs, guidance_rescale=0.0)
-    r, d = _rel(out.float(), want), _rel(plain, want)
+    r, d = rel_l2(out.float(), want), rel_l2(plain, want)
     print(f"\nRESCALE_HOST_LOOP {sampler} rel_l2 {r:.3e} (phi 0 vs 0.7 restated: {d:.3e})")
     assert torch.isfinite(out).all() and r < 2e-2, r
     assert r < 0.5 * d, (r, d)                                            # closer to the rescaled loop than to the plain one
@@ -176,61 +92,44 @@ def test_host_loop_matches_restatement(monkeypatch, small_cpu, sampler):
 
 @pytest.mark.parametrize("sampler", ["ddim", "2m"])
 def test_phi_0_calls_only_the_unscaled_entry_points(monkeypatch, small_cpu, sampler):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
-    lat, rl, emb = (t.half() for t in _inputs(4, 9))
+    lat, rl, emb = (t.half() for t in small_inputs(4, 9))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, M.DDIMScheduler(**SCHED_KWARGS) if sampler == "ddim" else _dpm())
     a = pipe.denoise(lat, rl, emb, 2, 3.5, guidance_rescale=0.0)
-    calls_a = list(CALLS)
-    del CALLS[:]
+    calls_a = fake_ops.tail_calls()
+    del fake_ops.CALLS[:]
     b = pipe.denoise(lat, rl, emb, 2, 3.5)
-    assert calls_a == list(CALLS) and all(kw == () for _, kw in calls_a) and "rescale" not in [k for k, _ in calls_a]
+    step = "cfg_ddim_step" if sampler == "ddim" else "cfg_multistep_step"
+    assert calls_a == fake_ops.tail_calls() and [(n, d["keywords"]) for n, d in calls_a if n.startswith("cfg_")] == [(step, ())] * 2
     assert torch.equal(a, b)
 
 
 # ---- 4. argument checks
-class _CountingUNet:
-    def __init__(self):
-        self.calls = 0
-
-    def __getattr__(self, name):
-        if name.startswith("__"):
-            raise AttributeError(name)
-
-        def f(*a, **k):
-            self.calls += 1
-        return f
-
-
-def _cpu_inputs():
-    return torch.zeros(1, 4, 2, 2, 2, dtype=torch.float16), torch.zeros(1, 2, 22, 2, 2, dtype=torch.float16), torch.zeros(2, 5, 64, dtype=torch.float16)
-
-
 @pytest.mark.parametrize("phi", [-0.1, 1.0001, float("nan"), float("inf")])
 @pytest.mark.parametrize("sampler", ["ddim", "2m"])
 def test_bad_phi_raises_before_any_unet(monkeypatch, phi, sampler):
-    _install(monkeypatch)
-    refu, den = _CountingUNet(), _CountingUNet()
+    fake_ops.install(monkeypatch)
+    refu, den = CountingUNet(), CountingUNet()
     pipe = M.MikuDanceVideoPipeline(None, None, refu, den, M.DDIMScheduler(**SCHED_KWARGS) if sampler == "ddim" else _dpm())
     with pytest.raises(ValueError, match="guidance_rescale"):
-        pipe.denoise(*_cpu_inputs(), 4, 3.5, guidance_rescale=phi)
-    assert refu.calls == 0 and den.calls == 0 and CALLS == []
+        pipe.denoise(*zero_inputs(), 4, 3.5, guidance_rescale=phi)
+    assert refu.calls == 0 and den.calls == 0 and fake_ops.CALLS == []
 
 
 def test_phi_without_cfg_runs_the_unscaled_path(monkeypatch, small_cpu):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
-    lat, rl, emb = (t.half() for t in _inputs(4, 11))
+    lat, rl, emb = (t.half() for t in small_inputs(4, 11))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, M.DDIMScheduler(**SCHED_KWARGS))
     a = pipe.denoise(lat, rl, emb[1:], 2, 1.0, guidance_rescale=0.7)
-    assert [k for k, _ in CALLS] == ["ddim", "ddim"] and all(kw == () for _, kw in CALLS)
+    assert _steps() == [("cfg_ddim_step", ())] * 2
     b = pipe.denoise(lat, rl, emb[1:], 2, 1.0)
     assert torch.equal(a, b)
 
 
 def test_call_forwards_guidance_rescale(monkeypatch):
     """MikuDanceVideoPipeline.__call__ and Pose2VideoPipeline.__call__ hand the keyword to denoise() (default 0.0)."""
-    import fake_ops
     from PIL import Image
     seen = []
 
@@ -252,24 +151,11 @@ def test_call_forwards_guidance_rescale(monkeypatch):
 
 
 # ---- 5. window parallelism: three gloo ranks
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _wp_worker(rank, world, port, q):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.set_num_threads(2)
+    worker_setup(rank, world, port)
     from mikudance_amd import MikuDanceVideoPipeline, dp
     from mikudance_amd.selftest import build_models
     from mikudance_amd.synth import synth_inputs
-    _install_process()
-    dp.init(backend="gloo")
     ref, den, _, _ = build_models(device="cpu", keep_state_dicts=False)
     lat, rl, emb = (t.half() for t in synth_inputs(16, 16, 16, ctx_len=5, ctx_dim=64, seed=321))
     kw = dict(context_frames=8, context_stride=1, context_overlap=2, guidance_rescale=0.7)     # 3 windows, the last one wraps
@@ -289,17 +175,8 @@ def _wp_worker(rank, world, port, q):
 
 
 def test_window_parallel_world3_equals_one_rank():
-    world = 3
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_wp_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = q.get(timeout=600)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = run_world(3, _wp_worker)
+    assert sorted(res) == ["2m", "ddim"]
     for name, r in res.items():
         assert all(r.values()), (name, r)
 
@@ -313,41 +190,17 @@ def test_script_flag_parses_and_defaults_to_0():
         IV.parse_args(["--guidance_rescale", "high"])
 
 
-def _script_tree(tmp_path, frames=2, size=32):
-    import yaml
-    from PIL import Image
-    from mikudance_amd import io_utils as U
-    os.makedirs(tmp_path / "inputs")
-    rng = np.random.default_rng(0)
-    img = lambda: Image.fromarray(rng.integers(0, 255, (size, size, 3), dtype=np.uint8))
-    img().save(tmp_path / "inputs" / "ref.png")
-    img().save(tmp_path / "inputs" / "skel.png")
-    U.save_videos_from_pil([img() for _ in range(frames)], str(tmp_path / "inputs" / "pose.mp4"), fps=12)
-    yaml.safe_dump({"noise_scheduler_kwargs": SCHED_KWARGS}, open(tmp_path / "infer.yaml", "w"))
-    yaml.safe_dump({"inference_config": str(tmp_path / "infer.yaml"), "weight_dtype": "fp16", "ref_image_path": str(tmp_path / "inputs" / "ref.png"),
-                    "ref_skel_path": str(tmp_path / "inputs" / "skel.png"), "ref_depth_path": "None", "tgt_pose_path": str(tmp_path / "inputs" / "pose.mp4"),
-                    "tgt_face_path": "None", "tgt_hand_path": "None", "tgt_w2c_path": "None", "tgt_c2w_path": "None"}, open(tmp_path / "cfg.yaml", "w"))
-    return str(tmp_path / "cfg.yaml"), size
-
-
 @pytest.mark.parametrize("argv,want", [([], 0.0), (["--guidance_rescale", "0.7"], 0.7), (["--guidance_rescale", "0.5", "--sampler", "dpmpp_2m_sde"], 0.5)])
 def test_script_flag_reaches_denoise(monkeypatch, tmp_path, argv, want):
-    import fake_ops
     from mikudance_amd import inference_video as IV
     seen = []
-
-    def build(config, infer_config, weight_dtype, device="cuda", video_decoder=False, sampler="ddim"):
-        pipe = M.MikuDanceVideoPipeline(vae=fake_ops.FakeVAE(), image_encoder=fake_ops.FakeCLIP(), reference_unet=None,
-                                        denoising_unet=types.SimpleNamespace(in_channels=4), scheduler=IV.build_scheduler(infer_config, sampler))
-        pipe._device = torch.device("cpu")
-        return pipe
 
     def spy(self, latents, *a, **kw):
         seen.append((kw["guidance_rescale"], type(self.scheduler).__name__))
         return latents
 
-    monkeypatch.setattr(IV, "build_pipeline", build)
+    monkeypatch.setattr(IV, "build_pipeline", fake_pipeline_builder(IV))
     monkeypatch.setattr(M.MikuDanceVideoPipeline, "denoise", spy)
-    cfg, size = _script_tree(tmp_path)
+    cfg, size = script_tree(tmp_path)
     out = IV.main(["--config", cfg, "-W", str(size), "-H", str(size), "--steps", "2", "--output_dir", str(tmp_path / "out")] + argv)
     assert os.path.exists(out) and len(seen) == 1 and seen[0][0] == want and math.isfinite(seen[0][0])

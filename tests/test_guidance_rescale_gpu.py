@@ -191,6 +191,23 @@ def test_bad_arguments_raise():
     with pytest.raises(_lib.MdanceHipError):
         _lib.call("md_cfg_multistep_step_scaled", lat.data_ptr(), ns.data_ptr(), cnt.data_ptr(), hist.data_ptr(), 0, out.data_ptr(), ftot, hw,
                   2, 3.5, 0.5, 0.5, 1.0, 1.0, 0.0, 0.5, ops._st())            # c_z != 0 without variance noise
+    # the unscaled DDIM entries share those checks: a null buffer or a non-finite coefficient is refused and the latents stay as they were
+    lat.copy_(torch.randn(lat.shape, generator=torch.Generator().manual_seed(3)))
+    keep, z = lat.clone(), torch.zeros_like(lat)
+    nan, inf = float("nan"), float("inf")
+    plain = lambda l=lat.data_ptr(), n=ns.data_ptr(), c=cnt.data_ptr(), halves=2, g=3.5, a_t=0.3, a_p=0.5: _lib.call(
+        "md_cfg_ddim_step", l, n, c, ftot, hw, halves, g, a_t, a_p, ops._st())
+    with_eta = lambda l=lat.data_ptr(), n=ns.data_ptr(), c=cnt.data_ptr(), zp=z.data_ptr(), halves=2, g=3.5, a_t=0.3, a_p=0.5, eta=0.5: _lib.call(
+        "md_cfg_ddim_step_eta", l, n, c, zp, ftot, hw, halves, g, a_t, a_p, eta, ops._st())
+    common = (dict(l=0), dict(n=0), dict(c=0), dict(a_t=nan), dict(a_p=nan), dict(g=inf), dict(g=nan), dict(halves=3))
+    for call, cases in ((plain, common), (with_eta, common + (dict(eta=nan), dict(eta=inf), dict(eta=-0.5), dict(zp=0)))):
+        for kw in cases:
+            with pytest.raises(_lib.MdanceHipError):
+                call(**kw)
+            assert torch.equal(lat, keep), kw
+    plain(c=0, halves=1)                                                   # no CFG: the counter is not read and may be NULL
+    with_eta(zp=0, eta=0.0)                                                # eta == 0: neither is the noise
+    assert torch.isfinite(lat).all() and not torch.equal(lat, keep)
     torch.cuda.synchronize()
 
 

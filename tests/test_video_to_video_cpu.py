@@ -14,7 +14,9 @@ import mikudance_amd as M
 from mikudance_amd.selftest import SCHED_KWARGS
 
 import dpmpp_ref as R
+import fake_ops
 import v2v_ref as V
+from loop_helpers import CountingUNet, fake_pipeline_builder, rel_l2, script_tree, small_cpu, small_inputs, zero_inputs  # noqa: F401 (small_cpu: fixture)
 
 MODES = [dict(), dict(algorithm_type="sde-dpmsolver++"), dict(solver_type="heun"), dict(algorithm_type="sde-dpmsolver++", solver_type="heun")]
 MODE_IDS = ["2m-midpoint", "2m-sde-midpoint", "2m-heun", "2m-sde-heun"]
@@ -27,50 +29,6 @@ def _dpm(**kw):
 
 def _ddim():
     return M.DDIMScheduler(**SCHED_KWARGS)
-
-
-# ---- the operators, emulated in PyTorch (fp32 arithmetic, one rounding of the latents), for the ones tests/fake_ops.py does not have
-CALLS = []
-
-
-def fake_add_noise(latents, x0, a, b):
-    CALLS.append(("add_noise", (a, b)))
-    z = latents.float()
-    out = b * z if a == 0.0 else a * x0.float() + b * z
-    latents.copy_(out.to(torch.float16))
-    return latents
-
-
-def fake_cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, halves=2,
-                            variance_noise=None, **kw):
-    CALLS.append(("multistep", (alpha_s, c_m1)))
-    if halves == 2:
-        u, c = (noise_sum / counter.view(1, -1, 1, 1)).unbind(0)
-        v = u + guidance * (c - u)
-    else:
-        v = noise_sum[0]
-    x = latents.float().view(ftot, hw, 4)
-    m0 = alpha_s * x - sigma_s * v
-    out = c_x * x + c_m0 * m0
-    if c_m1 != 0.0:
-        out = out + c_m1 * history.view(ftot, hw, 4)
-    history.view(ftot, hw, 4).copy_(m0)
-    if c_z != 0.0:
-        out = out + c_z * variance_noise.float().view(ftot, hw, 4)
-    latents.copy_(out.view(latents.shape).to(torch.float16))
-
-
-def _install(monkeypatch):
-    import fake_ops
-    from mikudance_amd import ops
-    fake_ops.install(monkeypatch)
-    monkeypatch.setattr(ops, "add_noise", fake_add_noise, raising=False)
-    monkeypatch.setattr(ops, "cfg_multistep_step", fake_cfg_multistep_step)
-    del CALLS[:]
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
 
 
 # ---- 1. get_timesteps: diffusers' img2img rule, literally
@@ -144,23 +102,6 @@ def test_set_begin_index_refuses_bad_indices():
 
 
 # ---- 3. argument checks, raised on CPU tensors before anything runs
-class _CountingUNet:
-    def __init__(self):
-        self.calls = 0
-
-    def __getattr__(self, name):
-        if name.startswith("__"):
-            raise AttributeError(name)
-
-        def f(*a, **k):
-            self.calls += 1
-        return f
-
-
-def _cpu_inputs():
-    return torch.zeros(1, 4, 2, 2, 2, dtype=torch.float16), torch.zeros(1, 2, 22, 2, 2, dtype=torch.float16), torch.zeros(2, 5, 64, dtype=torch.float16)
-
-
 BAD = [  # (strength, init_latents shape or None, steps, message)
     (float("nan"), (1, 4, 2, 2, 2), 4, "strength must be"), (float("inf"), (1, 4, 2, 2, 2), 4, "strength must be"),
     (0.0, (1, 4, 2, 2, 2), 4, "strength must be"), (-0.5, (1, 4, 2, 2, 2), 4, "strength must be"), (1.5, (1, 4, 2, 2, 2), 4, "strength must be"),
@@ -172,24 +113,17 @@ BAD = [  # (strength, init_latents shape or None, steps, message)
 @pytest.mark.parametrize("strength,shape,steps,msg", BAD)
 @pytest.mark.parametrize("make", [_ddim, _dpm], ids=["ddim", "dpm"])
 def test_bad_arguments_raise_before_any_unet(strength, shape, steps, msg, make):
-    refu, den = _CountingUNet(), _CountingUNet()
+    refu, den = CountingUNet(), CountingUNet()
     pipe = M.MikuDanceVideoPipeline(None, None, refu, den, make())
     init = None if shape is None else torch.zeros(shape, dtype=torch.float16)
     with pytest.raises(ValueError, match=msg):
-        pipe.denoise(*_cpu_inputs(), steps, 3.5, init_latents=init, strength=strength)
+        pipe.denoise(*zero_inputs(), steps, 3.5, init_latents=init, strength=strength)
     assert refu.calls == 0 and den.calls == 0
 
 
 # ---- 4. the host loop on emulated operators
-@pytest.fixture(scope="module")
-def small_cpu():
-    from mikudance_amd.selftest import build_models
-    return build_models(device="cpu")
-
-
 def _inputs(frames, seed):
-    from mikudance_amd.synth import synth_inputs
-    lat, rl, emb = (t.half() for t in synth_inputs(frames, 16, 16, ctx_len=5, ctx_dim=64, seed=seed))
+    lat, rl, emb = (t.half() for t in small_inputs(frames, seed))
     x0 = (torch.randn(lat.shape, generator=torch.Generator().manual_seed(seed + 1)) * 0.8).half()
     return lat, rl, emb, x0
 
@@ -197,7 +131,7 @@ def _inputs(frames, seed):
 @pytest.mark.parametrize("sampler,strength", [("ddim", 0.5), ("2m", 0.5), ("2m", 0.3), ("2m-sde", 0.5)])
 def test_host_loop_matches_oracle(monkeypatch, small_cpu, sampler, strength):
     from oracle import cpu_ref as O
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, ref_sd, den_sd = small_cpu
     lat, rl, emb, x0 = _inputs(4, 21)
     algo = "sde-dpmsolver++" if sampler == "2m-sde" else "dpmsolver++"
@@ -208,22 +142,24 @@ def test_host_loop_matches_oracle(monkeypatch, small_cpu, sampler, strength):
                        callback=lambda i, t, x: steps.append((i, t)))
     kept = V.kept_steps(8, strength)
     assert steps == list(enumerate([999, 874, 749, 624, 499, 374, 249, 124][8 - kept:]))
-    assert CALLS[0] == ("add_noise", sch.noise_coefficients(steps[0][1]))
+    tail = fake_ops.tail_calls()
+    a, b = sch.noise_coefficients(steps[0][1])
+    assert tail[0] == ("add_noise", dict(a=a, b=b, keywords=()))
     if sampler != "ddim":
-        assert [c for k, c in CALLS if k == "multistep"][0][1] == 0.0      # the first kept step is order 1
+        assert fake_ops.tail_calls("cfg_multistep_step")[0][1]["c_m1"] == 0.0      # the first kept step is order 1
     inner = O.DDIM() if sampler == "ddim" else R.Restated(2, algo, "midpoint", generator=torch.Generator().manual_seed(5))
     with torch.no_grad():
         want = V.denoise_loop(ref_sd, den_sd, lat.float(), rl.float(), emb.float(), 8, x0.float(), strength, scheduler=inner,
                               guidance_scale=3.5, reduced=True)
         plain = O.denoise_loop(ref_sd, den_sd, lat.float(), rl.float(), emb.float(), 8, guidance_scale=3.5, reduced=True)
-    r = _rel(out.float(), want)
-    print(f"\nV2V_HOST_LOOP {sampler} strength {strength} rel_l2 {r:.3e} (from the plain loop {_rel(want, plain):.3e})")
-    assert torch.isfinite(out).all() and r < 2e-2 and _rel(want, plain) > 0.1, r
+    r = rel_l2(out.float(), want)
+    print(f"\nV2V_HOST_LOOP {sampler} strength {strength} rel_l2 {r:.3e} (from the plain loop {rel_l2(want, plain):.3e})")
+    assert torch.isfinite(out).all() and r < 2e-2 and rel_l2(want, plain) > 0.1, r
 
 
 @pytest.mark.parametrize("sampler", ["ddim", "ddim-eta", "2m", "2m-sde"])
 def test_strength_1_equals_the_plain_loop(monkeypatch, small_cpu, sampler):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb, x0 = _inputs(4, 31)
     x0[0, 0, 0, 0, 0], x0[0, 1, 1, 1, 1] = float("nan"), float("inf")
@@ -231,9 +167,9 @@ def test_strength_1_equals_the_plain_loop(monkeypatch, small_cpu, sampler):
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, sch)
     eta = 0.5 if sampler == "ddim-eta" else 0.0
     a = pipe.denoise(lat, rl, emb, 3, 3.5, eta=eta, generator=torch.Generator().manual_seed(9))
-    assert not [k for k, _ in CALLS if k == "add_noise"]             # no new call without init_latents
+    assert not fake_ops.tail_calls("add_noise")                        # no new call without init_latents
     b = pipe.denoise(lat, rl, emb, 3, 3.5, eta=eta, generator=torch.Generator().manual_seed(9), init_latents=x0, strength=1.0)
-    assert ("add_noise", (0.0, 1.0)) in CALLS
+    assert [d for _, d in fake_ops.tail_calls("add_noise")] == [dict(a=0.0, b=1.0, keywords=())]
     assert torch.equal(a, b)
 
 
@@ -247,7 +183,6 @@ def _frames(n, size, seed):
 def test_call_encodes_video_and_forwards_it(monkeypatch):
     """MikuDanceVideoPipeline.__call__ and Pose2VideoPipeline.__call__: the frames are encoded like the reference image and reach denoise()
     as init_latents (1, 4, F, h, w) with strength; the noise is the generator's first draw, as without video."""
-    import fake_ops
     from mikudance_amd.pipeline_mikudance import _pil_to_tensor
     seen = []
 
@@ -296,40 +231,18 @@ def test_script_flags_parse():
             IV.parse_args(argv)
 
 
-def _script_tree(tmp_path, frames=2, size=32):
-    import yaml
-    from mikudance_amd import io_utils as U
-    os.makedirs(tmp_path / "inputs")
-    ims = _frames(2 + frames, size, 0)
-    ims[0].save(tmp_path / "inputs" / "ref.png")
-    ims[1].save(tmp_path / "inputs" / "skel.png")
-    U.save_videos_from_pil(ims[2:], str(tmp_path / "inputs" / "pose.mp4"), fps=12)
-    yaml.safe_dump({"noise_scheduler_kwargs": SCHED_KWARGS}, open(tmp_path / "infer.yaml", "w"))
-    yaml.safe_dump({"inference_config": str(tmp_path / "infer.yaml"), "weight_dtype": "fp16", "ref_image_path": str(tmp_path / "inputs" / "ref.png"),
-                    "ref_skel_path": str(tmp_path / "inputs" / "skel.png"), "ref_depth_path": "None", "tgt_pose_path": str(tmp_path / "inputs" / "pose.mp4"),
-                    "tgt_face_path": "None", "tgt_hand_path": "None", "tgt_w2c_path": "None", "tgt_c2w_path": "None"}, open(tmp_path / "cfg.yaml", "w"))
-    return str(tmp_path / "cfg.yaml"), size
-
-
 def test_script_init_video_reaches_denoise_and_frame_counts_must_match(monkeypatch, tmp_path):
-    import fake_ops
     from mikudance_amd import inference_video as IV
     from mikudance_amd import io_utils as U
     seen = []
-
-    def build(config, infer_config, weight_dtype, device="cuda", video_decoder=False, sampler="ddim"):
-        pipe = M.MikuDanceVideoPipeline(vae=fake_ops.FakeVAE(), image_encoder=fake_ops.FakeCLIP(), reference_unet=None,
-                                        denoising_unet=types.SimpleNamespace(in_channels=4), scheduler=IV.build_scheduler(infer_config, sampler))
-        pipe._device = torch.device("cpu")
-        return pipe
 
     def spy(self, latents, *a, **kw):
         seen.append((kw["init_latents"], kw["strength"]))
         return latents
 
-    monkeypatch.setattr(IV, "build_pipeline", build)
+    monkeypatch.setattr(IV, "build_pipeline", fake_pipeline_builder(IV))
     monkeypatch.setattr(M.MikuDanceVideoPipeline, "denoise", spy)
-    cfg, size = _script_tree(tmp_path)
+    cfg, size = script_tree(tmp_path)
     init = str(tmp_path / "inputs" / "init.mp4")
     U.save_videos_from_pil(_frames(2, size, 7), init, fps=12)
     base = ["--config", cfg, "-W", str(size), "-H", str(size), "--steps", "4", "--output_dir", str(tmp_path / "out")]

@@ -1,35 +1,26 @@
 """CPU: open-ended windows (context_schedule="uniform_open") and pyramid window fusion (context_fuse="pyramid") -- the layout against its
 rule restated in tests/fusion_ref.py plus its properties, the weights against diffusers' list and their per-frame normalisation, the argument
 checks, and the host loop of MikuDanceVideoPipeline.denoise() on emulated operators against the restated loop (one rank, three gloo ranks)."""
-import os
-import socket
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import mikudance_amd as M
 from mikudance_amd.context import get_context_scheduler
 from mikudance_amd.selftest import SCHED_KWARGS
 
+import dpmpp_ref as R
+import fake_ops
 import fusion_ref as FR
 import rescale_ref as RR
+import v2v_ref as V
+from loop_helpers import (CountingUNet, cosine, fake_pipeline_builder, rel_l2, run_world, script_tree, small_cpu, small_inputs,  # noqa: F401 (small_cpu: fixture)
+                          worker_setup)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIN12 = dict(context_frames=8, context_stride=1, context_overlap=4)        # f = 12: three windows (one wrapping) closed, two open
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
-
-
-def _cos(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float(a @ b / (a.norm() * b.norm()))
 
 
 # ---- 1. the layout
@@ -123,48 +114,23 @@ def test_a_wrapped_dilated_window_names_a_frame_twice():
 
 
 # ---- 3. argument checks
-class _CountingUNet:
-    def __init__(self):
-        self.calls = 0
-
-    def __getattr__(self, name):
-        if name.startswith("__"):
-            raise AttributeError(name)
-
-        def f(*a, **k):
-            self.calls += 1
-        return f
-
-
-def _install(monkeypatch):
-    import fake_ops
-    from mikudance_amd import ops
-    fake_ops.install(monkeypatch)
-    monkeypatch.setattr(ops, "window_accumulate_weighted", FR.fake_window_accumulate_weighted, raising=False)
-    del FR.WEIGHTED_CALLS[:]
-    return fake_ops
-
-
-def _install_process():
-    import fake_ops
-    from mikudance_amd import ops
-    fake_ops.install_process()
-    ops.window_accumulate_weighted = FR.fake_window_accumulate_weighted
-    del FR.WEIGHTED_CALLS[:]
+def _weighted():
+    """(f, ftot, hw, halves) of every weighted accumulate so far."""
+    return [(d["f"], d["ftot"], d["hw"], d["halves"]) for _, d in fake_ops.tail_calls("window_accumulate_weighted")]
 
 
 @pytest.mark.parametrize("bad", ["Pyramid", "triangle", "", None, 1])
 def test_bad_fuse_raises_before_any_model(monkeypatch, bad):
-    fake_ops = _install(monkeypatch)
-    refu, den = _CountingUNet(), _CountingUNet()
+    fake_ops.install(monkeypatch)
+    refu, den = CountingUNet(), CountingUNet()
     pipe = M.MikuDanceVideoPipeline(None, None, refu, den, M.DDIMScheduler(**SCHED_KWARGS))
     lat, rl, emb = torch.zeros(1, 4, 2, 2, 2, dtype=torch.float16), torch.zeros(1, 2, 22, 2, 2, dtype=torch.float16), torch.zeros(2, 5, 64, dtype=torch.float16)
     with pytest.raises(ValueError, match="context_fuse"):
         pipe.denoise(lat, rl, emb, 4, 3.5, context_fuse=bad)
-    assert refu.calls == 0 and den.calls == 0 and FR.WEIGHTED_CALLS == []
+    assert refu.calls == 0 and den.calls == 0 and fake_ops.tail_calls() == []
     # __call__: before the CLIP tower and the VAE as well
     from PIL import Image
-    vae, clip = _CountingUNet(), _CountingUNet()
+    vae, clip = CountingUNet(), CountingUNet()
     img = Image.new("RGB", (32, 32), (40, 80, 120))
     for cls in (M.MikuDanceVideoPipeline, M.Pose2VideoPipeline):
         pipe = cls(vae=vae, image_encoder=clip, reference_unet=refu, denoising_unet=den, scheduler=M.DDIMScheduler(**SCHED_KWARGS))
@@ -177,7 +143,6 @@ def test_bad_fuse_raises_before_any_model(monkeypatch, bad):
 
 
 def test_call_forwards_both_keywords(monkeypatch):
-    import fake_ops
     from PIL import Image
     seen = []
 
@@ -207,41 +172,17 @@ def test_script_flags_parse():
             IV.parse_args(argv)
 
 
-def _script_tree(tmp_path, frames=2, size=32):
-    import yaml
-    from PIL import Image
-    from mikudance_amd import io_utils as U
-    os.makedirs(tmp_path / "inputs")
-    rng = np.random.default_rng(0)
-    img = lambda: Image.fromarray(rng.integers(0, 255, (size, size, 3), dtype=np.uint8))
-    img().save(tmp_path / "inputs" / "ref.png")
-    img().save(tmp_path / "inputs" / "skel.png")
-    U.save_videos_from_pil([img() for _ in range(frames)], str(tmp_path / "inputs" / "pose.mp4"), fps=12)
-    yaml.safe_dump({"noise_scheduler_kwargs": SCHED_KWARGS}, open(tmp_path / "infer.yaml", "w"))
-    yaml.safe_dump({"inference_config": str(tmp_path / "infer.yaml"), "weight_dtype": "fp16", "ref_image_path": str(tmp_path / "inputs" / "ref.png"),
-                    "ref_skel_path": str(tmp_path / "inputs" / "skel.png"), "ref_depth_path": "None", "tgt_pose_path": str(tmp_path / "inputs" / "pose.mp4"),
-                    "tgt_face_path": "None", "tgt_hand_path": "None", "tgt_w2c_path": "None", "tgt_c2w_path": "None"}, open(tmp_path / "cfg.yaml", "w"))
-    return str(tmp_path / "cfg.yaml"), size
-
-
 def test_script_flags_reach_the_call(monkeypatch, tmp_path):
-    import fake_ops
     from mikudance_amd import inference_video as IV
     seen = []
-
-    def build(config, infer_config, weight_dtype, device="cuda", video_decoder=False, sampler="ddim"):
-        pipe = M.MikuDanceVideoPipeline(vae=fake_ops.FakeVAE(), image_encoder=fake_ops.FakeCLIP(), reference_unet=None,
-                                        denoising_unet=types.SimpleNamespace(in_channels=4), scheduler=IV.build_scheduler(infer_config, sampler))
-        pipe._device = torch.device("cpu")
-        return pipe
 
     def spy(self, latents, ref_latents, embeds, steps, guidance, schedule, frames, stride, overlap, *a, **kw):
         seen.append((schedule, frames, stride, overlap, kw["context_fuse"]))
         return latents
 
-    monkeypatch.setattr(IV, "build_pipeline", build)
+    monkeypatch.setattr(IV, "build_pipeline", fake_pipeline_builder(IV))
     monkeypatch.setattr(M.MikuDanceVideoPipeline, "denoise", spy)
-    cfg, size = _script_tree(tmp_path)
+    cfg, size = script_tree(tmp_path)
     base = ["--config", cfg, "-W", str(size), "-H", str(size), "--steps", "2", "--output_dir", str(tmp_path / "out")]
     IV.main(base)
     IV.main(base + ["--context_schedule", "uniform_open", "--context_fuse", "pyramid", "--context_frames", "16", "--context_overlap", "4"])
@@ -249,21 +190,10 @@ def test_script_flags_reach_the_call(monkeypatch, tmp_path):
 
 
 # ---- 4. the restated loop is the oracle's at uniform + flat
-def _inputs(frames, seed):
-    from mikudance_amd.synth import synth_inputs
-    return tuple(t.half().float() for t in synth_inputs(frames, 16, 16, ctx_len=5, ctx_dim=64, seed=seed))
-
-
-@pytest.fixture(scope="module")
-def small_cpu():
-    from mikudance_amd.selftest import build_models
-    return build_models(device="cpu")
-
-
 @pytest.mark.parametrize("g", [3.5, 1.0], ids=["cfg", "nocfg"])
 def test_restatement_equals_rescale_ref_at_uniform_flat(small_cpu, g):
     _, _, ref_sd, den_sd = small_cpu
-    lat, rl, emb = _inputs(12, 52)
+    lat, rl, emb = small_inputs(12, 52)
     emb = emb if g > 1 else emb[1:]
     with torch.no_grad():
         want = RR.denoise_loop(ref_sd, den_sd, lat, rl, emb, 2, guidance_scale=g, reduced=True, **WIN12)
@@ -277,65 +207,96 @@ def test_restatement_equals_rescale_ref_at_uniform_flat(small_cpu, g):
 @pytest.mark.parametrize("fuse", ["flat", "pyramid"])
 @pytest.mark.parametrize("schedule", ["uniform", "uniform_open"])
 def test_host_loop_matches_restatement(monkeypatch, small_cpu, schedule, fuse, g):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, ref_sd, den_sd = small_cpu
-    lat, rl, emb = _inputs(12, 61)
+    lat, rl, emb = small_inputs(12, 61)
     emb = emb if g > 1 else emb[1:]
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, M.DDIMScheduler(**SCHED_KWARGS))
     out = pipe.denoise(lat.half(), rl.half(), emb.half(), 3, g, context_schedule=schedule, context_fuse=fuse, **WIN12)
     nb = 2 if g > 1 else 1
     n_win = {"uniform": 3, "uniform_open": 2}[schedule]
-    assert FR.WEIGHTED_CALLS == ([(8, 12, 256, nb)] * (3 * n_win) if fuse == "pyramid" else [])
+    assert _weighted() == ([(8, 12, 256, nb)] * (3 * n_win) if fuse == "pyramid" else [])
     with torch.no_grad():
         want = FR.denoise_loop(ref_sd, den_sd, lat, rl, emb, 3, guidance_scale=g, reduced=True, schedule=schedule, fuse=fuse, **WIN12)
-    r, c = _rel(out.float(), want), _cos(out.float(), want)
+    r, c = rel_l2(out.float(), want), cosine(out.float(), want)
     print(f"\nFUSION_HOST_LOOP {schedule} {fuse} g={g} rel_l2 {r:.3e} cos {c:.7f}")
     assert torch.isfinite(out).all() and r <= 3e-2 and c >= 0.999, (r, c)
 
 
 def test_defaults_never_call_the_weighted_op_and_keep_the_bits(monkeypatch, small_cpu):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
-    lat, rl, emb = (t.half() for t in _inputs(12, 63))
+    lat, rl, emb = (t.half() for t in small_inputs(12, 63))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, M.DDIMScheduler(**SCHED_KWARGS))
     a = pipe.denoise(lat, rl, emb, 2, 3.5, context_schedule="uniform", context_fuse="flat", **WIN12)
     b = pipe.denoise(lat, rl, emb, 2, 3.5, **WIN12)
-    assert torch.equal(a, b) and FR.WEIGHTED_CALLS == []
+    assert torch.equal(a, b) and _weighted() == []
     c = pipe.denoise(lat, rl, emb, 2, 3.5, context_fuse="pyramid", **WIN12)
-    assert not torch.equal(a, c) and len(FR.WEIGHTED_CALLS) == 6          # the keyword is not silently ignored
+    assert not torch.equal(a, c) and len(_weighted()) == 6          # the keyword is not silently ignored
 
 
 @pytest.mark.parametrize("g", [3.5, 1.0], ids=["cfg", "nocfg"])
 def test_single_window_pyramid_is_bitwise_flat(monkeypatch, small_cpu, g):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
-    lat, rl, emb = (t.half() for t in _inputs(4, 65))
+    lat, rl, emb = (t.half() for t in small_inputs(4, 65))
     emb = emb if g > 1 else emb[1:]
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, M.DDIMScheduler(**SCHED_KWARGS))
     a = pipe.denoise(lat, rl, emb, 2, g)
     b = pipe.denoise(lat, rl, emb, 2, g, context_fuse="pyramid", context_schedule="uniform_open")
-    assert torch.equal(a, b) and len(FR.WEIGHTED_CALLS) == 2
+    assert torch.equal(a, b) and len(_weighted()) == 2
+
+
+def _check_combined(tag, out, want):
+    r, c = rel_l2(out.float(), want), cosine(out.float(), want)
+    print(f"\nFUSION_HOST_LOOP {tag} rel_l2 {r:.3e} cos {c:.7f}")
+    assert torch.isfinite(out).all() and r <= 3e-2 and c >= 0.999, (r, c)
+
+
+def test_loop_with_guidance_rescale(monkeypatch, small_cpu):
+    """Pyramid fusion on open windows feeding guidance rescale and the scaled DDIM step: the CPU counterpart of the GPU test of this name."""
+    fake_ops.install(monkeypatch)
+    ref, den, ref_sd, den_sd = small_cpu
+    lat, rl, emb = small_inputs(12, 330)
+    kw = dict(guidance_rescale=0.7, **WIN12)
+    pipe = M.MikuDanceVideoPipeline(None, None, ref, den, M.DDIMScheduler(**SCHED_KWARGS))
+    out = pipe.denoise(lat.half(), rl.half(), emb.half(), 3, 3.5, context_schedule="uniform_open", context_fuse="pyramid", **kw)
+    tail = fake_ops.tail_calls()
+    assert [(n, d["keywords"]) for n, d in tail] == ([("window_accumulate_weighted", ())] * 2 + [("cfg_guidance_rescale", ()), ("cfg_ddim_step", ("vscale",))]) * 3
+    assert _weighted() == [(8, 12, 256, 2)] * 6 and all(d["phi"] == 0.7 for _, d in fake_ops.tail_calls("cfg_guidance_rescale"))
+    with torch.no_grad():
+        want = FR.denoise_loop(ref_sd, den_sd, lat, rl, emb, 3, guidance_scale=3.5, reduced=True, schedule="uniform_open", fuse="pyramid", **kw)
+    _check_combined("rescale 0.7 ddim uniform_open pyramid", out, want)
+
+
+def test_loop_with_video_to_video(monkeypatch, small_cpu):
+    """Pyramid fusion on open windows inside a truncated, pre-noised DPM-Solver++ 2M schedule: the CPU counterpart of the GPU test of this name."""
+    from oracle import cpu_ref as O
+    fake_ops.install(monkeypatch)
+    ref, den, ref_sd, den_sd = small_cpu
+    lat, rl, emb = small_inputs(12, 340)
+    x0 = (torch.randn(lat.shape, generator=torch.Generator().manual_seed(341)) * 0.8).half().float()
+    strength, kept = 0.7, 2
+    assert V.kept_steps(3, strength) == kept
+    pipe = M.MikuDanceVideoPipeline(None, None, ref, den, M.DPMSolverMultistepScheduler(**SCHED_KWARGS))
+    out = pipe.denoise(lat.half(), rl.half(), emb.half(), 3, 3.5, init_latents=x0.half(), strength=strength, context_schedule="uniform_open",
+                       context_fuse="pyramid", **WIN12)
+    tail = fake_ops.tail_calls()
+    assert [(n, d["keywords"]) for n, d in tail] == [("add_noise", ())] + ([("window_accumulate_weighted", ())] * 2 + [("cfg_multistep_step", ())]) * kept
+    assert _weighted() == [(8, 12, 256, 2)] * (2 * kept) and fake_ops.tail_calls("cfg_multistep_step")[0][1]["c_m1"] == 0.0
+    start = V.noised(x0, lat, O.DDIM().set_timesteps(3)[3 - kept])
+    with torch.no_grad():
+        want = FR.denoise_loop(ref_sd, den_sd, start, rl, emb, 3, guidance_scale=3.5, reduced=True, schedule="uniform_open", fuse="pyramid",
+                               scheduler=V.Truncated(R.Restated(2, "dpmsolver++", "midpoint"), strength), **WIN12)
+    _check_combined(f"2m strength {strength} uniform_open pyramid", out, want)
 
 
 # ---- 6. window parallelism: three gloo ranks
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _wp_worker(rank, world, port, q):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.set_num_threads(2)
+    worker_setup(rank, world, port)
     from mikudance_amd import MikuDanceVideoPipeline, dp
     from mikudance_amd.selftest import build_models
     from mikudance_amd.synth import synth_inputs
-    _install_process()
-    dp.init(backend="gloo")
     ref, den, _, _ = build_models(device="cpu", keep_state_dicts=False)
     lat, rl, emb = (t.half() for t in synth_inputs(16, 16, 16, ctx_len=5, ctx_dim=64, seed=321))
     # F = 16, s = 8, o = 2, open: [0..7], [6..13], [8..15] -- three windows, one per rank, no frame in more than two of them... frames 8..13
@@ -354,15 +315,5 @@ def _wp_worker(rank, world, port, q):
 
 def test_window_parallel_world3_equals_one_rank():
     assert len(FR.open_windows(16, 8, 2, 1)) == 3
-    world = 3
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_wp_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = q.get(timeout=600)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = run_world(3, _wp_worker)
     assert all(res.values()), res

@@ -7,7 +7,6 @@ Kernel bound (derived, not tuned): fp16 inputs are exact in fp32; each contribut
 sum, each at most 2^-24 relative.  The k products together err by at most 2^-24 sum|w p|, each of the k sums by at most 2^-24 times the
 magnitude it holds, itself at most S = |initial| + sum|w p|: |error| <= (k + 1) 2^-24 S to first order."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -25,6 +24,7 @@ from oracle import cpu_ref as O  # noqa: E402
 
 import dpmpp_ref as R  # noqa: E402
 import fusion_ref as FR  # noqa: E402
+from loop_helpers import free_port  # noqa: E402
 import v2v_ref as V  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -245,14 +245,6 @@ def test_loop_with_video_to_video(small):
 
 
 # ---- 3. two ranks on one GPU
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _wp_worker(rank, world, port, q):
     try:
         sys.path.insert(0, ROOT)
@@ -286,7 +278,7 @@ def test_window_parallel_two_ranks_equal_one_rank():
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_wp_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
