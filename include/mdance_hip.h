@@ -161,6 +161,13 @@ int md_attention_plan(int D, int Lq, int Lk, int kv_stride, int ldvt, int vt_ali
 int md_temporal_attention_fwd_f16(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O,
                                   int ldo, int NB, int F, int HW, int H, int D, float scale, void* stream);
 
+/* Which kernel and workgroup geometry md_temporal_attention_fwd_f16 selects; no device access, nothing launched.  aligned16: whether Q, K,
+ * V and O are all 16-byte aligned.  Returns 500 the lane-per-query kernel (every D other than 40 / 80 / 160, or an operand that is not
+ * 16-byte aligned), 511 / 512 the matrix-core kernel with one / two 16-frame blocks (F <= 16 / F <= 32), or MD_ERR_ARG for what the
+ * entry point refuses (F outside 1..32, D no positive multiple of 8, H not a power of two <= 8, F*D too large for LDS).  *hg / *pb
+ * receive the heads and pixels one workgroup owns (either may be NULL; untouched on error).  The launcher runs the same function. */
+int md_temporal_attention_plan(int NB, int F, int HW, int H, int D, int aligned16, int* hg, int* pb);
+
 /* Layout packing at the API boundary (any strided fp16/fp32 source -> NHWC fp16 with zero channel padding and
  * nearest resize (Hin,Win)->(Ho,Wo); and back).  src/models/unet_2d_mix.py:1208-1210 (22-channel split),
  * src/models/man_module.py:27 (nearest resize), einops rearranges of src/models/resnet.py:12-16. */

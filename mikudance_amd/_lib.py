@@ -41,6 +41,7 @@ SIGNATURES = {
     "md_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "md_temporal_attention_fwd_f16": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int,
                                               c_float, P]),
+    "md_temporal_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "md_pack_nhwc_f16": (c_int, [P, c_int, P, c_int, c_int, c_long, c_long, c_long, c_long, c_long, c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_int, P]),
     "md_unpack_nhwc_f16": (c_int, [P, c_int, P, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_long, c_int, c_int,

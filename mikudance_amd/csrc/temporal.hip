@@ -388,37 +388,67 @@ __global__ __launch_bounds__(256) void temporal_attn_mfma_kernel(TemporalParams 
   }
 }
 
-template <int D, int QB>
-static void launch_temporal_mfma(TemporalParams p, hipStream_t st) {
-  // heads per workgroup: all of them unless one pixel's Q + K + V images (3 * F rows of HG * D * 2 + 16 bytes) exceed the LDS budget
-  // (48 KiB, swept 16 .. 128 at F = 16 and 48 / 64 / 100 at F = 30: profiles/r04_ab_temporal_q_and_o_through_lds.log); then as many
-  // pixels as fit, at most 4 * MAXU (pixel, head) units (MAXU = 4 / 2 per wave).  d = 40 / 80 / 160 at F <= 16: 8 / 4 / 2 heads of one pixel
+// LDS bytes of one matrix-core workgroup of HG heads x PB pixels: the Q, K and V images, 3 * F rows of PB * HG * D * 2 + 16 bytes
+static size_t temporal_mfma_lds(int F, int D, int hg, int pb) {
 #ifdef TA_Q_REGISTERS
-  constexpr int NIMG = 2;
-  const size_t cap = (size_t)(QB == 1 ? 48 : 80) * 1024;
+  return (size_t)2 * ((((size_t)F * (pb * hg * D * 2 + 16)) + 1023) / 1024 * 1024);
 #else
-  constexpr int NIMG = 3;                              // Q, K, V images
+  return (size_t)3 * F * (pb * hg * D * 2 + 16);
+#endif
+}
+
+// Plan codes (md_temporal_attention_plan exposes them so that the dispatch is testable without a GPU): 500 temporal_attn_kernel (one lane
+// per query), 511 / 512 temporal_attn_mfma_kernel with QB = 1 / 2.
+struct TemporalPlan {
+  int code, HG, PB;
+};
+
+// THE dispatch rule of md_temporal_attention_fwd_f16: the kernel and its workgroup geometry (HG heads x PB pixels) from the problem's
+// sizes and o16 (Q, K, V and O all 16-byte aligned).  The launcher and md_temporal_attention_plan both call it; no device access.
+static int temporal_plan(int NB, int F, int HW, int H, int D, bool o16, TemporalPlan* pl) {
+  MD_CHECK_ARG(F >= 1 && F <= 32, "md_temporal_attention_fwd: F=%d frames, the positional-encoding table holds 32", F);
+  MD_CHECK_ARG(D >= 8 && D % 8 == 0, "md_temporal_attention_fwd: D and strides must be multiples of 8");
+  MD_CHECK_ARG(H >= 1 && H <= 8 && (H & (H - 1)) == 0, "md_temporal_attention_fwd: H=%d heads must be a power of two <= 8", H);
+  if ((D == 40 || D == 80 || D == 160) && (long)NB * HW < (1L << 31) && o16) {
+    // heads per workgroup: all of them unless one pixel's Q + K + V images (3 * F rows of HG * D * 2 + 16 bytes) exceed the LDS budget
+    // (48 KiB, swept 16 .. 128 at F = 16 and 48 / 64 / 100 at F = 30: profiles/r04_ab_temporal_q_and_o_through_lds.log); then as many
+    // pixels as fit, at most 4 * MAXU (pixel, head) units (MAXU = 4 / 2 per wave).  d = 40 / 80 / 160 at F <= 16: 8 / 4 / 2 heads of one pixel
+    const int QB = F <= 16 ? 1 : 2;
+#ifdef TA_Q_REGISTERS
+    const size_t cap = (size_t)(QB == 1 ? 48 : 80) * 1024;
+#else
 #ifndef TA_LDS_CAP
 #define TA_LDS_CAP 48
 #endif
 #ifndef TA_LDS_CAP2
 #define TA_LDS_CAP2 48
 #endif
-  const size_t cap = (size_t)(QB == 1 ? TA_LDS_CAP : TA_LDS_CAP2) * 1024;
+    const size_t cap = (size_t)(QB == 1 ? TA_LDS_CAP : TA_LDS_CAP2) * 1024;
 #endif
-  constexpr int UNITS = QB == 1 ? 16 : 8;
-  int HG = p.H;
-#ifdef TA_Q_REGISTERS
-  auto lds = [&](int hg, int pb) { return (size_t)NIMG * ((((size_t)p.F * (pb * hg * D * 2 + 16)) + 1023) / 1024 * 1024); };
-#else
-  auto lds = [&](int hg, int pb) { return (size_t)NIMG * p.F * (pb * hg * D * 2 + 16); };
-#endif
-  while (HG > 1 && lds(HG, 1) > cap) HG >>= 1;
-  int PB = UNITS / HG;
-  while (PB > 1 && lds(HG, PB) > cap) --PB;
-  p.HG = HG; p.PB = PB;
-  const size_t smem = lds(HG, PB);
-  const int grid = cdiv((long)p.NB * p.HW, PB) * (p.H / HG);
+    const int UNITS = QB == 1 ? 16 : 8;
+    int HG = H;
+    while (HG > 1 && temporal_mfma_lds(F, D, HG, 1) > cap) HG >>= 1;
+    int PB = UNITS / HG;
+    while (PB > 1 && temporal_mfma_lds(F, D, HG, PB) > cap) --PB;
+    pl->code = 510 + QB; pl->HG = HG; pl->PB = PB;
+    return MD_OK;
+  }
+  // heads per workgroup: as many as keep one pixel's K+V (4*F*HG*D bytes) within 48 KiB and HG*F lanes within 256
+  int HG = H;
+  while (HG > 1 && ((size_t)4 * F * HG * D > 48 * 1024 || HG * F > 256)) HG >>= 1;
+  MD_CHECK_ARG((size_t)4 * F * HG * D <= 96 * 1024 && HG * F <= 256, "md_temporal_attention_fwd: F*D too large for LDS");
+  int PB = 256 / (HG * F);
+  const int pb_lds = (int)((48 * 1024) / ((size_t)4 * F * HG * D));
+  if (PB > pb_lds) PB = pb_lds;
+  if (PB < 1) PB = 1;
+  pl->code = 500; pl->HG = HG; pl->PB = PB;
+  return MD_OK;
+}
+
+template <int D, int QB>
+static void launch_temporal_mfma(const TemporalParams& p, hipStream_t st) {   // p.HG, p.PB: temporal_plan
+  const size_t smem = temporal_mfma_lds(p.F, D, p.HG, p.PB);
+  const int grid = cdiv((long)p.NB * p.HW, p.PB) * (p.H / p.HG);
   md_ensure_dynamic_lds<temporal_attn_mfma_kernel<D, QB>>(128 * 1024);
   hipLaunchKernelGGL((temporal_attn_mfma_kernel<D, QB>), dim3(grid), dim3(256), smem, st, p);
 }
@@ -437,9 +467,15 @@ static void launch_temporal(const TemporalParams& p, int grid, int threads, size
 
 extern "C" int md_temporal_attention_fwd_f16(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int NB, int F, int HW,
                                              int H, int D, float scale, void* stream) {
-  MD_CHECK_ARG(F >= 1 && F <= 32, "md_temporal_attention_fwd: F=%d frames, the positional-encoding table holds 32", F);
-  MD_CHECK_ARG(D % 8 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, "md_temporal_attention_fwd: D and strides must be multiples of 8");
-  MD_CHECK_ARG(H >= 1 && H <= 8 && (H & (H - 1)) == 0, "md_temporal_attention_fwd: H=%d heads must be a power of two <= 8", H);
+  MD_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, "md_temporal_attention_fwd: D and strides must be multiples of 8");
+#ifdef TA_Q_REGISTERS
+  const bool o16 = true;
+#else
+  // the matrix-core kernel moves every operand and the output as 16-byte pieces
+  const bool o16 = ((reinterpret_cast<uintptr_t>(O) | reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V)) & 15) == 0;
+#endif
+  TemporalPlan pl;
+  if (const int rc = temporal_plan(NB, F, HW, H, D, o16, &pl)) return rc;
   {
     // O must not overlap Q / K / V: a workgroup's output rows are other workgroups' inputs (every pixel's F frames are spread over the
     // token matrix), and the matrix-core kernel parks O in the LDS image of Q
@@ -453,16 +489,11 @@ extern "C" int md_temporal_attention_fwd_f16(const void* Q, int ldq, const void*
   p.Q = (const half_t*)Q; p.K = (const half_t*)K; p.V = (const half_t*)V; p.O = (half_t*)O;
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
   p.NB = NB; p.F = F; p.HW = HW; p.H = H; p.D = D;
+  p.PB = pl.PB; p.HG = pl.HG;
   p.scale_log2 = scale * 1.4426950408889634f;
-#ifdef TA_Q_REGISTERS
-  const bool o16 = true;
-#else
-  // the matrix-core kernel moves every operand and the output as 16-byte pieces
-  const bool o16 = ((reinterpret_cast<uintptr_t>(O) | reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V)) & 15) == 0;
-#endif
-  if ((D == 40 || D == 80 || D == 160) && (long)NB * HW < (1L << 31) && o16) {
-    hipStream_t st = (hipStream_t)stream;
-    if (F <= 16) {
+  hipStream_t st = (hipStream_t)stream;
+  if (pl.code != 500) {
+    if (pl.code == 511) {
       if (D == 40) launch_temporal_mfma<40, 1>(p, st);
       else if (D == 80) launch_temporal_mfma<80, 1>(p, st);
       else launch_temporal_mfma<160, 1>(p, st);
@@ -474,25 +505,25 @@ extern "C" int md_temporal_attention_fwd_f16(const void* Q, int ldq, const void*
     MD_CHECK_LAUNCH("md_temporal_attention_fwd");
     return MD_OK;
   }
-  // heads per workgroup: as many as keep one pixel's K+V (4*F*HG*D bytes) within 48 KiB and HG*F lanes within 256
-  int HG = H;
-  while (HG > 1 && ((size_t)4 * F * HG * D > 48 * 1024 || HG * F > 256)) HG >>= 1;
-  MD_CHECK_ARG((size_t)4 * F * HG * D <= 96 * 1024 && HG * F <= 256, "md_temporal_attention_fwd: F*D too large for LDS");
-  int PB = 256 / (HG * F);
-  const int pb_lds = (int)((48 * 1024) / ((size_t)4 * F * HG * D));
-  if (PB > pb_lds) PB = pb_lds;
-  if (PB < 1) PB = 1;
-  p.PB = PB; p.HG = HG;
-  p.scale_log2 = scale * 1.4426950408889634f;
+  const int PB = pl.PB, HG = pl.HG;
   const int threads = ((PB * HG * F + 63) / 64) * 64;
   const size_t region = (((size_t)2 * F * PB * HG * D + 1023) >> 10) << 10;   // K (and V) image, whole 1-KiB DMA rows
   const size_t smem = 2 * region;
   const int grid = cdiv((long)NB * HW, PB) * (H / HG);
-  hipStream_t st = (hipStream_t)stream;
   if (F <= 4) launch_temporal<4>(p, grid, threads, smem, st);
   else if (F <= 8) launch_temporal<8>(p, grid, threads, smem, st);
   else if (F <= 16) launch_temporal<16>(p, grid, threads, smem, st);
   else launch_temporal<32>(p, grid, threads, smem, st);
   MD_CHECK_LAUNCH("md_temporal_attention_fwd");
   return MD_OK;
+}
+
+// Which kernel and workgroup geometry md_temporal_attention_fwd_f16 selects (codes 500 / 511 / 512 above); nothing is launched and no
+// device is touched, so the table is pinned by CPU tests (tests/test_temporal_floor_cpu.py).  aligned16: the launcher's o16.
+extern "C" int md_temporal_attention_plan(int NB, int F, int HW, int H, int D, int aligned16, int* hg, int* pb) {
+  TemporalPlan pl;
+  if (const int rc = temporal_plan(NB, F, HW, H, D, aligned16 != 0, &pl)) return rc;
+  if (hg) *hg = pl.HG;
+  if (pb) *pb = pl.PB;
+  return pl.code;
 }

@@ -253,14 +253,14 @@ def softmax_rows_(x, scale=1.0):
     return x
 
 
-def temporal_attention(q, k, v, NB, F, HW, H, D, out=None):
-    """q/k/v: [(NB*F)*HW, >=H*D] token-major (frame-major rows).  Attention across the F frames of every pixel."""
+def temporal_attention(q, k, v, NB, F, HW, H, D, out=None, scale=None):
+    """q/k/v: [(NB*F)*HW, >=H*D] token-major (frame-major rows).  Attention across the F frames of every pixel; scale defaults to D ** -0.5."""
     ldq = _rowmajor(q, "q"); ldk = _rowmajor(k, "k"); ldv = _rowmajor(v, "v")
     if out is None:
         out = torch.empty((NB * F * HW, H * D), device=q.device, dtype=F16)
     ldo = _rowmajor(out, "out")
     _lib.call("md_temporal_attention_fwd_f16", q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo,
-              NB, F, HW, H, D, float(D ** -0.5), _st(),
+              NB, F, HW, H, D, float(D ** -0.5 if scale is None else scale), _st(),
               meta=(f"temporal_attention NB={NB} F={F} HW={HW} D={D}", 4.0 * NB * HW * H * F * F * D, 8.0 * NB * F * HW * H * D))
     return out
 

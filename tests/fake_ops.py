@@ -219,10 +219,10 @@ def softmax_rows_(x, scale=1.0):
     return x
 
 
-def temporal_attention(q, k, v, NB, F_, HW, H, D, out=None):
+def temporal_attention(q, k, v, NB, F_, HW, H, D, out=None, scale=None):
     C = H * D
     sh = lambda t: t[:, :C].float().view(NB, F_, HW, H, D).permute(0, 2, 3, 1, 4)        # (NB, HW, H, F, D)
-    p = torch.softmax(sh(q) @ sh(k).transpose(-1, -2) * D ** -0.5, dim=-1)
+    p = torch.softmax(sh(q) @ sh(k).transpose(-1, -2) * (D ** -0.5 if scale is None else scale), dim=-1)
     o = (p @ sh(v)).permute(0, 3, 1, 2, 4).reshape(NB * F_ * HW, C).to(F16)
     if out is not None:
         out.copy_(o)
