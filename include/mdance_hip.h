@@ -252,6 +252,25 @@ int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const voi
  * 1.0 starts from the noise itself).  n > 0, a and b finite and >= 0, both pointers 2-byte aligned; MD_ERR_ARG otherwise. */
 int md_add_noise_f16(void* latents, const void* x0, long n, float a, float b, void* stream);
 
+/* FreeInit noise re-initialisation (Wu et al., arXiv 2312.07537; diffusers FreeInitMixin._apply_free_init): between two sampling passes
+ * the result x0 is re-noised to the last training timestep and only its low spatio-temporal frequencies are kept; the high ones come from
+ * the fresh draw z.  Per channel, with 3-D transforms over (F, H, W):
+ *   out = fp16( z + IDFT3( lpf * DFT3( a x0 + b noise0 - z ) ) )
+ * which equals diffusers' real(ifftn(ifftshift(fftshift(fftn(a x0 + b noise0)) LPF + fftshift(fftn(z)) (1 - LPF)))) when lpf is the
+ * unshifted table made symmetric under k -> -k (mikudance_amd/free_init.py: freq_filter); the kernel itself takes ANY real table.
+ * out, x0, noise0, z: contiguous (F, H, W, 4) fp16 in the layout of md_pack_nhwc_f16, 8-byte aligned; out may alias x0.  lpf: (F, H, W)
+ * fp32 in unshifted (fftn) order, 4-byte aligned.  a = sqrt(abar_T), b = sqrt(1 - abar_T) of the last training timestep, from the caller
+ * in float64.  a == 0 never reads x0 (the rule of md_add_noise_f16).  All arithmetic is fp32 (dense separable DFT, twiddles from a
+ * table of n entries per axis indexed by (j k) mod n), ONE rounding to fp16 on the way out; deterministic: two calls give the same bits.
+ * md_free_init_plan: 1 when there is a kernel for the clip (1 <= F, H, W <= 256, every length, not only powers of two), else 0.
+ * workspace: 16-byte aligned, workspace_bytes >= md_free_init_workspace_bytes(F, H, W) (6 KiB + 32 bytes per pixel; 0 without a kernel).
+ * A shape without a kernel, a NULL pointer, a misaligned pointer, a or b negative or not finite, a short workspace: MD_ERR_ARG, nothing
+ * launched. */
+int md_free_init_plan(int F, int H, int W);
+size_t md_free_init_workspace_bytes(int F, int H, int W);
+int md_free_init_mix_f16(void* out, const void* x0, const void* noise0, const void* z, const float* lpf, int F, int H, int W, float a, float b,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

@@ -16,6 +16,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
     pipe(..., video=read_frames(--init_video), strength=--strength)                                (an addition: video-to-video)
     pipe(..., context_schedule=, context_fuse=, context_frames=, context_overlap=)                 (additions: how a clip longer than the
                      temporal context is cut into windows and how their overlaps are merged; defaults = the reference's call)
+    pipe(..., free_init_iters=, free_init_filter=, free_init_order=, free_init_spatial_stop=, free_init_temporal_stop=, free_init_fast=)
+                     (an addition: FreeInit noise re-initialisation, arXiv 2312.07537; default 1 pass = off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -33,6 +35,7 @@ from PIL import Image
 
 from . import (AutoencoderKL, AutoencoderKLTemporalDecoder, CLIPVisionModelWithProjection, DDIMScheduler, DPMSolverMultistepScheduler,
                MikuDanceVideoPipeline, UNet2DConditionModel, UNet2DConditionModelPlain, UNet3DConditionModel)
+from .free_init import FILTERS as FREE_INIT_FILTERS
 from .io_utils import frames_to_tensor, get_fps, load_config, read_frames, resize_depth, save_videos_grid, to_container
 from .scene_motion import camera_to_scene_motion
 
@@ -78,6 +81,15 @@ def parse_args(argv=None):
     parser.add_argument("--context_frames", type=int, default=None,
                         help="(addition) frames per window; default: the pipeline's (30, the motion module's temporal context)")
     parser.add_argument("--context_overlap", type=int, default=8, help="(addition) frames shared by neighbouring windows")
+    parser.add_argument("--free_init_iters", type=int, default=1,
+                        help="(addition) FreeInit (arXiv 2312.07537, diffusers enable_free_init): sampling passes; before every pass after the "
+                             "first the result is re-noised and only its low spatio-temporal frequencies are kept.  1 = off, 3 diffusers' value")
+    parser.add_argument("--free_init_filter", choices=FREE_INIT_FILTERS, default="butterworth", help="(addition) FreeInit's low-pass filter")
+    parser.add_argument("--free_init_order", type=int, default=4, help="(addition) order of the butterworth filter")
+    parser.add_argument("--free_init_spatial_stop", type=float, default=0.25, help="(addition) FreeInit: normalised spatial stop frequency")
+    parser.add_argument("--free_init_temporal_stop", type=float, default=0.25, help="(addition) FreeInit: normalised temporal stop frequency")
+    parser.add_argument("--free_init_fast", action="store_true",
+                        help="(addition) FreeInit: pass i of n runs int(steps / n * (i + 1)) steps (diffusers use_fast_sampling)")
     args = parser.parse_args(argv)
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
@@ -171,7 +183,9 @@ def main(argv=None):
     out = pipe(ref_image_pil, ref_skel_pil, pose_pils, face_pils, hand_pils, scene_motion_npy, width, height, num_frames,
                args.steps, args.cfg, generator=generator, guidance_rescale=args.guidance_rescale,
                video=init_pils, strength=args.strength, context_schedule=args.context_schedule, context_fuse=args.context_fuse,
-               context_frames=args.context_frames, context_overlap=args.context_overlap)
+               context_frames=args.context_frames, context_overlap=args.context_overlap, free_init_iters=args.free_init_iters,
+               free_init_filter=args.free_init_filter, free_init_order=args.free_init_order, free_init_spatial_stop=args.free_init_spatial_stop,
+               free_init_temporal_stop=args.free_init_temporal_stop, free_init_fast=args.free_init_fast)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

@@ -384,3 +384,33 @@ def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance,
     _lib.call("md_cfg_multistep_step" if vscale is None else "md_cfg_multistep_step_scaled", *bufs, history.data_ptr(), z,
               *(() if vscale is None else (vscale.data_ptr(),)), ftot, hw, halves, float(guidance), float(alpha_s), float(sigma_s), float(c_x),
               float(c_m0), float(c_m1), float(c_z), _st())
+
+
+_fi_ws = {}
+
+
+def free_init_mix(out, x0, noise0, z, lpf, a, b):
+    """FreeInit's frequency mix (md_free_init_mix_f16): out = fp16(z + IDFT3(lpf * DFT3(a x0 + b noise0 - z))) per channel over (F, H, W).
+    out / x0 / noise0 / z: contiguous (F, H, W, 4) fp16, out may be x0; lpf: contiguous (F, H, W) fp32, unshifted order
+    (free_init.freq_filter).  a == 0 never reads x0.  A shape without a kernel raises; the workspace is kept per (device, stream)."""
+    for t, name in ((out, "out"), (x0, "x0"), (noise0, "noise0"), (z, "z")):
+        _chk(t, name)
+    _chk(lpf, "lpf", torch.float32)
+    if out.dim() != 4 or out.shape[-1] != 4:
+        raise _lib.MdanceHipError(f"free_init_mix: latents must be (F, H, W, 4), got {tuple(out.shape)}")
+    F, H, W, _ = out.shape
+    if not _lib.load().md_free_init_plan(F, H, W):
+        raise _lib.MdanceHipError(f"free_init_mix: no kernel for a clip of F={F} H={H} W={W} (every axis must be 1..256)")
+    assert all(t.is_contiguous() and t.shape == out.shape for t in (out, x0, noise0, z)), [tuple(t.shape) for t in (out, x0, noise0, z)]
+    assert lpf.is_contiguous() and tuple(lpf.shape) == (F, H, W), (tuple(lpf.shape), (F, H, W))
+    need = _lib.load().md_free_init_workspace_bytes(F, H, W)
+    key = (out.device, torch.cuda.current_stream().cuda_stream)
+    ws = _fi_ws.get(key)
+    if ws is None or ws.numel() * 4 < need:
+        ws = torch.empty((need + 3) // 4, device=out.device, dtype=torch.float32)
+        _fi_ws[key] = ws
+    n = F * H * W * 4
+    _lib.call("md_free_init_mix_f16", out.data_ptr(), x0.data_ptr(), noise0.data_ptr(), z.data_ptr(), lpf.data_ptr(), F, H, W, float(a), float(b),
+              ws.data_ptr(), ws.numel() * 4, _st(),
+              meta=(f"free_init_mix F={F} H={H} W={W}", 16.0 * n * (F + H + W), 2.0 * n * 4 + 1.0 * n + 12 * 8.0 * n))
+    return out

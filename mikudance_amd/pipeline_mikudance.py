@@ -23,7 +23,7 @@ from typing import Callable, List, Optional, Union
 import numpy as np
 import torch
 
-from . import ops
+from . import free_init, ops
 from .context import get_context_scheduler
 from .mutual_mix_attention import ReferenceAttentionControl
 from .windows import accumulate_slots, fuse_weights
@@ -130,7 +130,9 @@ class MikuDanceVideoPipeline:
     @torch.no_grad()
     def denoise(self, latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule="uniform",
                 context_frames=None, context_stride=1, context_overlap=8, callback=None, callback_steps=1, eta=0.0, generator=None,
-                window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0, context_fuse="flat"):
+                window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0, context_fuse="flat", free_init_iters=1,
+                free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25, free_init_temporal_stop=0.25,
+                free_init_fast=False):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -168,9 +170,24 @@ class MikuDanceVideoPipeline:
                             WITHOUT classifier-free guidance the reference, and "flat", hand the scheduler the window SUM
                             (src/pipelines/pipeline_mikudance.py:670-674 divides under CFG only); "pyramid" always hands it the mean.
                             "flat" is bitwise the loop without the keyword; a clip of one window is the same bits under both
+        free_init_iters     FreeInit (Wu et al., arXiv 2312.07537; diffusers enable_free_init): n >= 1 sampling passes.  Pass 0 is the loop as
+                            it is.  Before every further pass one z ~ N(0, 1) is drawn (the pass's first draw, ahead of any eta / SDE draw)
+                            and md_free_init_mix_f16 replaces the latents by the low spatio-temporal frequencies of the result re-noised
+                            to the last training timestep (sqrt(abar_T) x + sqrt(1 - abar_T) noise0, noise0 = the `latents` passed in) plus
+                            the high frequencies of z; then the loop runs again from its first timestep (set_timesteps per pass, so
+                            DPM-Solver++ starts first order again; the reference-UNet banks are kept: they do not depend on the latents).
+                            callback's step_i counts from 0 in every pass.  Under window_parallel the mix is replicated on every rank (seed
+                            the ranks' generators alike, as for eta); no new collective.  Not with init_latents: re-noising to T discards
+                            what strength means.  1 (the default) is bitwise the loop without the keyword and makes no new operator call
+        free_init_filter    "butterworth" | "gaussian" | "ideal", with free_init_order (butterworth), free_init_spatial_stop and
+                            free_init_temporal_stop (normalised stop frequencies): diffusers' low-pass table, free_init.freq_filter
+        free_init_fast      diffusers' use_fast_sampling: pass i runs max(1, int(N / n * (i + 1))) steps instead of N
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         self._check_fuse(context_fuse)
+        n_fi = free_init_iters
+        free_init.check_arguments(n_fi, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
+                                  init_latents is not None, (latents.shape[2],) + tuple(latents.shape[3:]) if latents.dim() == 5 else None)
         phi = float(guidance_rescale)
         if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
             raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale}")
@@ -191,7 +208,8 @@ class MikuDanceVideoPipeline:
         if multistep and eta > 0:
             raise ValueError("eta applies to DDIMScheduler only; for stochastic DPM-Solver++ sampling use "
                              "DPMSolverMultistepScheduler(algorithm_type='sde-dpmsolver++')")
-        sch.set_timesteps(num_inference_steps)
+        fi_steps = [free_init.pass_steps(num_inference_steps, n_fi, i, free_init_fast) for i in range(n_fi)]
+        sch.set_timesteps(fi_steps[0])
         timesteps = [int(t) for t in sch.timesteps]
         t_start = 0
         if init_latents is not None:                                     # video-to-video: the tail of the schedule (DPM: begin index set)
@@ -210,6 +228,10 @@ class MikuDanceVideoPipeline:
             x0 = init_latents.to(dev)
             sx = x0.stride()
             ops.add_noise(lat, ops.pack_nhwc(x0, F_, F_, (0, sx[2], sx[1], sx[3], sx[4]), 0, c, 4, hh, ww), *sch.noise_coefficients(timesteps[0]))
+        if n_fi > 1:                                                     # FreeInit: the packed initial noise, the table, (a, b) of t = T
+            noise0 = lat.clone()
+            lpf = free_init.freq_filter(F_, hh, ww, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop).to(dev)
+            fi_ab = sch.noise_coefficients(sch.num_train_timesteps - 1)
         noise_sum = torch.zeros((nb, F_, HW, 4), device=dev, dtype=torch.float32)
         counter = torch.zeros((F_,), device=dev, dtype=torch.float32)
         windows = [list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
@@ -240,53 +262,59 @@ class MikuDanceVideoPipeline:
         den.clear_context_cache()
         refu.clear_context_cache()
         try:
-            for step_i, t in enumerate(timesteps):
-                noise_sum.zero_()
-                counter.zero_()
-                for wi, win in enumerate(windows):
-                    if window_parallel is not None and not window_parallel.mine(wi):
-                        continue                                         # another rank's window (its share arrives in the all_reduce)
-                    f = len(win)
-                    # ---- reference UNet (write): once per window unless reference_reuse is off
-                    if wi not in bank_cache or not self.reference_reuse:
-                        self._write_banks(writer, reader, embeds, ref_latents, win_long[wi], f, do_cfg, literal=not self.reference_reuse)
-                        banks = [blk.bank for blk in reader_blocks]
-                        if self.reference_reuse:
-                            bank_cache[wi] = banks
+            for fi in range(n_fi):
+                if fi > 0:                                               # re-initialise the noise, every rank the same, and start over
+                    z = self._draw_noise(latents, generator)
+                    ops.free_init_mix(lat, lat, noise0, z, lpf, *fi_ab)
+                    sch.set_timesteps(fi_steps[fi])
+                    timesteps = [int(t) for t in sch.timesteps]
+                for step_i, t in enumerate(timesteps):
+                    noise_sum.zero_()
+                    counter.zero_()
+                    for wi, win in enumerate(windows):
+                        if window_parallel is not None and not window_parallel.mine(wi):
+                            continue                                         # another rank's window (its share arrives in the all_reduce)
+                        f = len(win)
+                        # ---- reference UNet (write): once per window unless reference_reuse is off
+                        if wi not in bank_cache or not self.reference_reuse:
+                            self._write_banks(writer, reader, embeds, ref_latents, win_long[wi], f, do_cfg, literal=not self.reference_reuse)
+                            banks = [blk.bank for blk in reader_blocks]
+                            if self.reference_reuse:
+                                bank_cache[wi] = banks
+                        else:
+                            for blk, bk in zip(reader_blocks, bank_cache[wi]):
+                                blk.bank = bk
+                        # ---- denoising UNet (read)
+                        src = lat if whole else lat.index_select(0, win_long[wi])
+                        x = ops.pack_nhwc(src, nb * f, f, (0, HW * 4, 1, ww * 4, 4), 0, 4, 64, hh, ww)
+                        cross = den._cross(embeds[:nb], [i // f for i in range(nb * f)], dev)
+                        # both clip-halves are packed from the SAME latents (batch stride 0 above): the layers in front of the first attention
+                        # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
+                        pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
+                                                two_queues=self.two_queues)
+                        if wts_dev is None:
+                            ops.window_accumulate(pred, noise_sum, counter, win_dev[wi], f, F_, HW, halves=nb)
+                        else:
+                            ops.window_accumulate_weighted(pred, noise_sum, counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=nb)
+                        reader.clear()
+                        writer.clear()
+                    if window_parallel is not None:
+                        window_parallel.reduce(noise_sum, counter)
+                    if rescale:                                              # the same factor on every rank: same buffer, same arithmetic
+                        ops.cfg_guidance_rescale(noise_sum, counter, F_, HW, guidance_scale, phi, out=scaled["vscale"])
+                    if multistep:
+                        z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
+                        ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *sch.multistep_coefficients(t_start + step_i),
+                                               halves=nb, variance_noise=z, **scaled)
                     else:
-                        for blk, bk in zip(reader_blocks, bank_cache[wi]):
-                            blk.bank = bk
-                    # ---- denoising UNet (read)
-                    src = lat if whole else lat.index_select(0, win_long[wi])
-                    x = ops.pack_nhwc(src, nb * f, f, (0, HW * 4, 1, ww * 4, 4), 0, 4, 64, hh, ww)
-                    cross = den._cross(embeds[:nb], [i // f for i in range(nb * f)], dev)
-                    # both clip-halves are packed from the SAME latents (batch stride 0 above): the layers in front of the first attention
-                    # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
-                    pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
-                                            two_queues=self.two_queues)
-                    if wts_dev is None:
-                        ops.window_accumulate(pred, noise_sum, counter, win_dev[wi], f, F_, HW, halves=nb)
-                    else:
-                        ops.window_accumulate_weighted(pred, noise_sum, counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=nb)
-                    reader.clear()
-                    writer.clear()
-                if window_parallel is not None:
-                    window_parallel.reduce(noise_sum, counter)
-                if rescale:                                              # the same factor on every rank: same buffer, same arithmetic
-                    ops.cfg_guidance_rescale(noise_sum, counter, F_, HW, guidance_scale, phi, out=scaled["vscale"])
-                if multistep:
-                    z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
-                    ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *sch.multistep_coefficients(t_start + step_i),
-                                           halves=nb, variance_noise=z, **scaled)
-                else:
-                    a_t, a_prev = sch.step_coefficients(t)
-                    z = None
-                    if eta > 0:
-                        z = self._draw_noise(latents, generator)
-                    ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta), variance_noise=z,
-                                      **scaled)
-                if callback is not None and step_i % callback_steps == 0:
-                    callback(step_i, t, self._latents_out(lat, latents))
+                        a_t, a_prev = sch.step_coefficients(t)
+                        z = None
+                        if eta > 0:
+                            z = self._draw_noise(latents, generator)
+                        ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta), variance_noise=z,
+                                          **scaled)
+                    if callback is not None and step_i % callback_steps == 0:
+                        callback(step_i, t, self._latents_out(lat, latents))
         finally:
             refu.skip_dead_tail = False
             reader.clear()
@@ -476,7 +504,8 @@ class MikuDanceVideoPipeline:
                  return_dict: bool = True, callback: Optional[Callable[[int, int, torch.FloatTensor], None]] = None,
                  callback_steps: Optional[int] = 1, context_schedule="uniform", context_frames=None, context_stride=1,
                  context_overlap=8, context_batch_size=1, interpolation_factor=1, guidance_rescale: float = 0.0, video=None, strength: float = 1.0,
-                 context_fuse="flat", **kwargs):
+                 context_fuse="flat", free_init_iters=1, free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25,
+                 free_init_temporal_stop=0.25, free_init_fast=False, **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -490,6 +519,11 @@ class MikuDanceVideoPipeline:
         if video is not None and len(video) != video_length:
             raise ValueError(f"video has {len(video)} frames, video_length is {video_length}: they must be equal")
         self._check_strength(strength, video is not None, num_inference_steps)
+        # free_init_*: FreeInit passes (denoise()); checked here too, the clip's latent shape included, before anything runs
+        fi_kw = dict(free_init_iters=free_init_iters, free_init_filter=free_init_filter, free_init_order=free_init_order,
+                     free_init_spatial_stop=free_init_spatial_stop, free_init_temporal_stop=free_init_temporal_stop, free_init_fast=free_init_fast)
+        free_init.check_arguments(free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
+                                  video is not None, (video_length, (height or 768) // 8, (width or 768) // 8))
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -524,7 +558,7 @@ class MikuDanceVideoPipeline:
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
                                context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
                                guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength,
-                               context_fuse=context_fuse)
+                               context_fuse=context_fuse, **fi_kw)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)
