@@ -244,6 +244,38 @@ int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const voi
                                  const float* vscale, int Ftot, int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x,
                                  float c_m0, float c_m1, float c_z, void* stream);
 
+/* Adaptive projected guidance (APG; Sadat, Hilliges, Weber, "Eliminating Oversaturation and Artifacts of High Guidance Scales in Diffusion
+ * Models", arXiv 2410.02416, Algorithm 1; diffusers AdaptiveProjectedGuidance), applied to the window-averaged halves between
+ * src/pipelines/pipeline_mikudance.py:670-674 (CFG) and :678 (scheduler.step).  It acts on the data prediction, and the statistics are
+ * taken PER FRAME over that frame's HW 4 elements (diffusers reduces over every non-batch dimension, i.e. the whole clip).  With
+ * a = alpha_s = sqrt(abar_t), s = sigma_s = sqrt(1 - abar_t), x the latents, u = noise_sum[0] / counter, c = noise_sum[1] / counter:
+ *   D_c = a x - s c;   m = s (u - c) + momentum m_prev          momentum_buf [Ftot][HW][4] fp32, updated in place; momentum == 0 never
+ *                                                               reads it (it may hold NaN then)
+ *   N2 = sum m^2, P = sum m D_c, Q = sum D_c^2                  per frame, accumulated in fp64 in a fixed order
+ *   S = norm_threshold == 0 || N2 == 0 ? 1 : min(1, norm_threshold / sqrt(N2));   proj = Q == 0 ? 0 : P / Q
+ *   coef[fr] = (S, (1 - eta) S proj)                            [Ftot][2] fp32 in device memory (never read back by the library)
+ * Deterministic (a fixed number of workgroups per frame over fixed slices, fixed combine order, no atomics): two calls on the same inputs
+ * give the same bits.  halves must be 2; momentum finite in (-1, 1), eta in [0, 1], norm_threshold >= 0, alpha_s / sigma_s finite; no
+ * pointer may be NULL; latents 8-byte, noise_sum / momentum_buf 16-byte, workspace 8-byte, counter / coef 4-byte aligned;
+ * workspace_bytes >= md_cfg_apg_workspace_bytes(Ftot, HW) (384 bytes per frame at most).  MD_ERR_ARG otherwise, with nothing launched. */
+size_t md_cfg_apg_workspace_bytes(int Ftot, int HW);
+int md_cfg_apg_prepare(const void* latents, const void* noise_sum, const void* counter, void* momentum_buf, int Ftot, int HW, int halves,
+                       float alpha_s, float sigma_s, float momentum, float eta, float norm_threshold, void* workspace, size_t workspace_bytes,
+                       void* coef, void* stream);
+
+/* md_cfg_ddim_step / md_cfg_ddim_step_eta and md_cfg_multistep_step with APG's guided output in place of u + guidance (c - u):
+ *   v_g = c - (guidance - 1) (S m - K D_c) / s,   D_c = a x - s c,   (S, K) = coef[frame],   m = momentum_buf
+ * as md_cfg_apg_prepare left them for THIS step (a, s: sqrt(alpha_t), sqrt(1 - alpha_t) of the DDIM entry; alpha_s, sigma_s of the
+ * multistep entry, whose history receives alpha_s x - sigma_s v_g).  With eta = 1, norm_threshold = 0, momentum = 0 at prepare this is
+ * u + guidance (c - u) up to rounding.  halves must be 2, momentum_buf and coef not NULL, s > 0 (alpha_t in [0, 1)); other arguments as
+ * the plain entries; alignment for both as md_cfg_multistep_step, momentum_buf 16-byte, coef 4-byte.  MD_ERR_ARG otherwise, with nothing
+ * launched. */
+int md_cfg_ddim_step_apg(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const void* momentum_buf,
+                         const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
+int md_cfg_multistep_step_apg(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                              const void* momentum_buf, const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_s,
+                              float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
+
 /* Forward noising of a clean latent, the start of video-to-video sampling (`strength` < 1): latents = fp16(a x0 + b latents), computed in
  * fp32, in place, over n fp16 elements.  latents holds the N(0, 1) noise on entry; x0 is the clean VAE latent (already scaled by 0.18215),
  * both packed to the (F, h*w, 4) layout of md_pack_nhwc_f16.  a = sqrt(abar_t), b = sqrt(1 - abar_t) of the first kept timestep, computed by

@@ -179,24 +179,70 @@ __device__ __forceinline__ T guided_v(const T* __restrict__ ns, const float* __r
   return v;
 }
 
-// The argument rules all five step entry points share.  Alignment and a kernel's own buffers are its launcher's business.
-// noise_coeff: the factor of variance_noise (eta / c_z).  scaled: the *_scaled entries, which need CFG and the factor.
+// APG in the step kernels (adaptive projected guidance, the *_apg entries): the guided v is replaced by
+//   D_c = a x - s c ;  v_g = c - (g - 1) (S m - K D_c) / s
+// with c formed by guided_v, m the momentum buffer and (S, K) = coef[fr] as md_cfg_apg_prepare left them in device memory, a / s the
+// step's sqrt(abar_t) / sqrt(1 - abar_t), x the latent and gs = (g - 1) / s from the caller.  T as in guided_v.
+template <typename T>
+__device__ __forceinline__ T apg_v(const T* __restrict__ ns, const float* __restrict__ counter, const T* __restrict__ mom,
+                                   const float* __restrict__ coef, long i, long total, int fr, float guidance, float a, float s, float gs, T x) {
+  T c;
+  guided_v(ns, counter, i, total, fr, 2, guidance, &c);
+  const float S = coef[2 * fr], K = coef[2 * fr + 1];
+  const T dc = a * x - s * c;
+  return c - gs * (S * mom[i] - K * dc);
+}
+
+// What a step entry adds to the plain one: nothing, the guidance-rescale factor (*_scaled) or APG's momentum buffer and per-frame
+// coefficients (*_apg).
+struct StepExtra {
+  const float* vscale = nullptr;
+  const float* mom = nullptr;
+  const float* coef = nullptr;
+  bool scaled = false, apg = false;
+};
+
+// The argument rules all step entry points share.  Alignment and a kernel's own buffers are its launcher's business.
+// noise_coeff: the factor of variance_noise (eta / c_z).  ex.scaled: the *_scaled entries, which need CFG and the factor; ex.apg: the
+// *_apg entries, which need CFG, the momentum buffer and the coefficients.
 static int cfg_step_check(const char* who, const void* latents, const void* noise_sum, const void* counter, const void* variance_noise,
-                          bool scaled, const float* vscale, int Ftot, int HW, int halves, float noise_coeff, std::initializer_list<float> coeffs) {
+                          const StepExtra& ex, int Ftot, int HW, int halves, float noise_coeff, std::initializer_list<float> coeffs) {
   MD_CHECK_ARG(Ftot > 0 && HW > 0 && (halves == 1 || halves == 2), "%s: bad arguments", who);
   MD_CHECK_ARG(latents && noise_sum && (halves == 1 || counter), "%s: null pointer", who);
-  MD_CHECK_ARG(!scaled || (halves == 2 && vscale && ((uintptr_t)vscale % 4) == 0),
+  MD_CHECK_ARG(!ex.scaled || (halves == 2 && ex.vscale && ((uintptr_t)ex.vscale % 4) == 0),
                "%s: guidance rescale needs halves == 2 and a 4-byte aligned vscale", who);
+  MD_CHECK_ARG(!ex.apg || (halves == 2 && ex.mom && ex.coef), "%s: APG needs halves == 2, the momentum buffer and coef", who);
   for (const float c : coeffs) MD_CHECK_ARG(__builtin_isfinite(c), "%s: non-finite coefficient", who);
   MD_CHECK_ARG(noise_coeff == 0.f || variance_noise, "%s: a non-zero noise coefficient needs variance_noise", who);
   return MD_OK;
 }
 
+// The alignment md_cfg_multistep_step asks for (one pixel = 4 channels per access), which the *_apg entries ask for as well.
+static int cfg_pixel_alignment_check(const char* who, const void* latents, const void* noise_sum, const void* history,
+                                     const void* variance_noise, const StepExtra& ex) {
+  MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
+                   ((uintptr_t)variance_noise % 8) == 0,
+               "%s: latents / variance_noise need 8-byte, noise_sum / history 16-byte alignment", who);
+  MD_CHECK_ARG(!ex.apg || (((uintptr_t)ex.mom % 16) == 0 && ((uintptr_t)ex.coef % 4) == 0),
+               "%s: the momentum buffer needs 16-byte, coef 4-byte alignment", who);
+  return MD_OK;
+}
+
 // ---- CFG combine + DDIM v-prediction step -------------------------------------------------------------------------------
-//   v   = guided_v
+//   v   = guided_v                                                                   (the *_apg entry: apg_v)
 //   x0  = sqrt(a_t) x - sqrt(1-a_t) v ;  eps = sqrt(a_t) v + sqrt(1-a_t) x
 //   x'  = sqrt(a_prev) x0 + sqrt(1-a_prev) eps                                      DDIMScheduler.step
 // latents: [Ftot][HW][4] fp16, updated in place (fp32 arithmetic, one rounding).
+// ddim_update is the update every flavour of the kernel shares, from v on.
+__device__ __forceinline__ void ddim_update(half_t* __restrict__ lat, const half_t* __restrict__ variance_noise, long idx, float x, float v, float sa,
+                                            float sb, float sap, float sdir, float sigma) {
+  const float x0 = sa * x - sb * v;
+  const float ep = sa * v + sb * x;
+  float out = sap * x0 + sdir * ep;                              // sdir = sqrt(1 - alpha_prev - sigma^2)
+  if (variance_noise) out += sigma * (float)variance_noise[idx];  // eta > 0: + sigma_t * z
+  lat[idx] = (half_t)out;
+}
+
 template <bool SCALED>
 __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
                                 const half_t* __restrict__ variance_noise, int Ftot, int HW4, int halves, float guidance, float sa, float sb, float sap,
@@ -206,21 +252,31 @@ __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restric
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     float v = guided_v(noise_sum, counter, idx, total, (int)(idx / HW4), halves, guidance);
     if constexpr (SCALED) v *= vs;
+    ddim_update(lat, variance_noise, idx, (float)lat[idx], v, sa, sb, sap, sdir, sigma);
+  }
+}
+
+// The APG flavour: mom [Ftot][HW][4] fp32 and coef [Ftot][2] fp32 of md_cfg_apg_prepare at THIS step's (sa, sb); gs = (guidance - 1) / sb.
+__global__ void cfg_ddim_apg_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
+                                    const half_t* __restrict__ variance_noise, int Ftot, int HW4, float guidance, float sa, float sb, float sap,
+                                    float sdir, float sigma, const float* __restrict__ mom, const float* __restrict__ coef, float gs) {
+  const long total = (long)Ftot * HW4;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const float x = (float)lat[idx];
-    const float x0 = sa * x - sb * v;
-    const float ep = sa * v + sb * x;
-    float out = sap * x0 + sdir * ep;                              // sdir = sqrt(1 - alpha_prev - sigma^2)
-    if (variance_noise) out += sigma * (float)variance_noise[idx];  // eta > 0: + sigma_t * z
-    lat[idx] = (half_t)out;
+    const float v = apg_v(noise_sum, counter, mom, coef, idx, total, (int)(idx / HW4), guidance, sa, sb, gs, x);
+    ddim_update(lat, variance_noise, idx, x, v, sa, sb, sap, sdir, sigma);
   }
 }
 
 static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW, int halves,
-                           float guidance, float alpha_t, float alpha_prev, float eta, void* stream, bool scaled, const float* vscale,
-                           const char* who) {
-  if (cfg_step_check(who, latents, noise_sum, counter, variance_noise, scaled, vscale, Ftot, HW, halves, eta, {guidance, alpha_t, alpha_prev, eta}))
+                           float guidance, float alpha_t, float alpha_prev, float eta, void* stream, const StepExtra& ex, const char* who) {
+  if (cfg_step_check(who, latents, noise_sum, counter, variance_noise, ex, Ftot, HW, halves, eta, {guidance, alpha_t, alpha_prev, eta}))
     return MD_ERR_ARG;
   MD_CHECK_ARG(eta >= 0.f, "%s: eta must be >= 0", who);
+  if (ex.apg) {
+    if (cfg_pixel_alignment_check(who, latents, noise_sum, nullptr, variance_noise, ex)) return MD_ERR_ARG;
+    MD_CHECK_ARG(alpha_t >= 0.f && alpha_t < 1.f, "%s: APG divides by sqrt(1 - alpha_t): alpha_t must be in [0, 1)", who);
+  }
   // diffusers DDIMScheduler._get_variance: sigma_t^2 = eta^2 (1 - a_prev) / (1 - a_t) (1 - a_t / a_prev); a_t == 1 never occurs (t >= 0 of a
   // zero-terminal-SNR table has a_t < 1)
   const float var = eta > 0.f ? (1.f - alpha_prev) / (1.f - alpha_t) * (1.f - alpha_t / alpha_prev) : 0.f;
@@ -228,38 +284,77 @@ static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* cou
   const float dir2 = 1.f - alpha_prev - sigma * sigma;
   const long total = (long)Ftot * HW * 4;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(scaled ? cfg_ddim_kernel<true> : cfg_ddim_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents,
-                     (const float*)noise_sum, (const float*)counter, eta > 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW * 4, halves,
-                     guidance, sqrtf(alpha_t), sqrtf(1.f - alpha_t), sqrtf(alpha_prev), sqrtf(dir2 > 0.f ? dir2 : 0.f), sigma, vscale);
+  const half_t* z = eta > 0.f ? (const half_t*)variance_noise : nullptr;
+  const float sa = sqrtf(alpha_t), sb = sqrtf(1.f - alpha_t), sap = sqrtf(alpha_prev), sdir = sqrtf(dir2 > 0.f ? dir2 : 0.f);
+  if (ex.apg)
+    hipLaunchKernelGGL(cfg_ddim_apg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+                       (const float*)counter, z, Ftot, HW * 4, guidance, sa, sb, sap, sdir, sigma, ex.mom, ex.coef, (guidance - 1.f) / sb);
+  else
+    hipLaunchKernelGGL(ex.scaled ? cfg_ddim_kernel<true> : cfg_ddim_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents,
+                       (const float*)noise_sum, (const float*)counter, z, Ftot, HW * 4, halves, guidance, sa, sb, sap, sdir, sigma, ex.vscale);
   MD_CHECK_LAUNCH(who);
   return MD_OK;
 }
 
+static StepExtra step_scaled(const float* vscale) {
+  StepExtra ex;
+  ex.scaled = true;
+  ex.vscale = vscale;
+  return ex;
+}
+
+static StepExtra step_apg(const void* momentum_buf, const float* coef) {
+  StepExtra ex;
+  ex.apg = true;
+  ex.mom = (const float*)momentum_buf;
+  ex.coef = coef;
+  return ex;
+}
+
 extern "C" int md_cfg_ddim_step(void* latents, const void* noise_sum, const void* counter, int Ftot, int HW, int halves, float guidance, float alpha_t,
                                 float alpha_prev, void* stream) {
-  return cfg_ddim_launch(latents, noise_sum, counter, nullptr, Ftot, HW, halves, guidance, alpha_t, alpha_prev, 0.f, stream, false, nullptr,
+  return cfg_ddim_launch(latents, noise_sum, counter, nullptr, Ftot, HW, halves, guidance, alpha_t, alpha_prev, 0.f, stream, StepExtra(),
                          "md_cfg_ddim_step");
 }
 
 extern "C" int md_cfg_ddim_step_eta(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW, int halves,
                                     float guidance, float alpha_t, float alpha_prev, float eta, void* stream) {
-  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream, false, nullptr,
+  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream, StepExtra(),
                          "md_cfg_ddim_step_eta");
 }
 
 extern "C" int md_cfg_ddim_step_scaled(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const float* vscale,
                                        int Ftot, int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream) {
-  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream, true, vscale,
-                         "md_cfg_ddim_step_scaled");
+  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream,
+                         step_scaled(vscale), "md_cfg_ddim_step_scaled");
+}
+
+extern "C" int md_cfg_ddim_step_apg(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const void* momentum_buf,
+                                    const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta,
+                                    void* stream) {
+  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream,
+                         step_apg(momentum_buf, coef), "md_cfg_ddim_step_apg");
 }
 
 // ---- CFG combine + DPM-Solver++ multistep step (orders 1 / 2, ODE or SDE; Lu et al., arXiv 2211.01095) ------------------
-//   v   = guided_v
+//   v   = guided_v                                 (the *_apg entry: apg_v)
 //   m0  = alpha_s x - sigma_s v                    data prediction (x0) of this step
 //   x'  = c_x x + c_m0 m0 + c_m1 m1 + c_z z        m1 = the previous step's m0 (history), z = variance noise
 // The coefficients are host scalars (DPMSolverMultistepScheduler.multistep_coefficients): every solver variant is this one update.
 // One thread per pixel (4 channels): 8-byte latents / noise, 16-byte noise_sum / history.  history is read (only when c_m1 != 0: on
 // the first step it is uninitialised) and then overwritten with m0 by the same thread at the same index.
+// multistep_update is the update every flavour of the kernel shares, from v on.
+__device__ __forceinline__ void multistep_update(half4_t* __restrict__ lat4, floatx4* __restrict__ hist, const half_t* __restrict__ variance_noise,
+                                                 long p, floatx4 x, floatx4 v, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1,
+                                                 float c_z) {
+  const floatx4 m0 = alpha_s * x - sigma_s * v;
+  floatx4 out = c_x * x + c_m0 * m0;
+  if (c_m1 != 0.f) out += c_m1 * hist[p];
+  hist[p] = m0;
+  if (variance_noise) out += c_z * __builtin_convertvector(reinterpret_cast<const half4_t*>(variance_noise)[p], floatx4);
+  lat4[p] = __builtin_convertvector(out, half4_t);
+}
+
 template <bool SCALED>
 __global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
                                      float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, int halves,
@@ -273,31 +368,47 @@ __global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __re
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     floatx4 v = guided_v(ns, counter, p, total, (int)(p / HW), halves, guidance);
     if constexpr (SCALED) v *= vs;
+    multistep_update(lat4, hist, variance_noise, p, __builtin_convertvector(lat4[p], floatx4), v, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z);
+  }
+}
+
+// The APG flavour: mom / coef of md_cfg_apg_prepare at THIS step's (alpha_s, sigma_s); gs = (guidance - 1) / sigma_s.
+__global__ void cfg_multistep_apg_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
+                                         float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, float guidance,
+                                         float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z, const float* __restrict__ mom,
+                                         const float* __restrict__ coef, float gs) {
+  const long total = (long)Ftot * HW;  // pixels
+  const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
+  const floatx4* mom4 = reinterpret_cast<const floatx4*>(mom);
+  floatx4* hist = reinterpret_cast<floatx4*>(history);
+  half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
+  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const floatx4 x = __builtin_convertvector(lat4[p], floatx4);
-    const floatx4 m0 = alpha_s * x - sigma_s * v;
-    floatx4 out = c_x * x + c_m0 * m0;
-    if (c_m1 != 0.f) out += c_m1 * hist[p];
-    hist[p] = m0;
-    if (variance_noise) out += c_z * __builtin_convertvector(reinterpret_cast<const half4_t*>(variance_noise)[p], floatx4);
-    lat4[p] = __builtin_convertvector(out, half4_t);
+    const floatx4 v = apg_v(ns, counter, mom4, coef, p, total, (int)(p / HW), guidance, alpha_s, sigma_s, gs, x);
+    multistep_update(lat4, hist, variance_noise, p, x, v, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z);
   }
 }
 
 static int cfg_multistep_launch(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise, int Ftot, int HW,
                                 int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream,
-                                bool scaled, const float* vscale, const char* who) {
-  if (cfg_step_check(who, latents, noise_sum, counter, variance_noise, scaled, vscale, Ftot, HW, halves, c_z,
+                                const StepExtra& ex, const char* who) {
+  if (cfg_step_check(who, latents, noise_sum, counter, variance_noise, ex, Ftot, HW, halves, c_z,
                      {guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z}))
     return MD_ERR_ARG;
   MD_CHECK_ARG(history, "%s: null history", who);
-  MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
-                   ((uintptr_t)variance_noise % 8) == 0,
-               "%s: latents / variance_noise need 8-byte, noise_sum / history 16-byte alignment", who);
+  if (cfg_pixel_alignment_check(who, latents, noise_sum, history, variance_noise, ex)) return MD_ERR_ARG;
+  MD_CHECK_ARG(!ex.apg || sigma_s > 0.f, "%s: APG divides by sigma_s: it must be > 0", who);
   const long total = (long)Ftot * HW;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(scaled ? cfg_multistep_kernel<true> : cfg_multistep_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                     (half_t*)latents, (const float*)noise_sum, (const float*)counter, (float*)history,
-                     c_z != 0.f ? (const half_t*)variance_noise : nullptr, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, vscale);
+  const half_t* z = c_z != 0.f ? (const half_t*)variance_noise : nullptr;
+  if (ex.apg)
+    hipLaunchKernelGGL(cfg_multistep_apg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+                       (const float*)counter, (float*)history, z, Ftot, HW, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, ex.mom, ex.coef,
+                       (guidance - 1.f) / sigma_s);
+  else
+    hipLaunchKernelGGL(ex.scaled ? cfg_multistep_kernel<true> : cfg_multistep_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                       (half_t*)latents, (const float*)noise_sum, (const float*)counter, (float*)history, z, Ftot, HW, halves, guidance, alpha_s,
+                       sigma_s, c_x, c_m0, c_m1, c_z, ex.vscale);
   MD_CHECK_LAUNCH(who);
   return MD_OK;
 }
@@ -306,14 +417,21 @@ extern "C" int md_cfg_multistep_step(void* latents, const void* noise_sum, const
                                      int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
                                      void* stream) {
   return cfg_multistep_launch(latents, noise_sum, counter, history, variance_noise, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
-                              stream, false, nullptr, "md_cfg_multistep_step");
+                              stream, StepExtra(), "md_cfg_multistep_step");
 }
 
 extern "C" int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
                                             const float* vscale, int Ftot, int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x,
                                             float c_m0, float c_m1, float c_z, void* stream) {
   return cfg_multistep_launch(latents, noise_sum, counter, history, variance_noise, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
-                              stream, true, vscale, "md_cfg_multistep_step_scaled");
+                              stream, step_scaled(vscale), "md_cfg_multistep_step_scaled");
+}
+
+extern "C" int md_cfg_multistep_step_apg(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                                         const void* momentum_buf, const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_s,
+                                         float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream) {
+  return cfg_multistep_launch(latents, noise_sum, counter, history, variance_noise, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
+                              stream, step_apg(momentum_buf, coef), "md_cfg_multistep_step_apg");
 }
 
 // ---- guidance rescale factor (Lin et al., arXiv 2305.08891 section 3.4; diffusers rescale_noise_cfg) ----------------------------------
@@ -417,6 +535,119 @@ extern "C" int md_cfg_guidance_rescale(const void* noise_sum, const void* counte
   hipLaunchKernelGGL(cfg_rescale_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, nb, (double)total * 4.0, phi,
                      (float*)out_scale);
   MD_CHECK_LAUNCH("md_cfg_guidance_rescale");
+  return MD_OK;
+}
+
+// ---- adaptive projected guidance: momentum update and per-frame coefficients (Sadat et al., arXiv 2410.02416, Algorithm 1) -------------
+// On the data prediction, per frame fr over its HW 4 elements (one frame = one sample of the paper):
+//   u, c as guided_v forms them;  D_c = a x - s c;  m = s (u - c) + beta m_prev        m: fp32, updated in place; beta == 0 never reads it
+//   N2 = sum m^2, P = sum m D_c, Q = sum D_c^2                                        fp64
+//   S = r == 0 || N2 == 0 ? 1 : min(1, r / sqrt(N2));  proj = Q == 0 ? 0 : P / Q;  coef[fr] = (S, (1 - eta) S proj)
+// The discipline of md_cfg_guidance_rescale, per frame: apg_blocks_per_frame(HW) <= 16 workgroups per frame, each over a FIXED contiguous
+// slice of that frame's pixels, reduce in fp64 through the fixed butterfly and a fixed wave order into workspace partials; ONE small launch
+// of one wave per frame then adds that frame's partials in a fixed order and writes coef[fr].  No float atomics, no host sync.
+#define APG_MAX_BPF 16
+
+static int apg_blocks_per_frame(int HW) {
+  const int b = (HW + RS_THREADS - 1) / RS_THREADS;
+  return b < APG_MAX_BPF ? b : APG_MAX_BPF;
+}
+
+// part[fr * bpf + b] = (N2, P, Q) of workgroup b's slice of frame fr.  Grid: Ftot * bpf workgroups.
+__global__ void __launch_bounds__(RS_THREADS) cfg_apg_partials_kernel(const half_t* __restrict__ lat, const float* __restrict__ noise_sum,
+                                                                      const float* __restrict__ counter, float* __restrict__ mom,
+                                                                      double* __restrict__ part, int Ftot, int HW, int bpf, int chunk, float a,
+                                                                      float s, float beta) {
+  // u and c are rounded before they are subtracted (no fma across u - c: contracted, fl(ns_u inv) - ns_c inv leaves the rounding error of one
+  // product where u == c, and that frame's N2 would not be the exact 0 the S = 1 rule tests for)
+#pragma clang fp contract(off)
+  const long total = (long)Ftot * HW;
+  const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
+  const half4_t* lat4 = reinterpret_cast<const half4_t*>(lat);
+  floatx4* mom4 = reinterpret_cast<floatx4*>(mom);
+  const int fr = blockIdx.x / bpf, b = blockIdx.x - fr * bpf;
+  const int p0 = b * chunk, p1 = min(p0 + chunk, HW);
+  const float inv = 1.f / counter[fr];
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int q = p0 + threadIdx.x; q < p1; q += RS_THREADS) {
+    const long p = (long)fr * HW + q;
+    const floatx4 u = ns[p] * inv, c = ns[total + p] * inv;  // guided_v's u and c
+    const floatx4 x = __builtin_convertvector(lat4[p], floatx4);
+    const floatx4 dc = a * x - s * c;
+    floatx4 m = s * (u - c);
+    if (beta != 0.f) m += beta * mom4[p];
+    mom4[p] = m;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double md = (double)m[e], dd = (double)dc[e];
+      acc[0] += md * md;
+      acc[1] += md * dd;
+      acc[2] += dd * dd;
+    }
+  }
+  __shared__ double red[RS_THREADS / 64][3];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    acc[q] = wave_sum_f64(acc[q]);
+    if (lane == 0) red[wave][q] = acc[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double t = 0.0;
+    for (int w = 0; w < RS_THREADS / 64; ++w) t += red[w][threadIdx.x];
+    part[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
+  }
+}
+
+// One wave per frame: lane l takes partial l of its frame (bpf <= 16 < 64), then the fixed butterfly; lane 0 writes (S, K).
+__global__ void __launch_bounds__(64) cfg_apg_finalize_kernel(const double* __restrict__ part, int bpf, float eta, float r, float* __restrict__ coef) {
+  const int fr = blockIdx.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < bpf; b += 64)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) acc[q] += part[((size_t)fr * bpf + b) * 3 + q];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) acc[q] = wave_sum_f64(acc[q]);
+  if (threadIdx.x == 0) {
+    const double N2 = acc[0], P = acc[1], Q = acc[2];
+    double S = 1.0;
+    if (r != 0.f && N2 != 0.0) {
+      const double t = (double)r / sqrt(N2);
+      S = t < 1.0 ? t : 1.0;
+    }
+    const double proj = Q == 0.0 ? 0.0 : P / Q;
+    coef[2 * fr] = (float)S;
+    coef[2 * fr + 1] = (float)((1.0 - (double)eta) * S * proj);
+  }
+}
+
+extern "C" size_t md_cfg_apg_workspace_bytes(int Ftot, int HW) {
+  return Ftot > 0 && HW > 0 ? (size_t)Ftot * apg_blocks_per_frame(HW) * 3 * sizeof(double) : 0;
+}
+
+extern "C" int md_cfg_apg_prepare(const void* latents, const void* noise_sum, const void* counter, void* momentum_buf, int Ftot, int HW, int halves,
+                                  float alpha_s, float sigma_s, float momentum, float eta, float norm_threshold, void* workspace,
+                                  size_t workspace_bytes, void* coef, void* stream) {
+  MD_CHECK_ARG(Ftot > 0 && HW > 0 && halves == 2 && (long)Ftot * APG_MAX_BPF <= 0x7fffffffL, "md_cfg_apg_prepare: bad arguments (APG needs halves == 2)");
+  MD_CHECK_ARG(latents && noise_sum && counter && momentum_buf && workspace && coef, "md_cfg_apg_prepare: null pointer");
+  MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)momentum_buf % 16) == 0 &&
+                   ((uintptr_t)workspace % 8) == 0 && ((uintptr_t)counter % 4) == 0 && ((uintptr_t)coef % 4) == 0,
+               "md_cfg_apg_prepare: latents need 8-byte, noise_sum / momentum_buf 16-byte, workspace 8-byte, counter / coef 4-byte alignment");
+  MD_CHECK_ARG(__builtin_isfinite(alpha_s) && __builtin_isfinite(sigma_s), "md_cfg_apg_prepare: non-finite coefficient");
+  MD_CHECK_ARG(__builtin_isfinite(momentum) && momentum > -1.f && momentum < 1.f && __builtin_isfinite(eta) && eta >= 0.f && eta <= 1.f &&
+                   __builtin_isfinite(norm_threshold) && norm_threshold >= 0.f,
+               "md_cfg_apg_prepare: momentum must be finite in (-1, 1), eta in [0, 1], norm_threshold >= 0");
+  MD_CHECK_ARG(workspace_bytes >= md_cfg_apg_workspace_bytes(Ftot, HW), "md_cfg_apg_prepare: workspace too small");
+  const int bpf = apg_blocks_per_frame(HW);
+  const int chunk = (HW + bpf - 1) / bpf;
+  hipLaunchKernelGGL(cfg_apg_partials_kernel, dim3(Ftot * bpf), dim3(RS_THREADS), 0, (hipStream_t)stream, (const half_t*)latents,
+                     (const float*)noise_sum, (const float*)counter, (float*)momentum_buf, (double*)workspace, Ftot, HW, bpf, chunk, alpha_s, sigma_s,
+                     momentum);
+  MD_CHECK_LAUNCH("md_cfg_apg_prepare");
+  hipLaunchKernelGGL(cfg_apg_finalize_kernel, dim3(Ftot), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, bpf, eta, norm_threshold,
+                     (float*)coef);
+  MD_CHECK_LAUNCH("md_cfg_apg_prepare");
   return MD_OK;
 }
 

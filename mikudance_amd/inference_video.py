@@ -18,6 +18,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      temporal context is cut into windows and how their overlaps are merged; defaults = the reference's call)
     pipe(..., free_init_iters=, free_init_filter=, free_init_order=, free_init_spatial_stop=, free_init_temporal_stop=, free_init_fast=)
                      (an addition: FreeInit noise re-initialisation, arXiv 2312.07537; default 1 pass = off)
+    pipe(..., apg=--apg, apg_eta=, apg_norm_threshold=, apg_momentum=)                             (an addition: adaptive projected guidance,
+                     arXiv 2410.02416, per frame on the data prediction; default off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -90,6 +92,16 @@ def parse_args(argv=None):
     parser.add_argument("--free_init_temporal_stop", type=float, default=0.25, help="(addition) FreeInit: normalised temporal stop frequency")
     parser.add_argument("--free_init_fast", action="store_true",
                         help="(addition) FreeInit: pass i of n runs int(steps / n * (i + 1)) steps (diffusers use_fast_sampling)")
+    parser.add_argument("--apg", action="store_true",
+                        help="(addition) adaptive projected guidance (arXiv 2410.02416, diffusers AdaptiveProjectedGuidance) in place of plain "
+                             "classifier-free guidance, per frame on the data prediction.  Works with every --sampler; not with "
+                             "--guidance_rescale")
+    parser.add_argument("--apg_eta", type=float, default=0.0,
+                        help="(addition) APG: weight of the part of the guidance update parallel to the conditional prediction, in [0, 1]")
+    parser.add_argument("--apg_norm_threshold", type=float, default=0.0,
+                        help="(addition) APG: cap on the per-frame norm of the guidance update, >= 0; 0 = no cap")
+    parser.add_argument("--apg_momentum", type=float, default=0.0,
+                        help="(addition) APG: momentum of the update's running average over steps, in (-1, 1); the paper uses a negative value")
     args = parser.parse_args(argv)
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
@@ -185,7 +197,8 @@ def main(argv=None):
                video=init_pils, strength=args.strength, context_schedule=args.context_schedule, context_fuse=args.context_fuse,
                context_frames=args.context_frames, context_overlap=args.context_overlap, free_init_iters=args.free_init_iters,
                free_init_filter=args.free_init_filter, free_init_order=args.free_init_order, free_init_spatial_stop=args.free_init_spatial_stop,
-               free_init_temporal_stop=args.free_init_temporal_stop, free_init_fast=args.free_init_fast)
+               free_init_temporal_stop=args.free_init_temporal_stop, free_init_fast=args.free_init_fast,
+               apg=args.apg, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

@@ -386,6 +386,53 @@ def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance,
               float(c_m0), float(c_m1), float(c_z), _st())
 
 
+_apg_ws = {}
+
+
+def _apg_buffers(momentum_buf, coef, ftot, hw):
+    _chk(momentum_buf, "momentum_buf", torch.float32); _chk(coef, "coef", torch.float32)
+    assert momentum_buf.is_contiguous() and momentum_buf.numel() == ftot * hw * 4 and coef.is_contiguous() and coef.numel() == ftot * 2
+    return momentum_buf.data_ptr(), coef.data_ptr()
+
+
+def cfg_apg_prepare(latents, noise_sum, counter, momentum_buf, coef, ftot, hw, alpha_s, sigma_s, momentum, eta, norm_threshold):
+    """Adaptive projected guidance, the statistics pass of one step (md_cfg_apg_prepare; arXiv 2410.02416 Algorithm 1 on the data prediction,
+    PER FRAME): updates the fp32 (ftot, hw, 4) `momentum_buf` in place, m = sigma_s (u - c) + momentum m (momentum == 0 never reads it), and
+    writes the fp32 (ftot, 2) `coef` = (S, (1 - eta) S proj) per frame.  Both stay on the device: hand them to cfg_ddim_step_apg /
+    cfg_multistep_step_apg with the same alpha / sigma.  The workspace is kept per (device, stream) and reused."""
+    bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, 0.0, None, None)
+    mp, cp = _apg_buffers(momentum_buf, coef, ftot, hw)
+    need = _lib.load().md_cfg_apg_workspace_bytes(ftot, hw)
+    key = (noise_sum.device, torch.cuda.current_stream().cuda_stream)
+    ws = _apg_ws.get(key)
+    if ws is None or ws.numel() * 8 < need:
+        ws = torch.empty((max(need, 1 << 14) + 7) // 8, device=noise_sum.device, dtype=torch.float64)
+        _apg_ws[key] = ws
+    n = ftot * hw * 4
+    _lib.call("md_cfg_apg_prepare", *bufs, mp, ftot, hw, 2, float(alpha_s), float(sigma_s), float(momentum), float(eta), float(norm_threshold),
+              ws.data_ptr(), ws.numel() * 8, cp, _st(), meta=(f"cfg_apg_prepare F={ftot} HW={hw}", 0.0, (2.0 + 8.0 + 8.0) * n))
+    return coef
+
+
+def cfg_ddim_step_apg(latents, noise_sum, counter, momentum_buf, coef, ftot, hw, guidance, alpha_t, alpha_prev, eta=0.0, variance_noise=None):
+    """cfg_ddim_step under CFG with APG's guided output (md_cfg_ddim_step_apg): `momentum_buf` and `coef` as cfg_apg_prepare left them for this
+    step at alpha_s = sqrt(alpha_t), sigma_s = sqrt(1 - alpha_t).  eta / variance_noise as in cfg_ddim_step."""
+    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, eta, variance_noise, None)
+    _lib.call("md_cfg_ddim_step_apg", *bufs, z, *_apg_buffers(momentum_buf, coef, ftot, hw), ftot, hw, 2, float(guidance), float(alpha_t),
+              float(alpha_prev), float(eta), _st())
+
+
+def cfg_multistep_step_apg(latents, noise_sum, counter, history, momentum_buf, coef, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
+                           variance_noise=None):
+    """cfg_multistep_step under CFG with APG's guided output (md_cfg_multistep_step_apg): `momentum_buf` and `coef` as cfg_apg_prepare left them
+    for this step at the same alpha_s, sigma_s; `history` receives alpha_s x - sigma_s v_g.  The rest as in cfg_multistep_step."""
+    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, c_z, variance_noise, None)
+    _chk(history, "history", torch.float32)
+    assert history.is_contiguous() and history.numel() == ftot * hw * 4
+    _lib.call("md_cfg_multistep_step_apg", *bufs, history.data_ptr(), z, *_apg_buffers(momentum_buf, coef, ftot, hw), ftot, hw, 2, float(guidance),
+              float(alpha_s), float(sigma_s), float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
+
+
 _fi_ws = {}
 
 

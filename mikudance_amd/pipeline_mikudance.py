@@ -132,7 +132,7 @@ class MikuDanceVideoPipeline:
                 context_frames=None, context_stride=1, context_overlap=8, callback=None, callback_steps=1, eta=0.0, generator=None,
                 window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0, context_fuse="flat", free_init_iters=1,
                 free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25, free_init_temporal_stop=0.25,
-                free_init_fast=False):
+                free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -182,6 +182,26 @@ class MikuDanceVideoPipeline:
         free_init_filter    "butterworth" | "gaussian" | "ideal", with free_init_order (butterworth), free_init_spatial_stop and
                             free_init_temporal_stop (normalised stop frequencies): diffusers' low-pass table, free_init.freq_filter
         free_init_fast      diffusers' use_fast_sampling: pass i runs max(1, int(N / n * (i + 1))) steps instead of N
+        apg                 adaptive projected guidance (Sadat, Hilliges, Weber, arXiv 2410.02416, Algorithm 1; diffusers
+                            AdaptiveProjectedGuidance) in place of u + g (c - u), under CFG only (guidance_scale > 1).  Every step, after all
+                            windows (and the all_reduce) have accumulated, md_cfg_apg_prepare forms on the DATA prediction, with a = sqrt(abar_t),
+                            s = sqrt(1 - abar_t): D_c = a x - s c and the update m = s (u - c) + apg_momentum m_prev (= D_c - D_u plus the
+                            running average, one fp32 (F, h*w, 4) buffer per call, zeroed at the start of the loop and of every FreeInit pass;
+                            under window_parallel every rank keeps its own identical copy, no new collective), then PER FRAME over that
+                            frame's h*w*4 elements S = min(1, apg_norm_threshold / ||m||) (1 when the threshold or ||m|| is 0) and
+                            proj = <m, D_c> / <D_c, D_c> (0 when D_c is 0); the step (md_cfg_*_step_apg) runs on
+                            v_g = c - (g - 1) (S m - (1 - apg_eta) S proj D_c) / s, i.e. D_g = D_c + (g - 1) (orthogonal + apg_eta * parallel
+                            part of the capped update).  One departure from diffusers, which takes the norm and the projection over every
+                            non-batch dimension and so over the whole clip: here each frame is one sample of the paper, so
+                            apg_norm_threshold does not depend on the clip's length or the window layout.  The paper's settings (eta = 0, a
+                            negative momentum, a threshold chosen per model) are the paper's; nothing here validates image quality.  Works with
+                            every sampler, eta, init_latents / strength, window schedule and fuse mode; not with guidance_rescale > 0 (that
+                            would need a second statistics pass over v_g).  False (the default) is bitwise the loop without the keywords and
+                            makes no new operator call
+        apg_eta             finite, in [0, 1]: the weight of the part of the update parallel to D_c (1 keeps it, 0 removes it)
+        apg_norm_threshold  finite, >= 0: the cap on the per-frame norm of the update; 0 = no cap
+        apg_momentum        finite, in (-1, 1): beta of the running average over steps (the paper uses a negative value); with
+                            apg_eta = 1, apg_norm_threshold = 0, apg_momentum = 0 the result is u + g (c - u) up to rounding
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         self._check_fuse(context_fuse)
@@ -192,6 +212,7 @@ class MikuDanceVideoPipeline:
         if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
             raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale}")
         self._check_strength(strength, init_latents is not None, num_inference_steps)
+        self._check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale)
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         dev = latents.device
@@ -257,6 +278,13 @@ class MikuDanceVideoPipeline:
         # entry points, called exactly as without the keyword
         rescale = do_cfg and phi > 0.0
         scaled = dict(vscale=torch.empty((1,), device=dev, dtype=torch.float32)) if rescale else {}
+        # APG: the momentum buffer and the per-frame (S, K), both written and read on the device (no host sync); off or no CFG: the plain
+        # entry points, called exactly as without the keywords
+        apg_on = do_cfg and bool(apg)
+        if apg_on:
+            apg_m = torch.zeros((F_, HW, 4), device=dev, dtype=torch.float32)
+            apg_coef = torch.empty((F_, 2), device=dev, dtype=torch.float32)
+            apg_kw = (float(apg_momentum), float(apg_eta), float(apg_norm_threshold))
         bank_cache = {}
         refu.skip_dead_tail = True
         den.clear_context_cache()
@@ -268,6 +296,8 @@ class MikuDanceVideoPipeline:
                     ops.free_init_mix(lat, lat, noise0, z, lpf, *fi_ab)
                     sch.set_timesteps(fi_steps[fi])
                     timesteps = [int(t) for t in sch.timesteps]
+                if apg_on:
+                    apg_m.zero_()                                        # the running average starts over with every pass
                 for step_i, t in enumerate(timesteps):
                     noise_sum.zero_()
                     counter.zero_()
@@ -304,15 +334,26 @@ class MikuDanceVideoPipeline:
                         ops.cfg_guidance_rescale(noise_sum, counter, F_, HW, guidance_scale, phi, out=scaled["vscale"])
                     if multistep:
                         z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
-                        ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *sch.multistep_coefficients(t_start + step_i),
-                                               halves=nb, variance_noise=z, **scaled)
+                        co = sch.multistep_coefficients(t_start + step_i)
+                        if apg_on:                                           # the same statistics on every rank: same buffers, same arithmetic
+                            ops.cfg_apg_prepare(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, co[0], co[1], *apg_kw)
+                            ops.cfg_multistep_step_apg(lat, noise_sum, counter, history, apg_m, apg_coef, F_, HW, guidance_scale, *co,
+                                                       variance_noise=z)
+                        else:
+                            ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *co, halves=nb, variance_noise=z,
+                                                   **scaled)
                     else:
                         a_t, a_prev = sch.step_coefficients(t)
                         z = None
                         if eta > 0:
                             z = self._draw_noise(latents, generator)
-                        ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta), variance_noise=z,
-                                          **scaled)
+                        if apg_on:
+                            ops.cfg_apg_prepare(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, math.sqrt(a_t), math.sqrt(1.0 - a_t), *apg_kw)
+                            ops.cfg_ddim_step_apg(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, guidance_scale, a_t, a_prev, eta=float(eta),
+                                                  variance_noise=z)
+                        else:
+                            ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta),
+                                              variance_noise=z, **scaled)
                     if callback is not None and step_i % callback_steps == 0:
                         callback(step_i, t, self._latents_out(lat, latents))
         finally:
@@ -327,6 +368,20 @@ class MikuDanceVideoPipeline:
     def _check_fuse(context_fuse):
         if context_fuse not in ("flat", "pyramid"):
             raise ValueError(f"context_fuse must be 'flat' or 'pyramid', got {context_fuse!r}")
+
+    @staticmethod
+    def _check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale):
+        """The refusals of the apg* keywords (the values are checked whether or not apg is on, like guidance_rescale without CFG)."""
+        e, r, b = float(apg_eta), float(apg_norm_threshold), float(apg_momentum)
+        if not (math.isfinite(e) and 0.0 <= e <= 1.0):
+            raise ValueError(f"apg_eta must be a finite number in [0, 1], got {apg_eta}")
+        if not (math.isfinite(r) and r >= 0.0):
+            raise ValueError(f"apg_norm_threshold must be a finite number >= 0, got {apg_norm_threshold}")
+        if not (math.isfinite(b) and -1.0 < b < 1.0):
+            raise ValueError(f"apg_momentum must be a finite number in (-1, 1), got {apg_momentum}")
+        if apg and float(guidance_rescale) > 0.0:
+            raise ValueError("apg=True cannot be combined with guidance_rescale > 0: the rescale would need a second statistics pass over "
+                             "APG's guided output")
 
     @staticmethod
     def _check_strength(strength, has_init, num_inference_steps):
@@ -505,7 +560,7 @@ class MikuDanceVideoPipeline:
                  callback_steps: Optional[int] = 1, context_schedule="uniform", context_frames=None, context_stride=1,
                  context_overlap=8, context_batch_size=1, interpolation_factor=1, guidance_rescale: float = 0.0, video=None, strength: float = 1.0,
                  context_fuse="flat", free_init_iters=1, free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25,
-                 free_init_temporal_stop=0.25, free_init_fast=False, **kwargs):
+                 free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -524,6 +579,9 @@ class MikuDanceVideoPipeline:
                      free_init_spatial_stop=free_init_spatial_stop, free_init_temporal_stop=free_init_temporal_stop, free_init_fast=free_init_fast)
         free_init.check_arguments(free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
                                   video is not None, (video_length, (height or 768) // 8, (width or 768) // 8))
+        # apg*: adaptive projected guidance (denoise()); checked here too, before anything runs
+        self._check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale)
+        apg_kw = dict(apg=apg, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum)
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -558,7 +616,7 @@ class MikuDanceVideoPipeline:
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
                                context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
                                guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength,
-                               context_fuse=context_fuse, **fi_kw)
+                               context_fuse=context_fuse, **fi_kw, **apg_kw)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)
