@@ -276,6 +276,23 @@ int md_cfg_multistep_step_apg(void* latents, const void* noise_sum, const void* 
                               const void* momentum_buf, const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_s,
                               float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
 
+/* md_cfg_ddim_step / md_cfg_ddim_step_eta and md_cfg_multistep_step with perturbed-attention guidance (PAG; Ahn et al., "Self-Rectifying
+ * Diffusion Sampling with Perturbed-Attention Guidance", arXiv 2403.17377; diffusers PAGMixin / AnimateDiffPAGPipeline), applied to the
+ * window-accumulated planes between src/pipelines/pipeline_mikudance.py:670-674 (CFG) and :678 (scheduler.step):
+ *   v = v_plain + pag_scale inv (sum_c - sum_p)
+ * v_plain and inv exactly as the plain entries form them (halves == 2: inv = 1 / counter, v_plain = u + guidance (c - u), so this is diffusers'
+ * u + g (c - u) + s (c - p); halves == 1: inv = 1 and v_plain the window SUM, so it is c + s (c - p) on the sums), sum_c the conditional plane
+ * of noise_sum (plane halves - 1) and sum_p = perturbed_sum [Ftot][HW][4] fp32, the prediction of the conditional evaluation whose selected
+ * self-attention maps are the identity, accumulated over the windows like the other planes.  pag_scale == 0 gives the bits of the plain
+ * entry where the planes are finite (0 * Inf is NaN).  halves 1 or 2; perturbed_sum not NULL, pag_scale finite and >= 0; other arguments as
+ * the plain entries.  Alignment: the DDIM entry accesses single elements (latents / variance_noise 2-byte, noise_sum / counter /
+ * perturbed_sum 4-byte); the multistep entry as md_cfg_multistep_step, perturbed_sum 16-byte.  MD_ERR_ARG otherwise, with nothing launched. */
+int md_cfg_ddim_step_pag(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const void* perturbed_sum, int Ftot,
+                         int HW, int halves, float guidance, float pag_scale, float alpha_t, float alpha_prev, float eta, void* stream);
+int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                              const void* perturbed_sum, int Ftot, int HW, int halves, float guidance, float pag_scale, float alpha_s,
+                              float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
+
 /* Forward noising of a clean latent, the start of video-to-video sampling (`strength` < 1): latents = fp16(a x0 + b latents), computed in
  * fp32, in place, over n fp16 elements.  latents holds the N(0, 1) noise on entry; x0 is the clean VAE latent (already scaled by 0.18215),
  * both packed to the (F, h*w, 4) layout of md_pack_nhwc_f16.  a = sqrt(abar_t), b = sqrt(1 - abar_t) of the first kept timestep, computed by

@@ -297,16 +297,23 @@ class TransformerBlock(_Packed):
             self._kv_cache = (cross.root, ops.gemm(cross.ctx, pk["k2"]), ops.gemm(cross.ctx, pk["v2"], transpose_out=True), {})
         return self._kv_cache[1:]
 
-    def forward(self, h, B, L, cross):
-        """h: [B*L, C] tokens.  Returns tokens."""
+    def forward(self, h, B, L, cross, pag=None):
+        """h: [B*L, C] tokens.  Returns tokens.
+        pag: None, or the collection of TransformerBlocks whose self-attention is perturbed (perturbed-attention guidance, Ahn et al.,
+        arXiv 2403.17377; diffusers PAGIdentitySelfAttnProcessor2_0).  Not None says that ALL rows of h are a perturbed CONDITIONAL evaluation:
+        every row reads the bank (the conditional-only read below, with or without ref_cfg), and in a block that is in `pag` the attention map
+        softmax(q k^T d^-1/2) is the identity, attn1(x) = to_out(to_v(norm1(x) + bank)) + x: no q, no k, no attention launch, V row-major."""
         pk = self.packed()
         C, H = self.dim, self.heads
         D = C // H
+        if pag is not None and (CHAIN is not None or self.ref_mode == "write"):
+            raise ValueError("TransformerBlock: a perturbed evaluation is a call of its own: not one clip-half of a two-queue call, not a bank write")
+        perturbed = pag is not None and any(self is b for b in pag)
         if self.ref_mode == "read" and len(self.bank) == 1 and not (self.ref_cfg and CHAIN == 0):
             bank = self.bank[0]
             brows = bank.shape[0] * bank.shape[1] if bank.dim() == 3 else bank.shape[0]
             M = h.shape[0]
-            if self.ref_cfg and CHAIN == 1:
+            if pag is not None or (self.ref_cfg and CHAIN == 1):
                 # the conditional half on its own: every row reads the bank (the conditional frames' part of a literal 2f-frame bank)
                 begin, b2 = 0, bank.reshape(-1, C)
                 if brows == 2 * M:
@@ -323,19 +330,22 @@ class TransformerBlock(_Packed):
                 begin, b2 = 0, bank.reshape(-1, C)
                 assert b2.shape[0] == M
             n, kv = ops.layernorm(h, pk["n1w"], pk["n1b"], add=b2.contiguous(), add_mode=1, add_row_begin=begin)
-            q = ops.gemm(n, pk["q1"])
-            k = ops.gemm(kv, pk["k1"])
-            vt = ops.gemm(kv, pk["v1"], transpose_out=True)
+            if not perturbed:
+                q = ops.gemm(n, pk["q1"])
+                k = ops.gemm(kv, pk["k1"])
+                vt = ops.gemm(kv, pk["v1"], transpose_out=True)
         else:
-            n = ops.layernorm(h, pk["n1w"], pk["n1b"])
+            n = kv = ops.layernorm(h, pk["n1w"], pk["n1b"])
             if self.ref_mode == "write":
                 self.bank.append(n.view(B, L, C))
                 if self.stop_after_bank:
                     return h
-            qk = ops.gemm(n, pk["qk1"])
-            q, k = qk[:, :C], qk[:, C:]
-            vt = ops.gemm(n, pk["v1"], transpose_out=True)
-        a = ops.attention(q, k, vt, B, H, D, L, L)
+            if not perturbed:
+                qk = ops.gemm(n, pk["qk1"])
+                q, k = qk[:, :C], qk[:, C:]
+                vt = ops.gemm(n, pk["v1"], transpose_out=True)
+        # identity attention map: every query row takes its own V row
+        a = ops.gemm(kv, pk["v1"]) if perturbed else ops.attention(q, k, vt, B, H, D, L, L)
         kv2 = self.context_kv(cross)
         zf = min(cross.zero_frames, B) if ZERO_CONTEXT_SKIP else 0
         if zf:
@@ -375,12 +385,13 @@ class SpatialTransformer(_Packed):
                     pi=packing.conv1x1_weight(self.proj_in.weight, dev), pib=packing.vec(self.proj_in.bias, dev),
                     po=packing.conv1x1_weight(self.proj_out.weight, dev), pob=packing.vec(self.proj_out.bias, dev))
 
-    def forward(self, x, cross, out=None):
+    def forward(self, x, cross, out=None, pag=None):
+        """pag: handed on to the block (TransformerBlock.forward); None everywhere but in a perturbed evaluation."""
         pk = self.packed()
         B, Hh, Ww, C = x.shape
         blk = self.transformer_blocks[0]
         h = gn_linear(x, pk["nw"], pk["nb"], 1e-6, pk["pi"], pk["pib"])
-        h = blk(h, B, Hh * Ww, cross)
+        h = blk(h, B, Hh * Ww, cross, pag=pag)
         if blk.ref_mode == "write" and blk.stop_after_bank:
             return x
         if out is not None:

@@ -193,18 +193,35 @@ __device__ __forceinline__ T apg_v(const T* __restrict__ ns, const float* __rest
   return c - gs * (S * mom[i] - K * dc);
 }
 
-// What a step entry adds to the plain one: nothing, the guidance-rescale factor (*_scaled) or APG's momentum buffer and per-frame
-// coefficients (*_apg).
+// PAG in the step kernels (perturbed-attention guidance, the *_pag entries; Ahn et al., arXiv 2403.17377, diffusers PAGMixin): the guided v
+// gains the step away from a second conditional prediction p, made with the self-attention map of a few blocks replaced by the identity:
+//   v = guided_v + s (c - p)  =  guided_v + s inv (sum_c - sum_p)
+// inv as guided_v has it (1 / cnt under CFG, 1 without: the window SUM), sum_c the conditional plane of ns (plane halves - 1), sum_p the
+// perturbed plane `pp`, accumulated like the others.  s == 0 adds a zero: the bits of guided_v, for finite planes.  T as in guided_v.
+template <typename T>
+__device__ __forceinline__ T pag_v(const T* __restrict__ ns, const T* __restrict__ pp, const float* __restrict__ counter, long i, long total, int fr,
+                                   int halves, float guidance, float pag_scale) {
+  const T v = guided_v(ns, counter, i, total, fr, halves, guidance);
+  const float inv = halves == 2 ? 1.f / counter[fr] : 1.f;
+  const T d = ns[(halves == 2 ? total : 0) + i] - pp[i];
+  return v + (pag_scale * inv) * d;
+}
+
+// What a step entry adds to the plain one: nothing, the guidance-rescale factor (*_scaled), APG's momentum buffer and per-frame
+// coefficients (*_apg) or PAG's perturbed plane and scale (*_pag).
 struct StepExtra {
   const float* vscale = nullptr;
   const float* mom = nullptr;
   const float* coef = nullptr;
-  bool scaled = false, apg = false;
+  const float* pag_sum = nullptr;
+  float pag_scale = 0.f;
+  bool scaled = false, apg = false, pag = false;
 };
 
 // The argument rules all step entry points share.  Alignment and a kernel's own buffers are its launcher's business.
 // noise_coeff: the factor of variance_noise (eta / c_z).  ex.scaled: the *_scaled entries, which need CFG and the factor; ex.apg: the
-// *_apg entries, which need CFG, the momentum buffer and the coefficients.
+// *_apg entries, which need CFG, the momentum buffer and the coefficients; ex.pag: the *_pag entries, which need the perturbed plane and a
+// finite scale >= 0, with or without CFG.
 static int cfg_step_check(const char* who, const void* latents, const void* noise_sum, const void* counter, const void* variance_noise,
                           const StepExtra& ex, int Ftot, int HW, int halves, float noise_coeff, std::initializer_list<float> coeffs) {
   MD_CHECK_ARG(Ftot > 0 && HW > 0 && (halves == 1 || halves == 2), "%s: bad arguments", who);
@@ -212,12 +229,14 @@ static int cfg_step_check(const char* who, const void* latents, const void* nois
   MD_CHECK_ARG(!ex.scaled || (halves == 2 && ex.vscale && ((uintptr_t)ex.vscale % 4) == 0),
                "%s: guidance rescale needs halves == 2 and a 4-byte aligned vscale", who);
   MD_CHECK_ARG(!ex.apg || (halves == 2 && ex.mom && ex.coef), "%s: APG needs halves == 2, the momentum buffer and coef", who);
+  MD_CHECK_ARG(!ex.pag || (ex.pag_sum && __builtin_isfinite(ex.pag_scale) && ex.pag_scale >= 0.f),
+               "%s: PAG needs the perturbed plane and a finite pag_scale >= 0", who);
   for (const float c : coeffs) MD_CHECK_ARG(__builtin_isfinite(c), "%s: non-finite coefficient", who);
   MD_CHECK_ARG(noise_coeff == 0.f || variance_noise, "%s: a non-zero noise coefficient needs variance_noise", who);
   return MD_OK;
 }
 
-// The alignment md_cfg_multistep_step asks for (one pixel = 4 channels per access), which the *_apg entries ask for as well.
+// The alignment md_cfg_multistep_step asks for (one pixel = 4 channels per access), which the *_apg and *_pag entries ask for as well.
 static int cfg_pixel_alignment_check(const char* who, const void* latents, const void* noise_sum, const void* history,
                                      const void* variance_noise, const StepExtra& ex) {
   MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
@@ -225,11 +244,12 @@ static int cfg_pixel_alignment_check(const char* who, const void* latents, const
                "%s: latents / variance_noise need 8-byte, noise_sum / history 16-byte alignment", who);
   MD_CHECK_ARG(!ex.apg || (((uintptr_t)ex.mom % 16) == 0 && ((uintptr_t)ex.coef % 4) == 0),
                "%s: the momentum buffer needs 16-byte, coef 4-byte alignment", who);
+  MD_CHECK_ARG(!ex.pag || ((uintptr_t)ex.pag_sum % 16) == 0, "%s: the perturbed plane needs 16-byte alignment", who);
   return MD_OK;
 }
 
 // ---- CFG combine + DDIM v-prediction step -------------------------------------------------------------------------------
-//   v   = guided_v                                                                   (the *_apg entry: apg_v)
+//   v   = guided_v                                                                   (the *_apg entry: apg_v; *_pag: pag_v)
 //   x0  = sqrt(a_t) x - sqrt(1-a_t) v ;  eps = sqrt(a_t) v + sqrt(1-a_t) x
 //   x'  = sqrt(a_prev) x0 + sqrt(1-a_prev) eps                                      DDIMScheduler.step
 // latents: [Ftot][HW][4] fp16, updated in place (fp32 arithmetic, one rounding).
@@ -268,6 +288,20 @@ __global__ void cfg_ddim_apg_kernel(half_t* __restrict__ lat, const float* __res
   }
 }
 
+// The PAG flavour: pag_sum [Ftot][HW][4] fp32, the perturbed plane; halves 1 or 2.
+__global__ void cfg_ddim_pag_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
+                                    const half_t* __restrict__ variance_noise, int Ftot, int HW4, int halves, float guidance, float sa, float sb,
+                                    float sap, float sdir, float sigma, const float* __restrict__ pag_sum, float pag_scale) {
+  const long total = (long)Ftot * HW4;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    float v = pag_v(noise_sum, pag_sum, counter, idx, total, (int)(idx / HW4), halves, guidance, pag_scale);
+    // v goes into the update as a finished value: without this the compiler is free to fuse ddim_update's products with other sums than in
+    // cfg_ddim_kernel (it did: sb x + sa v instead of sa v + sb x), and pag_scale == 0 would not be the plain kernel's bits
+    asm volatile("" : "+v"(v));
+    ddim_update(lat, variance_noise, idx, (float)lat[idx], v, sa, sb, sap, sdir, sigma);
+  }
+}
+
 static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW, int halves,
                            float guidance, float alpha_t, float alpha_prev, float eta, void* stream, const StepExtra& ex, const char* who) {
   if (cfg_step_check(who, latents, noise_sum, counter, variance_noise, ex, Ftot, HW, halves, eta, {guidance, alpha_t, alpha_prev, eta}))
@@ -277,6 +311,10 @@ static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* cou
     if (cfg_pixel_alignment_check(who, latents, noise_sum, nullptr, variance_noise, ex)) return MD_ERR_ARG;
     MD_CHECK_ARG(alpha_t >= 0.f && alpha_t < 1.f, "%s: APG divides by sqrt(1 - alpha_t): alpha_t must be in [0, 1)", who);
   }
+  // the PAG kernel accesses single elements, like the plain one: natural alignment is all it needs
+  MD_CHECK_ARG(!ex.pag || (((uintptr_t)latents % 2) == 0 && ((uintptr_t)variance_noise % 2) == 0 && ((uintptr_t)noise_sum % 4) == 0 &&
+                           ((uintptr_t)counter % 4) == 0 && ((uintptr_t)ex.pag_sum % 4) == 0),
+               "%s: latents / variance_noise need 2-byte, noise_sum / counter / the perturbed plane 4-byte alignment", who);
   // diffusers DDIMScheduler._get_variance: sigma_t^2 = eta^2 (1 - a_prev) / (1 - a_t) (1 - a_t / a_prev); a_t == 1 never occurs (t >= 0 of a
   // zero-terminal-SNR table has a_t < 1)
   const float var = eta > 0.f ? (1.f - alpha_prev) / (1.f - alpha_t) * (1.f - alpha_t / alpha_prev) : 0.f;
@@ -289,6 +327,9 @@ static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* cou
   if (ex.apg)
     hipLaunchKernelGGL(cfg_ddim_apg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
                        (const float*)counter, z, Ftot, HW * 4, guidance, sa, sb, sap, sdir, sigma, ex.mom, ex.coef, (guidance - 1.f) / sb);
+  else if (ex.pag)
+    hipLaunchKernelGGL(cfg_ddim_pag_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+                       (const float*)counter, z, Ftot, HW * 4, halves, guidance, sa, sb, sap, sdir, sigma, ex.pag_sum, ex.pag_scale);
   else
     hipLaunchKernelGGL(ex.scaled ? cfg_ddim_kernel<true> : cfg_ddim_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents,
                        (const float*)noise_sum, (const float*)counter, z, Ftot, HW * 4, halves, guidance, sa, sb, sap, sdir, sigma, ex.vscale);
@@ -308,6 +349,14 @@ static StepExtra step_apg(const void* momentum_buf, const float* coef) {
   ex.apg = true;
   ex.mom = (const float*)momentum_buf;
   ex.coef = coef;
+  return ex;
+}
+
+static StepExtra step_pag(const void* perturbed_sum, float pag_scale) {
+  StepExtra ex;
+  ex.pag = true;
+  ex.pag_sum = (const float*)perturbed_sum;
+  ex.pag_scale = pag_scale;
   return ex;
 }
 
@@ -336,8 +385,15 @@ extern "C" int md_cfg_ddim_step_apg(void* latents, const void* noise_sum, const 
                          step_apg(momentum_buf, coef), "md_cfg_ddim_step_apg");
 }
 
+extern "C" int md_cfg_ddim_step_pag(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const void* perturbed_sum,
+                                    int Ftot, int HW, int halves, float guidance, float pag_scale, float alpha_t, float alpha_prev, float eta,
+                                    void* stream) {
+  return cfg_ddim_launch(latents, noise_sum, counter, variance_noise, Ftot, HW, halves, guidance, alpha_t, alpha_prev, eta, stream,
+                         step_pag(perturbed_sum, pag_scale), "md_cfg_ddim_step_pag");
+}
+
 // ---- CFG combine + DPM-Solver++ multistep step (orders 1 / 2, ODE or SDE; Lu et al., arXiv 2211.01095) ------------------
-//   v   = guided_v                                 (the *_apg entry: apg_v)
+//   v   = guided_v                                 (the *_apg entry: apg_v; *_pag: pag_v)
 //   m0  = alpha_s x - sigma_s v                    data prediction (x0) of this step
 //   x'  = c_x x + c_m0 m0 + c_m1 m1 + c_z z        m1 = the previous step's m0 (history), z = variance noise
 // The coefficients are host scalars (DPMSolverMultistepScheduler.multistep_coefficients): every solver variant is this one update.
@@ -389,6 +445,23 @@ __global__ void cfg_multistep_apg_kernel(half_t* __restrict__ lat, const float* 
   }
 }
 
+// The PAG flavour: pag_sum [Ftot][HW][4] fp32, the perturbed plane; halves 1 or 2.
+__global__ void cfg_multistep_pag_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
+                                         float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, int halves,
+                                         float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
+                                         const float* __restrict__ pag_sum, float pag_scale) {
+  const long total = (long)Ftot * HW;  // pixels
+  const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
+  const floatx4* pp = reinterpret_cast<const floatx4*>(pag_sum);
+  floatx4* hist = reinterpret_cast<floatx4*>(history);
+  half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
+  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    floatx4 v = pag_v(ns, pp, counter, p, total, (int)(p / HW), halves, guidance, pag_scale);
+    asm volatile("" : "+v"(v));  // as in cfg_ddim_pag_kernel: the update sees a finished v, like the plain kernel's
+    multistep_update(lat4, hist, variance_noise, p, __builtin_convertvector(lat4[p], floatx4), v, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z);
+  }
+}
+
 static int cfg_multistep_launch(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise, int Ftot, int HW,
                                 int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream,
                                 const StepExtra& ex, const char* who) {
@@ -405,6 +478,10 @@ static int cfg_multistep_launch(void* latents, const void* noise_sum, const void
     hipLaunchKernelGGL(cfg_multistep_apg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
                        (const float*)counter, (float*)history, z, Ftot, HW, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, ex.mom, ex.coef,
                        (guidance - 1.f) / sigma_s);
+  else if (ex.pag)
+    hipLaunchKernelGGL(cfg_multistep_pag_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
+                       (const float*)counter, (float*)history, z, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, ex.pag_sum,
+                       ex.pag_scale);
   else
     hipLaunchKernelGGL(ex.scaled ? cfg_multistep_kernel<true> : cfg_multistep_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
                        (half_t*)latents, (const float*)noise_sum, (const float*)counter, (float*)history, z, Ftot, HW, halves, guidance, alpha_s,
@@ -432,6 +509,13 @@ extern "C" int md_cfg_multistep_step_apg(void* latents, const void* noise_sum, c
                                          float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream) {
   return cfg_multistep_launch(latents, noise_sum, counter, history, variance_noise, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
                               stream, step_apg(momentum_buf, coef), "md_cfg_multistep_step_apg");
+}
+
+extern "C" int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                                         const void* perturbed_sum, int Ftot, int HW, int halves, float guidance, float pag_scale, float alpha_s,
+                                         float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream) {
+  return cfg_multistep_launch(latents, noise_sum, counter, history, variance_noise, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
+                              stream, step_pag(perturbed_sum, pag_scale), "md_cfg_multistep_step_pag");
 }
 
 // ---- guidance rescale factor (Lin et al., arXiv 2305.08891 section 3.4; diffusers rescale_noise_cfg) ----------------------------------

@@ -20,6 +20,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      (an addition: FreeInit noise re-initialisation, arXiv 2312.07537; default 1 pass = off)
     pipe(..., apg=--apg, apg_eta=, apg_norm_threshold=, apg_momentum=)                             (an addition: adaptive projected guidance,
                      arXiv 2410.02416, per frame on the data prediction; default off)
+    pipe(..., pag_scale=--pag_scale, pag_adaptive_scale=--pag_adaptive_scale, pag_applied_layers=--pag_layers)
+                     (an addition: perturbed-attention guidance, arXiv 2403.17377; default 0.0 = off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -102,6 +104,15 @@ def parse_args(argv=None):
                         help="(addition) APG: cap on the per-frame norm of the guidance update, >= 0; 0 = no cap")
     parser.add_argument("--apg_momentum", type=float, default=0.0,
                         help="(addition) APG: momentum of the update's running average over steps, in (-1, 1); the paper uses a negative value")
+    parser.add_argument("--pag_scale", type=float, default=0.0,
+                        help="(addition) perturbed-attention guidance (arXiv 2403.17377, diffusers PAGMixin): the weight of the step away from a "
+                             "second conditional prediction made with the self-attention map of --pag_layers replaced by the identity, >= 0; "
+                             "0.0 = off, 3.0 the paper's value.  Works with every --sampler and without --cfg; not with --guidance_rescale or --apg")
+    parser.add_argument("--pag_adaptive_scale", type=float, default=0.0,
+                        help="(addition) PAG: decay of the scale per timestep below 1000 (diffusers pag_adaptive_scale), >= 0; 0.0 = none")
+    parser.add_argument("--pag_layers", default="mid",
+                        help="(addition) PAG: comma-separated attention blocks of the denoising UNet, e.g. mid or "
+                             "down_blocks.2,up_blocks.1.attentions.0")
     args = parser.parse_args(argv)
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
@@ -198,7 +209,9 @@ def main(argv=None):
                context_frames=args.context_frames, context_overlap=args.context_overlap, free_init_iters=args.free_init_iters,
                free_init_filter=args.free_init_filter, free_init_order=args.free_init_order, free_init_spatial_stop=args.free_init_spatial_stop,
                free_init_temporal_stop=args.free_init_temporal_stop, free_init_fast=args.free_init_fast,
-               apg=args.apg, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum)
+               apg=args.apg, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum,
+               pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale,
+               pag_applied_layers=tuple(n.strip() for n in args.pag_layers.split(",") if n.strip()))
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

@@ -433,6 +433,33 @@ def cfg_multistep_step_apg(latents, noise_sum, counter, history, momentum_buf, c
               float(alpha_s), float(sigma_s), float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
 
 
+def _pag_plane(perturbed_sum, ftot, hw):
+    _chk(perturbed_sum, "perturbed_sum", torch.float32)
+    assert perturbed_sum.is_contiguous() and perturbed_sum.numel() == ftot * hw * 4
+    return perturbed_sum.data_ptr()
+
+
+def cfg_ddim_step_pag(latents, noise_sum, counter, perturbed_sum, ftot, hw, guidance, pag_scale, alpha_t, alpha_prev, halves=2, eta=0.0,
+                      variance_noise=None):
+    """cfg_ddim_step with perturbed-attention guidance (md_cfg_ddim_step_pag; arXiv 2403.17377): v + pag_scale inv (sum_c - perturbed_sum) in place
+    of the guided v, with or without CFG.  `perturbed_sum`: fp32 (ftot, hw, 4), the perturbed evaluation accumulated over the windows like one
+    plane of `noise_sum` (halves planes).  eta / variance_noise as in cfg_ddim_step."""
+    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, eta, variance_noise, None)
+    _lib.call("md_cfg_ddim_step_pag", *bufs, z, _pag_plane(perturbed_sum, ftot, hw), ftot, hw, halves, float(guidance), float(pag_scale),
+              float(alpha_t), float(alpha_prev), float(eta), _st())
+
+
+def cfg_multistep_step_pag(latents, noise_sum, counter, history, perturbed_sum, ftot, hw, guidance, pag_scale, alpha_s, sigma_s, c_x, c_m0, c_m1,
+                           c_z, halves=2, variance_noise=None):
+    """cfg_multistep_step with perturbed-attention guidance (md_cfg_multistep_step_pag): `perturbed_sum` and pag_scale as in cfg_ddim_step_pag;
+    `history` receives alpha_s x - sigma_s v of the PAG-guided v.  The rest as in cfg_multistep_step."""
+    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, c_z, variance_noise, None)
+    _chk(history, "history", torch.float32)
+    assert history.is_contiguous() and history.numel() == ftot * hw * 4
+    _lib.call("md_cfg_multistep_step_pag", *bufs, history.data_ptr(), z, _pag_plane(perturbed_sum, ftot, hw), ftot, hw, halves, float(guidance),
+              float(pag_scale), float(alpha_s), float(sigma_s), float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
+
+
 _fi_ws = {}
 
 

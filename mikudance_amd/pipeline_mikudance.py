@@ -132,7 +132,8 @@ class MikuDanceVideoPipeline:
                 context_frames=None, context_stride=1, context_overlap=8, callback=None, callback_steps=1, eta=0.0, generator=None,
                 window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0, context_fuse="flat", free_init_iters=1,
                 free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25, free_init_temporal_stop=0.25,
-                free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0):
+                free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
+                pag_applied_layers=("mid",)):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -202,6 +203,26 @@ class MikuDanceVideoPipeline:
         apg_norm_threshold  finite, >= 0: the cap on the per-frame norm of the update; 0 = no cap
         apg_momentum        finite, in (-1, 1): beta of the running average over steps (the paper uses a negative value); with
                             apg_eta = 1, apg_norm_threshold = 0, apg_momentum = 0 the result is u + g (c - u) up to rounding
+        pag_scale           perturbed-attention guidance (Ahn et al., arXiv 2403.17377; diffusers PAGMixin / AnimateDiffPAGPipeline), finite, >= 0.
+                            Every step and every window the denoising UNet is evaluated once more on the window's conditional frames (CLIP
+                            tokens, every row reads the reference bank) with the self-attention map of the blocks pag_applied_layers selects
+                            replaced by the identity, attn1(x) = to_out(to_v(norm1(x) + bank)) + x (no q, no k, no attention launch there;
+                            cross-attention, feed-forward and the motion modules are never perturbed; the reference UNet and the bank cache
+                            do not depend on it).  That prediction p is accumulated over the windows into one more plane of the fp32
+                            accumulator, with the same window weights (under window_parallel the rank that owns a window evaluates both
+                            of its branches and the one all_reduce carries the plane; no new collective), and the step (md_cfg_*_step_pag)
+                            runs on v + s_t (c - p): under CFG diffusers' u + g (c - u) + s (c - p), without CFG c + s (c - p) on what the
+                            loop hands the scheduler (the window sum for "flat", see context_fuse).  Works with both samplers, eta / SDE
+                            noise, init_latents / strength, every window schedule and fuse mode, FreeInit (every pass) and window_parallel;
+                            not with guidance_rescale > 0 and not with apg=True (each would need its statistics taken over the PAG-guided
+                            v).  Costs one conditional clip-half per window and step, less the self-attention of the selected blocks.
+                            0.0 (the default) is bitwise the loop without the keywords, makes no new operator call and allocates no buffer
+        pag_adaptive_scale  finite, >= 0: diffusers' _get_pag_scale, s_t = max(pag_scale - pag_adaptive_scale (1000 - t), 0) per step on the
+                            host; at a step with s_t == 0 the perturbed evaluation is skipped and the plain step entry runs.  0.0: no decay
+        pag_applied_layers  names of the denoising UNet's attention blocks, checkpoint-key prefixes: "mid_block" (alias "mid"),
+                            "down_blocks.I", "up_blocks.I", "down_blocks.I.attentions.J", "up_blocks.I.attentions.J"; a block is selected
+                            when its key prefix equals a name or starts with name + ".".  An empty sequence (with pag_scale > 0) and a
+                            name that selects no block raise ValueError
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         self._check_fuse(context_fuse)
@@ -213,6 +234,7 @@ class MikuDanceVideoPipeline:
             raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale}")
         self._check_strength(strength, init_latents is not None, num_inference_steps)
         self._check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale)
+        pag_s, pag_a, pag_names = self._check_pag(pag_scale, pag_adaptive_scale, pag_applied_layers, guidance_rescale, apg)
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         dev = latents.device
@@ -221,6 +243,9 @@ class MikuDanceVideoPipeline:
         do_cfg = guidance_scale > 1.0
         nb = 2 if do_cfg else 1
         den, refu, sch = self.denoising_unet, self.reference_unet, self.scheduler
+        # PAG: the selected blocks (a name that selects none raises here, before anything runs); off: nothing below changes
+        pag_on = pag_s > 0.0
+        pag_sel = den.pag_blocks(pag_names) if pag_on else None
         from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
         multistep = isinstance(sch, DPMSolverMultistepScheduler)
         if not multistep and not isinstance(sch, DDIMScheduler):
@@ -253,8 +278,13 @@ class MikuDanceVideoPipeline:
             noise0 = lat.clone()
             lpf = free_init.freq_filter(F_, hh, ww, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop).to(dev)
             fi_ab = sch.noise_coefficients(sch.num_train_timesteps - 1)
-        noise_sum = torch.zeros((nb, F_, HW, 4), device=dev, dtype=torch.float32)
+        # PAG: the perturbed prediction is one more plane of the accumulator (the all_reduce carries it), summed by the same kernels at
+        # halves = 1 against a scratch counter (they add to their counter: the real one would count every window twice)
+        noise_sum = torch.zeros((nb + 1 if pag_on else nb, F_, HW, 4), device=dev, dtype=torch.float32)
         counter = torch.zeros((F_,), device=dev, dtype=torch.float32)
+        ns_main, ns_pag, pag_counter = noise_sum, None, None
+        if pag_on:
+            ns_main, ns_pag, pag_counter = noise_sum[:nb], noise_sum[nb:], torch.zeros((F_,), device=dev, dtype=torch.float32)
         windows = [list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
                                                                             context_stride, context_overlap)]
         mm_len = getattr(den, "temporal_position_encoding_max_len", None)
@@ -301,6 +331,7 @@ class MikuDanceVideoPipeline:
                 for step_i, t in enumerate(timesteps):
                     noise_sum.zero_()
                     counter.zero_()
+                    s_t = self._pag_scale_at(pag_s, pag_a, t) if pag_on else 0.0      # a pure function of t: no sync
                     for wi, win in enumerate(windows):
                         if window_parallel is not None and not window_parallel.mine(wi):
                             continue                                         # another rank's window (its share arrives in the all_reduce)
@@ -323,9 +354,17 @@ class MikuDanceVideoPipeline:
                         pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
                                                 two_queues=self.two_queues)
                         if wts_dev is None:
-                            ops.window_accumulate(pred, noise_sum, counter, win_dev[wi], f, F_, HW, halves=nb)
+                            ops.window_accumulate(pred, ns_main, counter, win_dev[wi], f, F_, HW, halves=nb)
                         else:
-                            ops.window_accumulate_weighted(pred, noise_sum, counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=nb)
+                            ops.window_accumulate_weighted(pred, ns_main, counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=nb)
+                        if s_t > 0.0:
+                            # ---- PAG: the conditional frames once more (the banks are still in place), selected self-attention maps = identity
+                            pred = den.forward_nhwc(x[(nb - 1) * f:], 1, f, torch.full((1,), float(t)), cross.rows(f, 2 * f) if do_cfg else cross,
+                                                    pag=pag_sel)
+                            if wts_dev is None:
+                                ops.window_accumulate(pred, ns_pag, pag_counter, win_dev[wi], f, F_, HW, halves=1)
+                            else:
+                                ops.window_accumulate_weighted(pred, ns_pag, pag_counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=1)
                         reader.clear()
                         writer.clear()
                     if window_parallel is not None:
@@ -339,8 +378,11 @@ class MikuDanceVideoPipeline:
                             ops.cfg_apg_prepare(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, co[0], co[1], *apg_kw)
                             ops.cfg_multistep_step_apg(lat, noise_sum, counter, history, apg_m, apg_coef, F_, HW, guidance_scale, *co,
                                                        variance_noise=z)
+                        elif s_t > 0.0:
+                            ops.cfg_multistep_step_pag(lat, ns_main, counter, history, ns_pag[0], F_, HW, guidance_scale, s_t, *co, halves=nb,
+                                                       variance_noise=z)
                         else:
-                            ops.cfg_multistep_step(lat, noise_sum, counter, history, F_, HW, guidance_scale, *co, halves=nb, variance_noise=z,
+                            ops.cfg_multistep_step(lat, ns_main, counter, history, F_, HW, guidance_scale, *co, halves=nb, variance_noise=z,
                                                    **scaled)
                     else:
                         a_t, a_prev = sch.step_coefficients(t)
@@ -351,8 +393,11 @@ class MikuDanceVideoPipeline:
                             ops.cfg_apg_prepare(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, math.sqrt(a_t), math.sqrt(1.0 - a_t), *apg_kw)
                             ops.cfg_ddim_step_apg(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, guidance_scale, a_t, a_prev, eta=float(eta),
                                                   variance_noise=z)
+                        elif s_t > 0.0:
+                            ops.cfg_ddim_step_pag(lat, ns_main, counter, ns_pag[0], F_, HW, guidance_scale, s_t, a_t, a_prev, halves=nb,
+                                                  eta=float(eta), variance_noise=z)
                         else:
-                            ops.cfg_ddim_step(lat, noise_sum, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta),
+                            ops.cfg_ddim_step(lat, ns_main, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta),
                                               variance_noise=z, **scaled)
                     if callback is not None and step_i % callback_steps == 0:
                         callback(step_i, t, self._latents_out(lat, latents))
@@ -382,6 +427,31 @@ class MikuDanceVideoPipeline:
         if apg and float(guidance_rescale) > 0.0:
             raise ValueError("apg=True cannot be combined with guidance_rescale > 0: the rescale would need a second statistics pass over "
                              "APG's guided output")
+
+    @staticmethod
+    def _check_pag(pag_scale, pag_adaptive_scale, pag_applied_layers, guidance_rescale, apg):
+        """The refusals of the pag_* keywords that need no model -> (pag_scale, pag_adaptive_scale, layer names).  The values and the form of
+        the names are checked whether or not PAG is on; which blocks the names select is the UNet's business (pag_blocks)."""
+        from .unet_3d_mix import check_pag_layer_names
+        s, a = float(pag_scale), float(pag_adaptive_scale)
+        if not (math.isfinite(s) and s >= 0.0):
+            raise ValueError(f"pag_scale must be a finite number >= 0, got {pag_scale}")
+        if not (math.isfinite(a) and a >= 0.0):
+            raise ValueError(f"pag_adaptive_scale must be a finite number >= 0, got {pag_adaptive_scale}")
+        names = check_pag_layer_names(pag_applied_layers)
+        if s > 0.0 and not names:
+            raise ValueError("pag_applied_layers is empty: perturbed-attention guidance needs at least one attention block")
+        if s > 0.0 and float(guidance_rescale) > 0.0:
+            raise ValueError("pag_scale > 0 cannot be combined with guidance_rescale > 0: the rescale would need its statistics taken over the "
+                             "PAG-guided output")
+        if s > 0.0 and apg:
+            raise ValueError("pag_scale > 0 cannot be combined with apg=True: APG's statistics would have to be taken over the PAG-guided output")
+        return s, a, names
+
+    @staticmethod
+    def _pag_scale_at(pag_scale, pag_adaptive_scale, t):
+        """diffusers PAGMixin._get_pag_scale: the scale decays linearly as t falls from 1000 and stops at 0."""
+        return max(pag_scale - pag_adaptive_scale * (1000 - int(t)), 0.0)
 
     @staticmethod
     def _check_strength(strength, has_init, num_inference_steps):
@@ -560,7 +630,8 @@ class MikuDanceVideoPipeline:
                  callback_steps: Optional[int] = 1, context_schedule="uniform", context_frames=None, context_stride=1,
                  context_overlap=8, context_batch_size=1, interpolation_factor=1, guidance_rescale: float = 0.0, video=None, strength: float = 1.0,
                  context_fuse="flat", free_init_iters=1, free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25,
-                 free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, **kwargs):
+                 free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0,
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -582,6 +653,11 @@ class MikuDanceVideoPipeline:
         # apg*: adaptive projected guidance (denoise()); checked here too, before anything runs
         self._check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale)
         apg_kw = dict(apg=apg, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum)
+        # pag_*: perturbed-attention guidance (denoise()); checked here too, the layer names against the UNet's blocks included
+        pag_s, _, pag_names = self._check_pag(pag_scale, pag_adaptive_scale, pag_applied_layers, guidance_rescale, apg)
+        if pag_s > 0.0:
+            self.denoising_unet.pag_blocks(pag_names)
+        pag_kw = dict(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, pag_applied_layers=pag_applied_layers)
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -616,7 +692,7 @@ class MikuDanceVideoPipeline:
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
                                context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
                                guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength,
-                               context_fuse=context_fuse, **fi_kw, **apg_kw)
+                               context_fuse=context_fuse, **fi_kw, **apg_kw, **pag_kw)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)

@@ -6,6 +6,7 @@ API mirror of the reference `UNet3DConditionModel` (src/models/unet_3d_mix.py:34
 Internally frames are folded into the batch and everything runs NHWC fp16 on the HIP kernels.
 """
 import json
+import re
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Optional
@@ -250,6 +251,37 @@ class _UNetBase(_Packed):
                 out += [a.transformer_blocks[0] for a in blk.attentions]
         return out
 
+    def attention_block_prefixes(self):
+        """[(checkpoint-key prefix, TransformerBlock)] of every spatial transformer: "down_blocks.I.attentions.J", "mid_block.attentions.0",
+        "up_blocks.I.attentions.J", in evaluation order."""
+        out = []
+        for name, blks in (("down_blocks", self.down_blocks), ("up_blocks", self.up_blocks)):
+            for i, blk in enumerate(blks):
+                if blk.has_cross_attention:
+                    out += [(f"{name}.{i}.attentions.{j}", a.transformer_blocks[0]) for j, a in enumerate(blk.attentions)]
+        nd = sum(1 for p, _ in out if p.startswith("down_blocks"))
+        mid = [(f"mid_block.attentions.{j}", a.transformer_blocks[0]) for j, a in enumerate(self.mid_block.attentions)]
+        return out[:nd] + mid + out[nd:]
+
+    def pag_blocks(self, applied_layers):
+        """The TransformerBlocks that `pag_applied_layers` selects (perturbed-attention guidance, diffusers PAGMixin.set_pag_applied_layers
+        restricted to the names of this model): "mid_block" (alias "mid"), "down_blocks.I", "up_blocks.I", "down_blocks.I.attentions.J",
+        "up_blocks.I.attentions.J".  A block is selected when its key prefix equals a name or starts with name + ".".  An empty sequence
+        and a name that selects no block raise ValueError."""
+        names = check_pag_layer_names(applied_layers)
+        if not names:
+            raise ValueError("pag_applied_layers is empty: perturbed-attention guidance needs at least one attention block")
+        blocks = self.attention_block_prefixes()
+        picked = []
+        for name in names:
+            key = "mid_block" if name == "mid" else name
+            hit = [b for p, b in blocks if p == key or p.startswith(key + ".")]
+            if not hit:
+                raise ValueError(f"pag_applied_layers: {name!r} selects no attention block of this UNet (its blocks: "
+                                 f"{', '.join(p for p, _ in blocks)})")
+            picked += [b for b in hit if not any(b is q for q in picked)]
+        return tuple(picked)
+
     @property
     def dtype(self):
         return self.conv_in.weight.dtype
@@ -265,6 +297,25 @@ class _UNetBase(_Packed):
         each upsampler then resizes to the spatial size of the skip it is about to meet instead of exactly 2x."""
         m = 2 ** (levels - 1)
         return bool(h % m or w % m)
+
+
+_PAG_NAME = re.compile(r"^(mid|mid_block|(down|up)_blocks\.\d+(\.attentions\.\d+)?)$")
+
+
+def check_pag_layer_names(applied_layers):
+    """pag_applied_layers as a tuple of names of the forms UNet3DConditionModel.pag_blocks documents; anything else raises ValueError.
+    Needs no model: the pipeline calls it before anything runs."""
+    if isinstance(applied_layers, str):
+        applied_layers = (applied_layers,)
+    try:
+        names = tuple(applied_layers)
+    except TypeError:
+        raise ValueError(f"pag_applied_layers must be a sequence of layer names, got {applied_layers!r}") from None
+    for name in names:
+        if not isinstance(name, str) or not _PAG_NAME.match(name):
+            raise ValueError(f"pag_applied_layers: unknown layer name {name!r}; the forms are 'mid_block' (or 'mid'), 'down_blocks.I', "
+                             "'up_blocks.I', 'down_blocks.I.attentions.J', 'up_blocks.I.attentions.J'")
+    return names
 
 
 class UNet3DConditionModel(_UNetBase):
@@ -319,8 +370,12 @@ class UNet3DConditionModel(_UNetBase):
         self._build(in_channels, tuple(block_out_channels), cross_attention_dim, norm_eps, flags, mm_kwargs, with_out=True)
 
     # ------------------------------------------------------------------------------------------ internal NHWC forward
-    def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False):
+    def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None):
         """x: (nb*f, h, w, 64) fp16 (4 latent channels, zero padded); returns pred tokens [(nb*f*h*w), 4].
+        pag: None, or the blocks of pag_blocks(): this call is then the PERTURBED evaluation of perturbed-attention guidance (arXiv 2403.17377), a
+        call of its own beside the main one: nb must be 1, x the conditional frames, cross their context (the main call's context or its
+        rows(f, 2f): the cached K / V projections are shared, nothing of the main call is touched).  Every row reads the bank, and the selected
+        blocks' self-attention map is the identity (TransformerBlock.forward).  Not with two_queues: one clip-half has nothing to run beside.
         halves_identical: the caller GUARANTEES that the two clip-halves of x hold the same latents (classifier-free guidance: the loop of
         src/pipelines/pipeline_mikudance.py:626-633 feeds `torch.cat([latents] * 2)`) -- with equal timesteps, conv_in and the first resnet
         (no attention in front of them: nothing has seen the context or the bank yet) then produce the same tensor for both halves, so
@@ -328,6 +383,8 @@ class UNet3DConditionModel(_UNetBase):
         two_queues (with halves_identical): behind those shared layers the unconditional and the conditional half are independent all the way
         to the output (per-image GroupNorm, per-row attention and LayerNorm, per-clip-half temporal attention: src/models/unet_3d_mix.py:
         418-598, src/models/mutual_mix_attention.py:173-201), and they are evaluated as TWO KERNEL QUEUES (_forward_two_queues)."""
+        if pag is not None and (nb != 1 or two_queues or halves_identical):
+            raise ValueError("forward_nhwc: the perturbed evaluation (pag=) is one clip-half on one queue: nb == 1, no two_queues, no halves_identical")
         pk = self.packed()
         dev = x.device
         _, hh, ww, _ = x.shape
@@ -359,11 +416,11 @@ class UNet3DConditionModel(_UNetBase):
                 first = dst
         else:
             x = ops.conv3x3(x, pk["cin"], c0, bias=pk["cinb"], out=skips.slot(B, hh, ww, c0, dev))
-        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, first))
+        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, first, pag=pag))
 
-    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, first=None, out=None):
+    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, first=None, out=None, pag=None):
         """Everything behind conv_in.  x: conv_in's output (nb*f, h, w, C0), already in its skip slot; `first`: the first resnet's output when
-        the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes, (nb*f, h, w, 4)."""
+        the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes, (nb*f, h, w, 4); `pag`: see forward_nhwc."""
         dev = x.device
         B = x.shape[0]
         for bi, blk in enumerate(self.down_blocks):
@@ -379,14 +436,14 @@ class UNet3DConditionModel(_UNetBase):
                 if not last_op and first is not None and bi == 0 and j == 0:
                     dst = skips.slot(B, H_, W_, r.cout, dev)
                 if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst)
+                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag)
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
             if blk.downsamplers is not None:
                 x = blk.downsamplers[0](x, out=skips.slot(B, (x.shape[1] + 1) // 2, (x.shape[2] + 1) // 2, blk.downsamplers[0].c, dev))
         mb = self.mid_block
         x = mb.resnets[0](x, self._temb(pk, trows, mb.resnets[0]), f * x.shape[1] * x.shape[2], gf)
-        x = mb.attentions[0](x, cross)
+        x = mb.attentions[0](x, cross, pag=pag)
         if mb.motion_modules[0] is not None:
             x = mb.motion_modules[0](x, nb, f)
         x = mb.resnets[1](x, self._temb(pk, trows, mb.resnets[1]), f * x.shape[1] * x.shape[2], gf, out=skips.hidden_slot())
@@ -400,7 +457,7 @@ class UNet3DConditionModel(_UNetBase):
                 dst = skips.hidden_slot() if len(skips) and not (last and blk.upsamplers is not None) else None
                 x = r(x, self._temb(pk, trows, r), f * H_ * W_, gf, out=None if (blk.has_cross_attention or mm is not None) else dst)
                 if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst)
+                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag)
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
             if blk.upsamplers is not None:
