@@ -320,6 +320,20 @@ size_t md_free_init_workspace_bytes(int F, int H, int W);
 int md_free_init_mix_f16(void* out, const void* x0, const void* noise0, const void* z, const float* lpf, int F, int H, int W, float a, float b,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Token downsampling of the K / V source of spatial self-attention (ToDo: Token Downsampling, Smith et al., arXiv 2402.13573; the
+ * pipeline's kv_downsample=): Q keeps every token, to_k / to_v read the token grid reduced by s per axis.
+ * x: [B*Hh*Ww][C] fp16 row-major and contiguous, the tokens of B frames; y: [B*out_stride][C].  With Ho = Hh / s, Wo = Ww / s (integer
+ * division: a last row / column that does not fill a block is dropped) and Lk = Ho*Wo, frame b writes rows b*out_stride + oy*Wo + ox:
+ *   mode 0 (nearest, the paper's): y = x[b, oy*s, ox*s], a copy: torch F.interpolate(scale_factor=1/s, mode="nearest") on the grid
+ *   mode 1 (mean): the s x s block at (oy*s, ox*s), added in fp32 in the order (dy, dx) ascending, times fp32(1 / s^2), rounded ONCE to
+ *                  fp16: torch F.avg_pool2d(kernel_size=s, stride=s)
+ * Rows [Lk, out_stride) of every frame are written as exact +0: the pad md_attention_fwd_f16 documents, so y goes through the bias-free
+ * to_k / to_v and into that entry with kv_stride = out_stride.  Nothing outside the B*out_stride rows of y is written.  16-byte loads and
+ * stores, no atomics: two calls give the same bits.
+ * s in 2..8, mode 0 or 1, C % 8 == 0, Ho >= 1 and Wo >= 1, out_stride >= Lk and out_stride % 8 == 0, x and y not NULL, 16-byte aligned
+ * and not overlapping; MD_ERR_ARG otherwise, with nothing launched. */
+int md_token_pool_f16(const void* x, void* y, int B, int Hh, int Ww, int C, int s, int mode, int out_stride, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

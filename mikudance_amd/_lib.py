@@ -69,6 +69,7 @@ SIGNATURES = {
     "md_free_init_plan": (c_int, [c_int, c_int, c_int]),
     "md_free_init_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "md_free_init_mix_f16": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, c_size_t, P]),
+    "md_token_pool_f16": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
 }
 
 _lib = None

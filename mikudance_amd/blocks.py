@@ -297,8 +297,13 @@ class TransformerBlock(_Packed):
             self._kv_cache = (cross.root, ops.gemm(cross.ctx, pk["k2"]), ops.gemm(cross.ctx, pk["v2"], transpose_out=True), {})
         return self._kv_cache[1:]
 
-    def forward(self, h, B, L, cross, pag=None):
+    def forward(self, h, B, L, cross, pag=None, kv_pool=None):
         """h: [B*L, C] tokens.  Returns tokens.
+        kv_pool: None, or (Hh, Ww, s, mode) with Hh * Ww == L: token downsampling of the self-attention K / V (ToDo, Smith et al., arXiv
+        2402.13573).  q = to_q(norm1(x)) keeps every token; the K / V source -- norm1(x), or norm1(x) + bank on the rows that read the bank,
+        pooled AFTER the add -- goes through ops.token_pool (s per axis, mode "nearest" or "mean") in front of to_k / to_v, and the attention
+        runs with Lk = (Hh // s) * (Ww // s) keys at kv_stride = roundup8(Lk).  The bank written is the full-resolution norm1(x).  A block whose
+        self-attention is perturbed has no attention to shorten: kv_pool has no effect there.  None: exactly the operator calls below.
         pag: None, or the collection of TransformerBlocks whose self-attention is perturbed (perturbed-attention guidance, Ahn et al.,
         arXiv 2403.17377; diffusers PAGIdentitySelfAttnProcessor2_0).  Not None says that ALL rows of h are a perturbed CONDITIONAL evaluation:
         every row reads the bank (the conditional-only read below, with or without ref_cfg), and in a block that is in `pag` the attention map
@@ -309,6 +314,9 @@ class TransformerBlock(_Packed):
         if pag is not None and (CHAIN is not None or self.ref_mode == "write"):
             raise ValueError("TransformerBlock: a perturbed evaluation is a call of its own: not one clip-half of a two-queue call, not a bank write")
         perturbed = pag is not None and any(self is b for b in pag)
+        pool = kv_pool is not None and not perturbed
+        if pool and kv_pool[0] * kv_pool[1] != L:
+            raise ValueError(f"TransformerBlock: kv_pool grid {kv_pool[0]} x {kv_pool[1]} does not hold L = {L} tokens")
         if self.ref_mode == "read" and len(self.bank) == 1 and not (self.ref_cfg and CHAIN == 0):
             bank = self.bank[0]
             brows = bank.shape[0] * bank.shape[1] if bank.dim() == 3 else bank.shape[0]
@@ -332,20 +340,30 @@ class TransformerBlock(_Packed):
             n, kv = ops.layernorm(h, pk["n1w"], pk["n1b"], add=b2.contiguous(), add_mode=1, add_row_begin=begin)
             if not perturbed:
                 q = ops.gemm(n, pk["q1"])
-                k = ops.gemm(kv, pk["k1"])
-                vt = ops.gemm(kv, pk["v1"], transpose_out=True)
+                if not pool:
+                    k = ops.gemm(kv, pk["k1"])
+                    vt = ops.gemm(kv, pk["v1"], transpose_out=True)
         else:
             n = kv = ops.layernorm(h, pk["n1w"], pk["n1b"])
             if self.ref_mode == "write":
                 self.bank.append(n.view(B, L, C))
                 if self.stop_after_bank:
                     return h
-            if not perturbed:
+            if pool:
+                q = ops.gemm(n, pk["q1"])                                # q alone: the fused q|k GEMM has no k to make here
+            elif not perturbed:
                 qk = ops.gemm(n, pk["qk1"])
                 q, k = qk[:, :C], qk[:, C:]
                 vt = ops.gemm(n, pk["v1"], transpose_out=True)
-        # identity attention map: every query row takes its own V row
-        a = ops.gemm(kv, pk["v1"]) if perturbed else ops.attention(q, k, vt, B, H, D, L, L)
+        if pool:
+            # K / V from the downsampled grid (its pad rows are zeros and to_k / to_v have no bias: zero K rows, zero V^T columns)
+            kvp, Lk, stride = ops.token_pool(kv, B, kv_pool[0], kv_pool[1], kv_pool[2], kv_pool[3])
+            k = ops.gemm(kvp, pk["k1"])
+            vt = ops.gemm(kvp, pk["v1"], transpose_out=True)
+            a = ops.attention(q, k, vt, B, H, D, L, Lk, kv_stride=stride)
+        else:
+            # identity attention map: every query row takes its own V row
+            a = ops.gemm(kv, pk["v1"]) if perturbed else ops.attention(q, k, vt, B, H, D, L, L)
         kv2 = self.context_kv(cross)
         zf = min(cross.zero_frames, B) if ZERO_CONTEXT_SKIP else 0
         if zf:
@@ -385,13 +403,19 @@ class SpatialTransformer(_Packed):
                     pi=packing.conv1x1_weight(self.proj_in.weight, dev), pib=packing.vec(self.proj_in.bias, dev),
                     po=packing.conv1x1_weight(self.proj_out.weight, dev), pob=packing.vec(self.proj_out.bias, dev))
 
-    def forward(self, x, cross, out=None, pag=None):
-        """pag: handed on to the block (TransformerBlock.forward); None everywhere but in a perturbed evaluation."""
+    def forward(self, x, cross, out=None, pag=None, kv_pool=None):
+        """pag: handed on to the block (TransformerBlock.forward); None everywhere but in a perturbed evaluation.
+        kv_pool: None, or (s, mode) -- or (Hh, Ww, s, mode) with this tensor's own grid: K / V token downsampling, handed on to the block as
+        (Hh, Ww, s, mode) (the block only knows L)."""
         pk = self.packed()
         B, Hh, Ww, C = x.shape
         blk = self.transformer_blocks[0]
         h = gn_linear(x, pk["nw"], pk["nb"], 1e-6, pk["pi"], pk["pib"])
-        h = blk(h, B, Hh * Ww, cross, pag=pag)
+        if kv_pool is not None:
+            if len(kv_pool) == 4 and tuple(kv_pool[:2]) != (Hh, Ww):
+                raise ValueError(f"SpatialTransformer: kv_pool grid {tuple(kv_pool[:2])} is not this tensor's {Hh} x {Ww}")
+            kv_pool = (Hh, Ww) + tuple(kv_pool[-2:])
+        h = blk(h, B, Hh * Ww, cross, pag=pag, kv_pool=kv_pool)
         if blk.ref_mode == "write" and blk.stop_after_bank:
             return x
         if out is not None:

@@ -22,6 +22,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      arXiv 2410.02416, per frame on the data prediction; default off)
     pipe(..., pag_scale=--pag_scale, pag_adaptive_scale=--pag_adaptive_scale, pag_applied_layers=--pag_layers)
                      (an addition: perturbed-attention guidance, arXiv 2403.17377; default 0.0 = off)
+    pipe(..., kv_downsample=--kv_downsample, kv_downsample_mode=--kv_downsample_mode)
+                     (an addition: K / V token downsampling in the spatial self-attention, arXiv 2402.13573; default 1 = off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -49,6 +51,15 @@ from .scene_motion import camera_to_scene_motion
 SAMPLERS = {"ddim": lambda kw: DDIMScheduler(**kw),
             "dpmpp_2m": lambda kw: DPMSolverMultistepScheduler.from_config(kw, solver_order=2, algorithm_type="dpmsolver++"),
             "dpmpp_2m_sde": lambda kw: DPMSolverMultistepScheduler.from_config(kw, solver_order=2, algorithm_type="sde-dpmsolver++")}
+
+
+def _factors(text):
+    """--kv_downsample: "2" or "4,2" -> a tuple of integers (their range is the pipeline's business)."""
+    import argparse
+    try:
+        return tuple(int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected comma-separated integers, got {text!r}") from None
 
 
 def parse_args(argv=None):
@@ -113,6 +124,12 @@ def parse_args(argv=None):
     parser.add_argument("--pag_layers", default="mid",
                         help="(addition) PAG: comma-separated attention blocks of the denoising UNet, e.g. mid or "
                              "down_blocks.2,up_blocks.1.attentions.0")
+    parser.add_argument("--kv_downsample", type=_factors, default=(1,), metavar="N[,N...]",
+                        help="(addition) K / V token downsampling in the spatial self-attention of the denoising UNet (ToDo, arXiv 2402.13573), "
+                             "an approximation that saves attention time at high resolution: one integer factor 1..8 per resolution level from "
+                             "the highest down, e.g. 2 or 4,2; 1 = off")
+    parser.add_argument("--kv_downsample_mode", choices=("nearest", "mean"), default="nearest",
+                        help="(addition) how the K / V token grid is reduced: nearest (the paper's) or the mean of each block")
     args = parser.parse_args(argv)
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
@@ -211,7 +228,8 @@ def main(argv=None):
                free_init_temporal_stop=args.free_init_temporal_stop, free_init_fast=args.free_init_fast,
                apg=args.apg, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum,
                pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale,
-               pag_applied_layers=tuple(n.strip() for n in args.pag_layers.split(",") if n.strip()))
+               pag_applied_layers=tuple(n.strip() for n in args.pag_layers.split(",") if n.strip()),
+               kv_downsample=args.kv_downsample, kv_downsample_mode=args.kv_downsample_mode)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

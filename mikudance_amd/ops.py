@@ -488,3 +488,29 @@ def free_init_mix(out, x0, noise0, z, lpf, a, b):
               ws.data_ptr(), ws.numel() * 4, _st(),
               meta=(f"free_init_mix F={F} H={H} W={W}", 16.0 * n * (F + H + W), 2.0 * n * 4 + 1.0 * n + 12 * 8.0 * n))
     return out
+
+
+POOL_MODES = {"nearest": 0, "mean": 1}
+
+
+def token_pool(x, B, Hh, Ww, s, mode="nearest", out=None):
+    """Token downsampling of a K / V source (md_token_pool_f16; ToDo, arXiv 2402.13573): x [B*Hh*Ww, C] contiguous, the tokens of B frames ->
+    (y, Lk, stride): y [B*stride, C], frame b in rows [b*stride, b*stride + Lk), Lk = (Hh // s) * (Ww // s), stride = roundup8(Lk), the rows
+    behind Lk exact zeros (the pad of `attention`: pass kv_stride=stride).  mode "nearest": the token at (oy*s, ox*s); "mean": the mean of the
+    s x s block, fp32, one rounding.  `out`: a contiguous [B*stride, C] destination."""
+    _chk(x, "x"); _chk(out, "out")
+    if mode not in POOL_MODES:
+        raise _lib.MdanceHipError(f"token_pool: mode must be one of {sorted(POOL_MODES)}, got {mode!r}")
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[0] != B * Hh * Ww:
+        raise _lib.MdanceHipError(f"token_pool: x must be a contiguous [B*Hh*Ww, C] matrix, got {tuple(x.shape)} for B={B} Hh={Hh} Ww={Ww}")
+    C = x.shape[1]
+    Ho, Wo = Hh // s, Ww // s
+    Lk = Ho * Wo
+    stride = (Lk + 7) // 8 * 8
+    if out is None:
+        out = torch.empty((B * stride, C), device=x.device, dtype=F16)
+    assert out.is_contiguous() and tuple(out.shape) == (B * stride, C), (tuple(out.shape), (B * stride, C))
+    taps = s * s if mode == "mean" else 1
+    _lib.call("md_token_pool_f16", x.data_ptr(), out.data_ptr(), B, Hh, Ww, C, s, POOL_MODES[mode], stride, _st(),
+              meta=(f"token_pool B={B} {Hh}x{Ww} C={C} s={s} {mode}", 1.0 * B * Lk * C * (taps if taps > 1 else 0), 2.0 * B * C * (Lk * taps + stride)))
+    return out, Lk, stride

@@ -133,7 +133,7 @@ class MikuDanceVideoPipeline:
                 window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0, context_fuse="flat", free_init_iters=1,
                 free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25, free_init_temporal_stop=0.25,
                 free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
-                pag_applied_layers=("mid",)):
+                pag_applied_layers=("mid",), kv_downsample=1, kv_downsample_mode="nearest"):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -223,6 +223,21 @@ class MikuDanceVideoPipeline:
                             "down_blocks.I", "up_blocks.I", "down_blocks.I.attentions.J", "up_blocks.I.attentions.J"; a block is selected
                             when its key prefix equals a name or starts with name + ".".  An empty sequence (with pag_scale > 0) and a
                             name that selects no block raise ValueError
+        kv_downsample       K / V token downsampling in the spatial self-attention of the denoising UNet (ToDo: Token Downsampling, Smith et al.,
+                            arXiv 2402.13573), an opt-in APPROXIMATION that trades accuracy for time at high resolution: an integer factor 1..8
+                            per resolution level from the highest down (an int n stands for (n,); level i = down_blocks.i and the up block of
+                            the same resolution, the last level also mid_block; missing levels and 1 = untouched).  At a level with factor s,
+                            Q keeps every token while to_k / to_v read the token grid reduced by s per axis (ops.token_pool, after the
+                            reference bank has been added), so that level's attention FLOPs and K / V projection rows fall by s^2; the
+                            price is one pass over the K / V source and a q-only GEMM where the plain path fuses q|k.  The reference UNet, its
+                            banks (full resolution), cross-attention and the motion modules are untouched; with PAG the unselected blocks of
+                            the perturbed evaluation pool like the main one.  Sits inside the UNet: works with every sampler, eta, init_latents,
+                            window schedule, fuse mode, FreeInit, APG, PAG, guidance_rescale, window_parallel and two_queues.  ValueError, before
+                            anything runs, for other values, more factors than levels, a level without attention, or a factor that leaves a
+                            level of THIS latent size without a single s x s block (levels halve with ceil).  1 (the default) and all ones:
+                            bitwise the loop without the keyword, no new operator call
+        kv_downsample_mode  "nearest" (the paper's: the token at the top-left of each s x s block, F.interpolate nearest) or "mean" (the block's
+                            mean, F.avg_pool2d)
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         self._check_fuse(context_fuse)
@@ -235,6 +250,7 @@ class MikuDanceVideoPipeline:
         self._check_strength(strength, init_latents is not None, num_inference_steps)
         self._check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale)
         pag_s, pag_a, pag_names = self._check_pag(pag_scale, pag_adaptive_scale, pag_applied_layers, guidance_rescale, apg)
+        kv_factors, kv_mode = self._check_kv_downsample(kv_downsample, kv_downsample_mode, latents.shape[-2], latents.shape[-1])
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         dev = latents.device
@@ -246,6 +262,9 @@ class MikuDanceVideoPipeline:
         # PAG: the selected blocks (a name that selects none raises here, before anything runs); off: nothing below changes
         pag_on = pag_s > 0.0
         pag_sel = den.pag_blocks(pag_names) if pag_on else None
+        # K / V token downsampling: the per-block plan (too many factors / a level without attention raise here); all ones: no plan, no keyword
+        kv_plan = den.kv_downsample_plan(kv_factors, kv_mode) if any(s > 1 for s in kv_factors) else None
+        kv_kw = {} if kv_plan is None else dict(kv_downsample=kv_plan)
         from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
         multistep = isinstance(sch, DPMSolverMultistepScheduler)
         if not multistep and not isinstance(sch, DDIMScheduler):
@@ -352,7 +371,7 @@ class MikuDanceVideoPipeline:
                         # both clip-halves are packed from the SAME latents (batch stride 0 above): the layers in front of the first attention
                         # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
                         pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
-                                                two_queues=self.two_queues)
+                                                two_queues=self.two_queues, **kv_kw)
                         if wts_dev is None:
                             ops.window_accumulate(pred, ns_main, counter, win_dev[wi], f, F_, HW, halves=nb)
                         else:
@@ -360,7 +379,7 @@ class MikuDanceVideoPipeline:
                         if s_t > 0.0:
                             # ---- PAG: the conditional frames once more (the banks are still in place), selected self-attention maps = identity
                             pred = den.forward_nhwc(x[(nb - 1) * f:], 1, f, torch.full((1,), float(t)), cross.rows(f, 2 * f) if do_cfg else cross,
-                                                    pag=pag_sel)
+                                                    pag=pag_sel, **kv_kw)
                             if wts_dev is None:
                                 ops.window_accumulate(pred, ns_pag, pag_counter, win_dev[wi], f, F_, HW, halves=1)
                             else:
@@ -447,6 +466,15 @@ class MikuDanceVideoPipeline:
         if s > 0.0 and apg:
             raise ValueError("pag_scale > 0 cannot be combined with apg=True: APG's statistics would have to be taken over the PAG-guided output")
         return s, a, names
+
+    @staticmethod
+    def _check_kv_downsample(kv_downsample, kv_downsample_mode, h, w):
+        """The refusals of kv_downsample / kv_downsample_mode that need no model -> (factors, mode): the values, the mode, and every selected
+        level of an h x w latent keeping at least one s x s block.  How many levels there are is the UNet's business (kv_downsample_plan)."""
+        from .unet_3d_mix import check_kv_downsample, check_kv_downsample_grid
+        factors, mode = check_kv_downsample(kv_downsample, kv_downsample_mode)
+        check_kv_downsample_grid(factors, int(h), int(w))
+        return factors, mode
 
     @staticmethod
     def _pag_scale_at(pag_scale, pag_adaptive_scale, t):
@@ -631,7 +659,8 @@ class MikuDanceVideoPipeline:
                  context_overlap=8, context_batch_size=1, interpolation_factor=1, guidance_rescale: float = 0.0, video=None, strength: float = 1.0,
                  context_fuse="flat", free_init_iters=1, free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25,
                  free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0,
-                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), **kwargs):
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), kv_downsample=1,
+                 kv_downsample_mode="nearest", **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -658,6 +687,11 @@ class MikuDanceVideoPipeline:
         if pag_s > 0.0:
             self.denoising_unet.pag_blocks(pag_names)
         pag_kw = dict(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, pag_applied_layers=pag_applied_layers)
+        # kv_downsample*: K / V token downsampling (denoise()); checked here too, against the clip's latent size and the UNet's levels
+        kv_factors, kv_mode = self._check_kv_downsample(kv_downsample, kv_downsample_mode, (height or 768) // 8, (width or 768) // 8)
+        if any(s > 1 for s in kv_factors):
+            self.denoising_unet.kv_downsample_plan(kv_factors, kv_mode)
+        kv_kw = dict(kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode)
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -692,7 +726,7 @@ class MikuDanceVideoPipeline:
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
                                context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
                                guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength,
-                               context_fuse=context_fuse, **fi_kw, **apg_kw, **pag_kw)
+                               context_fuse=context_fuse, **fi_kw, **apg_kw, **pag_kw, **kv_kw)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)

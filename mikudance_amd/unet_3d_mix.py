@@ -282,6 +282,30 @@ class _UNetBase(_Packed):
             picked += [b for b in hit if not any(b is q for q in picked)]
         return tuple(picked)
 
+    def kv_downsample_plan(self, factors, mode="nearest"):
+        """The per-block plan of K / V token downsampling (ToDo, arXiv 2402.13573) that forward_nhwc(kv_downsample=) takes:
+        {SpatialTransformer: (s, mode)} for every spatial transformer of a level whose factor is > 1, or None when no factor is.
+        factors: integers 1..8, one per resolution level from the highest down (an int n stands for (n,)); level i covers down_blocks.i and
+        the up block at the same resolution, up_blocks.(levels - 1 - i), and the last level also mid_block; missing levels mean 1 = untouched.
+        ValueError for anything else, for more factors than levels and for a factor > 1 on a level without an attention block."""
+        factors, mode = check_kv_downsample(factors, mode)
+        n = len(self.down_blocks)
+        if len(factors) > n:
+            raise ValueError(f"kv_downsample: {len(factors)} factors for a UNet of {n} resolution levels")
+        plan = {}
+        for i, s in enumerate(factors):
+            if s == 1:
+                continue
+            names = [(f"down_blocks.{i}", self.down_blocks[i]), (f"up_blocks.{n - 1 - i}", self.up_blocks[n - 1 - i])]
+            if i == n - 1:
+                names.append(("mid_block", self.mid_block))
+            hit = [a for _, blk in names if blk.has_cross_attention for a in blk.attentions]
+            if not hit:
+                raise ValueError(f"kv_downsample: factor {s} on level {i}, which has no attention block ({', '.join(nm for nm, _ in names)})")
+            for a in hit:
+                plan[a] = (s, mode)
+        return plan or None
+
     @property
     def dtype(self):
         return self.conv_in.weight.dtype
@@ -316,6 +340,35 @@ def check_pag_layer_names(applied_layers):
             raise ValueError(f"pag_applied_layers: unknown layer name {name!r}; the forms are 'mid_block' (or 'mid'), 'down_blocks.I', "
                              "'up_blocks.I', 'down_blocks.I.attentions.J', 'up_blocks.I.attentions.J'")
     return names
+
+
+KV_POOL_MODES = ("nearest", "mean")
+
+
+def check_kv_downsample(factors, mode):
+    """kv_downsample / kv_downsample_mode as (tuple of integer factors 1..8, mode); an int n stands for (n,).  ValueError otherwise.  Needs no
+    model: the pipeline calls it before anything runs."""
+    import numbers
+    if isinstance(factors, numbers.Integral) and not isinstance(factors, bool):
+        factors = (factors,)
+    try:
+        factors = tuple(factors)
+    except TypeError:
+        raise ValueError(f"kv_downsample must be an integer or a sequence of integers, got {factors!r}") from None
+    for v in factors:
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not 1 <= v <= 8:
+            raise ValueError(f"kv_downsample: every factor must be an integer in 1..8, got {v!r}")
+    if mode not in KV_POOL_MODES:
+        raise ValueError(f"kv_downsample_mode must be one of {KV_POOL_MODES}, got {mode!r}")
+    return tuple(int(v) for v in factors), mode
+
+
+def check_kv_downsample_grid(factors, h, w):
+    """Refuses a factor whose level of an h x w latent has no s x s block to pool (the levels halve with ceil, as the stride-2 conv does)."""
+    for i, s in enumerate(factors):
+        if s > 1 and (h // s < 1 or w // s < 1):
+            raise ValueError(f"kv_downsample: factor {s} on level {i}, whose token grid is {h} x {w} for this latent size: nothing left to attend to")
+        h, w = (h + 1) // 2, (w + 1) // 2
 
 
 class UNet3DConditionModel(_UNetBase):
@@ -370,8 +423,10 @@ class UNet3DConditionModel(_UNetBase):
         self._build(in_channels, tuple(block_out_channels), cross_attention_dim, norm_eps, flags, mm_kwargs, with_out=True)
 
     # ------------------------------------------------------------------------------------------ internal NHWC forward
-    def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None):
+    def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None, kv_downsample=None):
         """x: (nb*f, h, w, 64) fp16 (4 latent channels, zero padded); returns pred tokens [(nb*f*h*w), 4].
+        kv_downsample: None, or the plan of kv_downsample_plan(): the spatial transformers it names compute their self-attention K / V from the
+        downsampled token grid (SpatialTransformer.forward(kv_pool=)), on one queue and on two, in the main and in a perturbed evaluation.
         pag: None, or the blocks of pag_blocks(): this call is then the PERTURBED evaluation of perturbed-attention guidance (arXiv 2403.17377), a
         call of its own beside the main one: nb must be 1, x the conditional frames, cross their context (the main call's context or its
         rows(f, 2f): the cached K / V projections are shared, nothing of the main call is touched).  Every row reads the bank, and the selected
@@ -397,7 +452,7 @@ class UNet3DConditionModel(_UNetBase):
         share = bool(halves_identical and nb == 2 and float(tt[0]) == float(tt[-1]))
         b0 = self.down_blocks[0]
         if share and two_queues and x.is_cuda and (b0.has_cross_attention or b0.motion_modules[0] is not None):
-            return self._forward_two_queues(x, f, trows, cross, pk, gf, force_size)
+            return self._forward_two_queues(x, f, trows, cross, pk, gf, force_size, kv_downsample=kv_downsample)
         skips = _Skips(self._skip_plan())
         first = None
         if share:
@@ -416,11 +471,13 @@ class UNet3DConditionModel(_UNetBase):
                 first = dst
         else:
             x = ops.conv3x3(x, pk["cin"], c0, bias=pk["cinb"], out=skips.slot(B, hh, ww, c0, dev))
-        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, first, pag=pag))
+        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, first, pag=pag, kv_downsample=kv_downsample))
 
-    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, first=None, out=None, pag=None):
+    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, first=None, out=None, pag=None, kv_downsample=None):
         """Everything behind conv_in.  x: conv_in's output (nb*f, h, w, C0), already in its skip slot; `first`: the first resnet's output when
-        the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes, (nb*f, h, w, 4); `pag`: see forward_nhwc."""
+        the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes, (nb*f, h, w, 4); `pag`, `kv_downsample`:
+        see forward_nhwc."""
+        kvp = (lambda a: None) if kv_downsample is None else kv_downsample.get
         dev = x.device
         B = x.shape[0]
         for bi, blk in enumerate(self.down_blocks):
@@ -436,14 +493,14 @@ class UNet3DConditionModel(_UNetBase):
                 if not last_op and first is not None and bi == 0 and j == 0:
                     dst = skips.slot(B, H_, W_, r.cout, dev)
                 if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag)
+                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag, kv_pool=kvp(blk.attentions[j]))
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
             if blk.downsamplers is not None:
                 x = blk.downsamplers[0](x, out=skips.slot(B, (x.shape[1] + 1) // 2, (x.shape[2] + 1) // 2, blk.downsamplers[0].c, dev))
         mb = self.mid_block
         x = mb.resnets[0](x, self._temb(pk, trows, mb.resnets[0]), f * x.shape[1] * x.shape[2], gf)
-        x = mb.attentions[0](x, cross, pag=pag)
+        x = mb.attentions[0](x, cross, pag=pag, kv_pool=kvp(mb.attentions[0]))
         if mb.motion_modules[0] is not None:
             x = mb.motion_modules[0](x, nb, f)
         x = mb.resnets[1](x, self._temb(pk, trows, mb.resnets[1]), f * x.shape[1] * x.shape[2], gf, out=skips.hidden_slot())
@@ -457,7 +514,7 @@ class UNet3DConditionModel(_UNetBase):
                 dst = skips.hidden_slot() if len(skips) and not (last and blk.upsamplers is not None) else None
                 x = r(x, self._temb(pk, trows, r), f * H_ * W_, gf, out=None if (blk.has_cross_attention or mm is not None) else dst)
                 if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag)
+                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag, kv_pool=kvp(blk.attentions[j]))
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
             if blk.upsamplers is not None:
@@ -465,7 +522,7 @@ class UNet3DConditionModel(_UNetBase):
         x = groupnorm_frames(x, pk["ow"], pk["ob"], self.norm_eps, True, gf)
         return ops.conv3x3(x, pk["co"], 4, bias=pk["cob"], out=out)
 
-    def _forward_two_queues(self, x, f, trows, cross, pk, gf, force_size):
+    def _forward_two_queues(self, x, f, trows, cross, pk, gf, force_size, kv_downsample=None):
         """The two clip-halves of a classifier-free-guidance batch as two kernel queues (stage B, without CU masks).
 
         One queue of B = 2f kernels leaves the chip idle wherever a launch cannot fill it -- partial last rounds of the persistent GEMM / conv
@@ -517,7 +574,7 @@ class UNet3DConditionModel(_UNetBase):
                 blocks.CHAIN = c
                 try:
                     self._body(slot0 if c == 0 else slot1, sk[c], 1, f, trows[c:c + 1], cross.rows(c * f, (c + 1) * f), pk, gf, force_size,
-                               first=first, out=pred[c * f:(c + 1) * f])
+                               first=first, out=pred[c * f:(c + 1) * f], kv_downsample=kv_downsample)
                 finally:
                     blocks.CHAIN = None
                 ev = torch.cuda.Event()
