@@ -334,6 +334,27 @@ int md_free_init_mix_f16(void* out, const void* x0, const void* noise0, const vo
  * and not overlapping; MD_ERR_ARG otherwise, with nothing launched. */
 int md_token_pool_f16(const void* x, void* y, int B, int Hh, int Ww, int C, int s, int mode, int out_stride, void* stream);
 
+/* Query blur of smoothed-energy guidance (SEG, Hong, arXiv 2408.00760; the pipeline's seg_scale=): the queries of the selected
+ * self-attention blocks are filtered over the token grid (TransformerBlock.forward(seg=), through ops.token_blur).
+ * x: [B*Hh*Ww][C] fp16 row-major and contiguous, the tokens of B frames, row = (b*Hh + y)*Ww + x (the layout of md_token_pool_f16); y: the
+ * same shape.  Every channel is filtered on its own.
+ * md_token_blur_f16: separable filter with reflect padding (the official gaussian_blur_2d, taken per axis).  wx: kx fp32 taps along the
+ *   grid's x axis, wy: ky taps along y, device tables made by the caller (ops.token_blur: w_j ~ exp(-(j/sigma)^2/2), j = -r..r, float64,
+ *   normalised, rounded once).  Output position p adds tap j = 0..k-1 in ascending order, tap j reading position reflect(p + j - k/2) with
+ *   reflect(i) = -i for i < 0 and 2(n-1) - i for i >= n (torch "reflect": the edge is not repeated).  First x -> workspace along x, then
+ *   workspace -> y along y: fp32 accumulation and an fp32 intermediate, ONE rounding to fp16.  A one-tap filter of weight 1 returns x bit
+ *   for bit.  kx, ky odd, 1 <= kx <= Ww + 1, 1 <= ky <= Hh + 1; Hh, Ww <= 224 (a line is staged in 64 KiB of LDS).
+ * md_token_mean_f16: sigma = infinity, the reference's inf_blur: every token of frame b becomes that frame's per-channel mean over its L
+ *   tokens (fp32 sums in a fixed order, times fp32(1/L), one rounding).  It is not the limit of the reflect-padded filter.
+ * workspace: md_token_blur_workspace_bytes(B, Hh, Ww, C) bytes (B*Hh*Ww*C*4; the mean, with Hh*Ww = L, needs no more), 16-byte aligned, not
+ * overlapping x or y.  No atomics: two calls give the same bits.  Nothing outside the B*Hh*Ww rows of y is written.
+ * C % 8 == 0, all sizes positive, x / y / workspace / tables not NULL, 16-byte aligned, x and y not overlapping; MD_ERR_ARG otherwise, with
+ * nothing launched and y untouched. */
+size_t md_token_blur_workspace_bytes(int B, int Hh, int Ww, int C);
+int md_token_blur_f16(const void* x, void* y, int B, int Hh, int Ww, int C, const float* wy, int ky, const float* wx, int kx, void* workspace,
+                      void* stream);
+int md_token_mean_f16(const void* x, void* y, int B, int L, int C, void* workspace, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

@@ -70,6 +70,9 @@ SIGNATURES = {
     "md_free_init_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "md_free_init_mix_f16": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, c_size_t, P]),
     "md_token_pool_f16": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "md_token_blur_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "md_token_blur_f16": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P]),
+    "md_token_mean_f16": (c_int, [P, P, c_int, c_int, c_int, P, P]),
 }
 
 _lib = None

@@ -297,8 +297,14 @@ class TransformerBlock(_Packed):
             self._kv_cache = (cross.root, ops.gemm(cross.ctx, pk["k2"]), ops.gemm(cross.ctx, pk["v2"], transpose_out=True), {})
         return self._kv_cache[1:]
 
-    def forward(self, h, B, L, cross, pag=None, kv_pool=None):
+    def forward(self, h, B, L, cross, pag=None, kv_pool=None, seg=None):
         """h: [B*L, C] tokens.  Returns tokens.
+        seg: None, or (blocks, Hh, Ww, sigma) with Hh * Ww == L: smoothed-energy guidance (SEG, Hong, arXiv 2408.00760).  Not None has pag's
+        meaning -- ALL rows of h are a perturbed CONDITIONAL evaluation, every row reads the bank -- with pag's refusals, and in a block that is
+        in `blocks` the QUERIES are blurred over the token grid: q = to_q(norm1(x)) from the q-only GEMM goes through ops.token_blur (sigma a
+        positive float: Gaussian with reflect padding; math.inf: the frame's mean query; channel-wise, so the head split needs no handling),
+        K and V come unblurred from norm1(x) + bank, and the attention launch and everything behind it are unchanged; kv_pool still shortens
+        K / V there.  A block that is not in `blocks` issues the conditional half's calls.  Not together with pag.
         kv_pool: None, or (Hh, Ww, s, mode) with Hh * Ww == L: token downsampling of the self-attention K / V (ToDo, Smith et al., arXiv
         2402.13573).  q = to_q(norm1(x)) keeps every token; the K / V source -- norm1(x), or norm1(x) + bank on the rows that read the bank,
         pooled AFTER the add -- goes through ops.token_pool (s per axis, mode "nearest" or "mean") in front of to_k / to_v, and the attention
@@ -311,9 +317,14 @@ class TransformerBlock(_Packed):
         pk = self.packed()
         C, H = self.dim, self.heads
         D = C // H
-        if pag is not None and (CHAIN is not None or self.ref_mode == "write"):
+        if pag is not None and seg is not None:
+            raise ValueError("TransformerBlock: pag and seg are two perturbations of one evaluation: give one of them")
+        if (pag is not None or seg is not None) and (CHAIN is not None or self.ref_mode == "write"):
             raise ValueError("TransformerBlock: a perturbed evaluation is a call of its own: not one clip-half of a two-queue call, not a bank write")
         perturbed = pag is not None and any(self is b for b in pag)
+        blur = seg is not None and any(self is b for b in seg[0])
+        if blur and seg[1] * seg[2] != L:
+            raise ValueError(f"TransformerBlock: seg grid {seg[1]} x {seg[2]} does not hold L = {L} tokens")
         pool = kv_pool is not None and not perturbed
         if pool and kv_pool[0] * kv_pool[1] != L:
             raise ValueError(f"TransformerBlock: kv_pool grid {kv_pool[0]} x {kv_pool[1]} does not hold L = {L} tokens")
@@ -321,7 +332,7 @@ class TransformerBlock(_Packed):
             bank = self.bank[0]
             brows = bank.shape[0] * bank.shape[1] if bank.dim() == 3 else bank.shape[0]
             M = h.shape[0]
-            if pag is not None or (self.ref_cfg and CHAIN == 1):
+            if pag is not None or seg is not None or (self.ref_cfg and CHAIN == 1):
                 # the conditional half on its own: every row reads the bank (the conditional frames' part of a literal 2f-frame bank)
                 begin, b2 = 0, bank.reshape(-1, C)
                 if brows == 2 * M:
@@ -351,10 +362,16 @@ class TransformerBlock(_Packed):
                     return h
             if pool:
                 q = ops.gemm(n, pk["q1"])                                # q alone: the fused q|k GEMM has no k to make here
+            elif blur:
+                q = ops.gemm(n, pk["q1"])                                # q alone and contiguous: it goes through the blur
+                k = ops.gemm(kv, pk["k1"])
+                vt = ops.gemm(kv, pk["v1"], transpose_out=True)
             elif not perturbed:
                 qk = ops.gemm(n, pk["qk1"])
                 q, k = qk[:, :C], qk[:, C:]
                 vt = ops.gemm(n, pk["v1"], transpose_out=True)
+        if blur:
+            q = ops.token_blur(q, B, seg[1], seg[2], seg[3])
         if pool:
             # K / V from the downsampled grid (its pad rows are zeros and to_k / to_v have no bias: zero K rows, zero V^T columns)
             kvp, Lk, stride = ops.token_pool(kv, B, kv_pool[0], kv_pool[1], kv_pool[2], kv_pool[3])
@@ -403,8 +420,10 @@ class SpatialTransformer(_Packed):
                     pi=packing.conv1x1_weight(self.proj_in.weight, dev), pib=packing.vec(self.proj_in.bias, dev),
                     po=packing.conv1x1_weight(self.proj_out.weight, dev), pob=packing.vec(self.proj_out.bias, dev))
 
-    def forward(self, x, cross, out=None, pag=None, kv_pool=None):
+    def forward(self, x, cross, out=None, pag=None, kv_pool=None, seg=None):
         """pag: handed on to the block (TransformerBlock.forward); None everywhere but in a perturbed evaluation.
+        seg: None, or (blocks, sigma) -- or (blocks, Hh, Ww, sigma) with this tensor's own grid: smoothed-energy guidance, handed on to the
+        block as (blocks, Hh, Ww, sigma) (the block only knows L).
         kv_pool: None, or (s, mode) -- or (Hh, Ww, s, mode) with this tensor's own grid: K / V token downsampling, handed on to the block as
         (Hh, Ww, s, mode) (the block only knows L)."""
         pk = self.packed()
@@ -415,7 +434,11 @@ class SpatialTransformer(_Packed):
             if len(kv_pool) == 4 and tuple(kv_pool[:2]) != (Hh, Ww):
                 raise ValueError(f"SpatialTransformer: kv_pool grid {tuple(kv_pool[:2])} is not this tensor's {Hh} x {Ww}")
             kv_pool = (Hh, Ww) + tuple(kv_pool[-2:])
-        h = blk(h, B, Hh * Ww, cross, pag=pag, kv_pool=kv_pool)
+        if seg is not None:
+            if len(seg) == 4 and tuple(seg[1:3]) != (Hh, Ww):
+                raise ValueError(f"SpatialTransformer: seg grid {tuple(seg[1:3])} is not this tensor's {Hh} x {Ww}")
+            seg = (seg[0], Hh, Ww, seg[-1])
+        h = blk(h, B, Hh * Ww, cross, pag=pag, kv_pool=kv_pool, seg=seg)
         if blk.ref_mode == "write" and blk.stop_after_bank:
             return x
         if out is not None:

@@ -24,6 +24,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      (an addition: perturbed-attention guidance, arXiv 2403.17377; default 0.0 = off)
     pipe(..., kv_downsample=--kv_downsample, kv_downsample_mode=--kv_downsample_mode)
                      (an addition: K / V token downsampling in the spatial self-attention, arXiv 2402.13573; default 1 = off)
+    pipe(..., seg_scale=--seg_scale, seg_blur_sigma=--seg_blur_sigma, seg_applied_layers=--seg_layers)
+                     (an addition: smoothed-energy guidance, arXiv 2408.00760; default 0.0 = off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -130,6 +132,14 @@ def parse_args(argv=None):
                              "the highest down, e.g. 2 or 4,2; 1 = off")
     parser.add_argument("--kv_downsample_mode", choices=("nearest", "mean"), default="nearest",
                         help="(addition) how the K / V token grid is reduced: nearest (the paper's) or the mean of each block")
+    parser.add_argument("--seg_scale", type=float, default=0.0,
+                        help="(addition) smoothed-energy guidance scale (SEG, arXiv 2408.00760): steer away from a second conditional "
+                             "prediction made with the self-attention queries of --seg_layers Gaussian-blurred over the token grid, >= 0; "
+                             "0.0 = off; not with --pag_scale, --guidance_rescale or --apg")
+    parser.add_argument("--seg_blur_sigma", type=float, default=100.0,
+                        help="(addition) SEG: sigma of the query blur in tokens, > 0; inf = every query becomes its frame's mean query")
+    parser.add_argument("--seg_layers", default="mid",
+                        help="(addition) SEG: comma-separated attention blocks of the denoising UNet, as --pag_layers")
     args = parser.parse_args(argv)
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
@@ -229,7 +239,9 @@ def main(argv=None):
                apg=args.apg, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum,
                pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale,
                pag_applied_layers=tuple(n.strip() for n in args.pag_layers.split(",") if n.strip()),
-               kv_downsample=args.kv_downsample, kv_downsample_mode=args.kv_downsample_mode)
+               kv_downsample=args.kv_downsample, kv_downsample_mode=args.kv_downsample_mode,
+               seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma,
+               seg_applied_layers=tuple(n.strip() for n in args.seg_layers.split(",") if n.strip()))
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

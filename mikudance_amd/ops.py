@@ -514,3 +514,64 @@ def token_pool(x, B, Hh, Ww, s, mode="nearest", out=None):
     _lib.call("md_token_pool_f16", x.data_ptr(), out.data_ptr(), B, Hh, Ww, C, s, POOL_MODES[mode], stride, _st(),
               meta=(f"token_pool B={B} {Hh}x{Ww} C={C} s={s} {mode}", 1.0 * B * Lk * C * (taps if taps > 1 else 0), 2.0 * B * C * (Lk * taps + stride)))
     return out, Lk, stride
+
+
+def blur_kernel_size(sigma, n):
+    """Taps of SEG's Gaussian along a grid axis of n tokens: the official gaussian_blur_2d's ceil(6 sigma) + 1 - ceil(6 sigma) % 2, clamped to
+    the largest odd number a reflect-padded axis of n allows (n if n is odd, else n + 1); 1 for n = 1."""
+    import math
+    c = math.ceil(6.0 * sigma)
+    return int(min(c + 1 - c % 2, n if n % 2 else n + 1))
+
+
+def blur_taps(sigma, n):
+    """The normalised Gaussian taps w_j ~ exp(-(j / sigma)^2 / 2), j = -r..r, r = blur_kernel_size(sigma, n) // 2, in float64 (a list)."""
+    import math
+    r = blur_kernel_size(sigma, n) // 2
+    w = [math.exp(-0.5 * (j / sigma) ** 2) for j in range(-r, r + 1)]
+    tot = math.fsum(w)
+    return [v / tot for v in w]
+
+
+_blur_tables = {}
+_blur_ws = {}
+
+
+def token_blur(x, B, Hh, Ww, sigma, out=None):
+    """The query blur of smoothed-energy guidance (SEG, arXiv 2408.00760; md_token_blur_f16 / md_token_mean_f16): x [B*Hh*Ww, C] contiguous,
+    the tokens of B frames on an Hh x Ww grid -> y of the same shape, every channel filtered on its own.  sigma: a finite float > 0 -- the
+    separable Gaussian with reflect padding, taps per axis as blur_taps (float64 on the host, rounded once to fp32, kept on the device per
+    (sigma, n)) -- or math.inf: every token becomes its frame's mean.  fp32 throughout, one rounding; `out`: a contiguous destination of x's
+    shape that does not overlap x.  The fp32 workspace is kept per (device, stream)."""
+    import math
+    _chk(x, "x"); _chk(out, "out")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or math.isnan(sigma) or not sigma > 0:
+        raise _lib.MdanceHipError(f"token_blur: sigma must be a positive float or math.inf, got {sigma!r}")
+    if x.dim() != 2 or not x.is_contiguous() or B < 1 or Hh < 1 or Ww < 1 or x.shape[0] != B * Hh * Ww:
+        raise _lib.MdanceHipError(f"token_blur: x must be a contiguous [B*Hh*Ww, C] matrix, got {tuple(x.shape)} for B={B} Hh={Hh} Ww={Ww}")
+    C = x.shape[1]
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.is_contiguous() and out.shape == x.shape, (tuple(out.shape), tuple(x.shape))
+    need = _lib.load().md_token_blur_workspace_bytes(B, Hh, Ww, C)
+    key = (x.device, torch.cuda.current_stream().cuda_stream)
+    ws = _blur_ws.get(key)
+    if ws is None or ws.numel() * 4 < need:
+        ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
+        _blur_ws[key] = ws
+    n = B * Hh * Ww * C
+    if math.isinf(sigma):
+        _lib.call("md_token_mean_f16", x.data_ptr(), out.data_ptr(), B, Hh * Ww, C, ws.data_ptr(), _st(),
+                  meta=(f"token_blur B={B} {Hh}x{Ww} C={C} mean", 1.0 * n, 4.0 * n))
+        return out
+    tabs = []
+    for ax in (Hh, Ww):
+        tkey = (x.device, float(sigma), ax)
+        t = _blur_tables.get(tkey)
+        if t is None:
+            t = _blur_tables[tkey] = torch.tensor(blur_taps(float(sigma), ax), dtype=torch.float64).to(torch.float32).to(x.device)
+        tabs.append(t)
+    wy, wx = tabs
+    _lib.call("md_token_blur_f16", x.data_ptr(), out.data_ptr(), B, Hh, Ww, C, wy.data_ptr(), wy.numel(), wx.data_ptr(), wx.numel(), ws.data_ptr(),
+              _st(), meta=(f"token_blur B={B} {Hh}x{Ww} C={C} k={wy.numel()}x{wx.numel()}", 2.0 * n * (wy.numel() + wx.numel()), 12.0 * n))
+    return out

@@ -133,7 +133,8 @@ class MikuDanceVideoPipeline:
                 window_parallel=None, guidance_rescale=0.0, init_latents=None, strength=1.0, context_fuse="flat", free_init_iters=1,
                 free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25, free_init_temporal_stop=0.25,
                 free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
-                pag_applied_layers=("mid",), kv_downsample=1, kv_downsample_mode="nearest"):
+                pag_applied_layers=("mid",), kv_downsample=1, kv_downsample_mode="nearest", seg_scale=0.0, seg_blur_sigma=100.0,
+                seg_applied_layers=("mid",)):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -238,6 +239,20 @@ class MikuDanceVideoPipeline:
                             bitwise the loop without the keyword, no new operator call
         kv_downsample_mode  "nearest" (the paper's: the token at the top-left of each s x s block, F.interpolate nearest) or "mean" (the block's
                             mean, F.avg_pool2d)
+        seg_scale           smoothed-energy guidance (SEG; Hong, arXiv 2408.00760), finite, >= 0.  With seg_scale > 0 every window of every step
+                            gets one more evaluation of the denoising UNet on the conditional frames, PAG's perturbed evaluation with a
+                            tunable perturbation: in the blocks seg_applied_layers selects the self-attention QUERIES are Gaussian-blurred
+                            over the block's own token grid (ops.token_blur on the q-only GEMM's output; K and V unblurred), so the map
+                            stays a softmax of real energies, only flatter.  Its prediction p is PAG's extra plane of the accumulator and
+                            the step is PAG's: v + seg_scale (c - p) through md_cfg_*_step_pag, with or without CFG; no new step kernel.
+                            Works with every sampler, eta, init_latents, window schedule, fuse mode, FreeInit, kv_downsample and
+                            window_parallel.  ValueError, before anything runs, together with pag_scale > 0 (there is one perturbed
+                            plane), guidance_rescale > 0 or apg=True (PAG's reasons).  0.0 (the default): exactly the loop without the
+                            keywords, no new operator call
+        seg_blur_sigma      the blur's sigma in tokens: a finite number > 0 (taps ceil(6 sigma) rounded up to odd, clamped to the grid, reflect
+                            padding: the official implementation's gaussian_blur_2d, per axis) or math.inf (every query becomes its frame's mean
+                            query: the official inf_blur).  100.0, the paper's default, spans every grid of a 768 x 768 clip
+        seg_applied_layers  as pag_applied_layers
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         self._check_fuse(context_fuse)
@@ -251,6 +266,7 @@ class MikuDanceVideoPipeline:
         self._check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale)
         pag_s, pag_a, pag_names = self._check_pag(pag_scale, pag_adaptive_scale, pag_applied_layers, guidance_rescale, apg)
         kv_factors, kv_mode = self._check_kv_downsample(kv_downsample, kv_downsample_mode, latents.shape[-2], latents.shape[-1])
+        seg_s, seg_sigma, seg_names = self._check_seg(seg_scale, seg_blur_sigma, seg_applied_layers, pag_scale, guidance_rescale, apg)
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         dev = latents.device
@@ -262,6 +278,12 @@ class MikuDanceVideoPipeline:
         # PAG: the selected blocks (a name that selects none raises here, before anything runs); off: nothing below changes
         pag_on = pag_s > 0.0
         pag_sel = den.pag_blocks(pag_names) if pag_on else None
+        # SEG: PAG's perturbed evaluation with blurred queries in the selected blocks, PAG's plane and PAG's step (never both: _check_seg)
+        seg_on = seg_s > 0.0
+        if seg_on:
+            seg_sel = den.pag_blocks(seg_names, "seg_applied_layers", "smoothed-energy guidance")
+        pert_on = pag_on or seg_on
+        pert_kw = dict(seg=(seg_sel, seg_sigma)) if seg_on else dict(pag=pag_sel)
         # K / V token downsampling: the per-block plan (too many factors / a level without attention raise here); all ones: no plan, no keyword
         kv_plan = den.kv_downsample_plan(kv_factors, kv_mode) if any(s > 1 for s in kv_factors) else None
         kv_kw = {} if kv_plan is None else dict(kv_downsample=kv_plan)
@@ -299,10 +321,10 @@ class MikuDanceVideoPipeline:
             fi_ab = sch.noise_coefficients(sch.num_train_timesteps - 1)
         # PAG: the perturbed prediction is one more plane of the accumulator (the all_reduce carries it), summed by the same kernels at
         # halves = 1 against a scratch counter (they add to their counter: the real one would count every window twice)
-        noise_sum = torch.zeros((nb + 1 if pag_on else nb, F_, HW, 4), device=dev, dtype=torch.float32)
+        noise_sum = torch.zeros((nb + 1 if pert_on else nb, F_, HW, 4), device=dev, dtype=torch.float32)
         counter = torch.zeros((F_,), device=dev, dtype=torch.float32)
         ns_main, ns_pag, pag_counter = noise_sum, None, None
-        if pag_on:
+        if pert_on:
             ns_main, ns_pag, pag_counter = noise_sum[:nb], noise_sum[nb:], torch.zeros((F_,), device=dev, dtype=torch.float32)
         windows = [list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
                                                                             context_stride, context_overlap)]
@@ -350,7 +372,7 @@ class MikuDanceVideoPipeline:
                 for step_i, t in enumerate(timesteps):
                     noise_sum.zero_()
                     counter.zero_()
-                    s_t = self._pag_scale_at(pag_s, pag_a, t) if pag_on else 0.0      # a pure function of t: no sync
+                    s_t = self._pag_scale_at(pag_s, pag_a, t) if pag_on else seg_s    # a pure function of t: no sync (SEG: constant, 0 = off)
                     for wi, win in enumerate(windows):
                         if window_parallel is not None and not window_parallel.mine(wi):
                             continue                                         # another rank's window (its share arrives in the all_reduce)
@@ -377,9 +399,10 @@ class MikuDanceVideoPipeline:
                         else:
                             ops.window_accumulate_weighted(pred, ns_main, counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=nb)
                         if s_t > 0.0:
-                            # ---- PAG: the conditional frames once more (the banks are still in place), selected self-attention maps = identity
+                            # ---- PAG / SEG: the conditional frames once more (the banks are still in place), the selected self-attention maps
+                            # = identity / from blurred queries
                             pred = den.forward_nhwc(x[(nb - 1) * f:], 1, f, torch.full((1,), float(t)), cross.rows(f, 2 * f) if do_cfg else cross,
-                                                    pag=pag_sel, **kv_kw)
+                                                    **pert_kw, **kv_kw)
                             if wts_dev is None:
                                 ops.window_accumulate(pred, ns_pag, pag_counter, win_dev[wi], f, F_, HW, halves=1)
                             else:
@@ -466,6 +489,31 @@ class MikuDanceVideoPipeline:
         if s > 0.0 and apg:
             raise ValueError("pag_scale > 0 cannot be combined with apg=True: APG's statistics would have to be taken over the PAG-guided output")
         return s, a, names
+
+    @staticmethod
+    def _check_seg(seg_scale, seg_blur_sigma, seg_applied_layers, pag_scale, guidance_rescale, apg):
+        """The refusals of the seg_* keywords that need no model -> (seg_scale, sigma, layer names).  The values and the form of the names are
+        checked whether or not SEG is on; which blocks the names select is the UNet's business (pag_blocks)."""
+        from .unet_3d_mix import check_pag_layer_names
+        try:
+            s, sigma = float(seg_scale), float(seg_blur_sigma)
+        except (TypeError, ValueError):
+            raise ValueError(f"seg_scale and seg_blur_sigma must be numbers, got {seg_scale!r} and {seg_blur_sigma!r}") from None
+        if not (math.isfinite(s) and s >= 0.0):
+            raise ValueError(f"seg_scale must be a finite number >= 0, got {seg_scale}")
+        if math.isnan(sigma) or not sigma > 0.0:
+            raise ValueError(f"seg_blur_sigma must be a finite number > 0 or math.inf, got {seg_blur_sigma}")
+        names = check_pag_layer_names(seg_applied_layers, "seg_applied_layers")
+        if s > 0.0 and not names:
+            raise ValueError("seg_applied_layers is empty: smoothed-energy guidance needs at least one attention block")
+        if s > 0.0 and float(pag_scale) > 0.0:
+            raise ValueError("seg_scale > 0 cannot be combined with pag_scale > 0: the loop carries one perturbed plane")
+        if s > 0.0 and float(guidance_rescale) > 0.0:
+            raise ValueError("seg_scale > 0 cannot be combined with guidance_rescale > 0: the rescale would need its statistics taken over the "
+                             "SEG-guided output")
+        if s > 0.0 and apg:
+            raise ValueError("seg_scale > 0 cannot be combined with apg=True: APG's statistics would have to be taken over the SEG-guided output")
+        return s, sigma, names
 
     @staticmethod
     def _check_kv_downsample(kv_downsample, kv_downsample_mode, h, w):
@@ -660,7 +708,7 @@ class MikuDanceVideoPipeline:
                  context_fuse="flat", free_init_iters=1, free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25,
                  free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0,
                  pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), kv_downsample=1,
-                 kv_downsample_mode="nearest", **kwargs):
+                 kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -692,6 +740,11 @@ class MikuDanceVideoPipeline:
         if any(s > 1 for s in kv_factors):
             self.denoising_unet.kv_downsample_plan(kv_factors, kv_mode)
         kv_kw = dict(kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode)
+        # seg_*: smoothed-energy guidance (denoise()); checked here too, and a name that selects no block raises before CLIP / VAE run
+        seg_s, _, seg_names = self._check_seg(seg_scale, seg_blur_sigma, seg_applied_layers, pag_scale, guidance_rescale, apg)
+        if seg_s > 0.0:
+            self.denoising_unet.pag_blocks(seg_names, "seg_applied_layers", "smoothed-energy guidance")
+        seg_kw = dict(seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers)
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -726,7 +779,7 @@ class MikuDanceVideoPipeline:
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
                                context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
                                guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength,
-                               context_fuse=context_fuse, **fi_kw, **apg_kw, **pag_kw, **kv_kw)
+                               context_fuse=context_fuse, **fi_kw, **apg_kw, **pag_kw, **kv_kw, **seg_kw)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)

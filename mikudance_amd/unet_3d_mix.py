@@ -263,21 +263,22 @@ class _UNetBase(_Packed):
         mid = [(f"mid_block.attentions.{j}", a.transformer_blocks[0]) for j, a in enumerate(self.mid_block.attentions)]
         return out[:nd] + mid + out[nd:]
 
-    def pag_blocks(self, applied_layers):
+    def pag_blocks(self, applied_layers, what="pag_applied_layers", feature="perturbed-attention guidance"):
         """The TransformerBlocks that `pag_applied_layers` selects (perturbed-attention guidance, diffusers PAGMixin.set_pag_applied_layers
         restricted to the names of this model): "mid_block" (alias "mid"), "down_blocks.I", "up_blocks.I", "down_blocks.I.attentions.J",
         "up_blocks.I.attentions.J".  A block is selected when its key prefix equals a name or starts with name + ".".  An empty sequence
-        and a name that selects no block raise ValueError."""
-        names = check_pag_layer_names(applied_layers)
+        and a name that selects no block raise ValueError.  Smoothed-energy guidance selects its blocks the same way: `what` / `feature` are the
+        keyword and the feature that the error messages name."""
+        names = check_pag_layer_names(applied_layers, what)
         if not names:
-            raise ValueError("pag_applied_layers is empty: perturbed-attention guidance needs at least one attention block")
+            raise ValueError(f"{what} is empty: {feature} needs at least one attention block")
         blocks = self.attention_block_prefixes()
         picked = []
         for name in names:
             key = "mid_block" if name == "mid" else name
             hit = [b for p, b in blocks if p == key or p.startswith(key + ".")]
             if not hit:
-                raise ValueError(f"pag_applied_layers: {name!r} selects no attention block of this UNet (its blocks: "
+                raise ValueError(f"{what}: {name!r} selects no attention block of this UNet (its blocks: "
                                  f"{', '.join(p for p, _ in blocks)})")
             picked += [b for b in hit if not any(b is q for q in picked)]
         return tuple(picked)
@@ -326,18 +327,18 @@ class _UNetBase(_Packed):
 _PAG_NAME = re.compile(r"^(mid|mid_block|(down|up)_blocks\.\d+(\.attentions\.\d+)?)$")
 
 
-def check_pag_layer_names(applied_layers):
-    """pag_applied_layers as a tuple of names of the forms UNet3DConditionModel.pag_blocks documents; anything else raises ValueError.
+def check_pag_layer_names(applied_layers, what="pag_applied_layers"):
+    """pag_applied_layers (or the keyword `what` names) as a tuple of names of the forms UNet3DConditionModel.pag_blocks documents; anything else raises ValueError.
     Needs no model: the pipeline calls it before anything runs."""
     if isinstance(applied_layers, str):
         applied_layers = (applied_layers,)
     try:
         names = tuple(applied_layers)
     except TypeError:
-        raise ValueError(f"pag_applied_layers must be a sequence of layer names, got {applied_layers!r}") from None
+        raise ValueError(f"{what} must be a sequence of layer names, got {applied_layers!r}") from None
     for name in names:
         if not isinstance(name, str) or not _PAG_NAME.match(name):
-            raise ValueError(f"pag_applied_layers: unknown layer name {name!r}; the forms are 'mid_block' (or 'mid'), 'down_blocks.I', "
+            raise ValueError(f"{what}: unknown layer name {name!r}; the forms are 'mid_block' (or 'mid'), 'down_blocks.I', "
                              "'up_blocks.I', 'down_blocks.I.attentions.J', 'up_blocks.I.attentions.J'")
     return names
 
@@ -423,8 +424,12 @@ class UNet3DConditionModel(_UNetBase):
         self._build(in_channels, tuple(block_out_channels), cross_attention_dim, norm_eps, flags, mm_kwargs, with_out=True)
 
     # ------------------------------------------------------------------------------------------ internal NHWC forward
-    def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None, kv_downsample=None):
+    def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None, kv_downsample=None, seg=None):
         """x: (nb*f, h, w, 64) fp16 (4 latent channels, zero padded); returns pred tokens [(nb*f*h*w), 4].
+        seg: None, or (blocks, sigma) with the blocks of pag_blocks(): this call is then the perturbed evaluation of smoothed-energy guidance
+        (SEG, arXiv 2408.00760), a call of its own like pag= and with the same conditions; in the selected blocks the self-attention QUERIES are
+        blurred over the block's own token grid (sigma: a positive float, or math.inf for the mean query; TransformerBlock.forward(seg=)).
+        Not together with pag.
         kv_downsample: None, or the plan of kv_downsample_plan(): the spatial transformers it names compute their self-attention K / V from the
         downsampled token grid (SpatialTransformer.forward(kv_pool=)), on one queue and on two, in the main and in a perturbed evaluation.
         pag: None, or the blocks of pag_blocks(): this call is then the PERTURBED evaluation of perturbed-attention guidance (arXiv 2403.17377), a
@@ -438,8 +443,11 @@ class UNet3DConditionModel(_UNetBase):
         two_queues (with halves_identical): behind those shared layers the unconditional and the conditional half are independent all the way
         to the output (per-image GroupNorm, per-row attention and LayerNorm, per-clip-half temporal attention: src/models/unet_3d_mix.py:
         418-598, src/models/mutual_mix_attention.py:173-201), and they are evaluated as TWO KERNEL QUEUES (_forward_two_queues)."""
-        if pag is not None and (nb != 1 or two_queues or halves_identical):
-            raise ValueError("forward_nhwc: the perturbed evaluation (pag=) is one clip-half on one queue: nb == 1, no two_queues, no halves_identical")
+        if pag is not None and seg is not None:
+            raise ValueError("forward_nhwc: pag= and seg= are two perturbations of one evaluation: give one of them")
+        if (pag is not None or seg is not None) and (nb != 1 or two_queues or halves_identical):
+            raise ValueError(f"forward_nhwc: the perturbed evaluation ({'pag' if seg is None else 'seg'}=) is one clip-half on one queue: "
+                             "nb == 1, no two_queues, no halves_identical")
         pk = self.packed()
         dev = x.device
         _, hh, ww, _ = x.shape
@@ -471,12 +479,12 @@ class UNet3DConditionModel(_UNetBase):
                 first = dst
         else:
             x = ops.conv3x3(x, pk["cin"], c0, bias=pk["cinb"], out=skips.slot(B, hh, ww, c0, dev))
-        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, first, pag=pag, kv_downsample=kv_downsample))
+        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, first, pag=pag, kv_downsample=kv_downsample, seg=seg))
 
-    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, first=None, out=None, pag=None, kv_downsample=None):
+    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, first=None, out=None, pag=None, kv_downsample=None, seg=None):
         """Everything behind conv_in.  x: conv_in's output (nb*f, h, w, C0), already in its skip slot; `first`: the first resnet's output when
-        the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes, (nb*f, h, w, 4); `pag`, `kv_downsample`:
-        see forward_nhwc."""
+        the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes, (nb*f, h, w, 4); `pag`, `kv_downsample`,
+        `seg`: see forward_nhwc."""
         kvp = (lambda a: None) if kv_downsample is None else kv_downsample.get
         dev = x.device
         B = x.shape[0]
@@ -493,14 +501,14 @@ class UNet3DConditionModel(_UNetBase):
                 if not last_op and first is not None and bi == 0 and j == 0:
                     dst = skips.slot(B, H_, W_, r.cout, dev)
                 if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag, kv_pool=kvp(blk.attentions[j]))
+                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag, kv_pool=kvp(blk.attentions[j]), seg=seg)
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
             if blk.downsamplers is not None:
                 x = blk.downsamplers[0](x, out=skips.slot(B, (x.shape[1] + 1) // 2, (x.shape[2] + 1) // 2, blk.downsamplers[0].c, dev))
         mb = self.mid_block
         x = mb.resnets[0](x, self._temb(pk, trows, mb.resnets[0]), f * x.shape[1] * x.shape[2], gf)
-        x = mb.attentions[0](x, cross, pag=pag, kv_pool=kvp(mb.attentions[0]))
+        x = mb.attentions[0](x, cross, pag=pag, kv_pool=kvp(mb.attentions[0]), seg=seg)
         if mb.motion_modules[0] is not None:
             x = mb.motion_modules[0](x, nb, f)
         x = mb.resnets[1](x, self._temb(pk, trows, mb.resnets[1]), f * x.shape[1] * x.shape[2], gf, out=skips.hidden_slot())
@@ -514,7 +522,7 @@ class UNet3DConditionModel(_UNetBase):
                 dst = skips.hidden_slot() if len(skips) and not (last and blk.upsamplers is not None) else None
                 x = r(x, self._temb(pk, trows, r), f * H_ * W_, gf, out=None if (blk.has_cross_attention or mm is not None) else dst)
                 if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag, kv_pool=kvp(blk.attentions[j]))
+                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag, kv_pool=kvp(blk.attentions[j]), seg=seg)
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
             if blk.upsamplers is not None:
