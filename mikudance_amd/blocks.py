@@ -7,6 +7,8 @@ Activation convention: a (B, H, W, C) fp16 contiguous tensor; its 2-D view [B*H*
 reference's NCHW<->token shuffles (src/models/transformer_3d.py:121,134-136,185-189,201;
 src/models/motion_module.py:159,166-168,182-189,404-406,437) do not exist here.
 """
+from dataclasses import dataclass
+
 import torch
 from torch import nn
 
@@ -244,12 +246,44 @@ class CrossContext:
 
 ZERO_CONTEXT_SKIP = True     # tests switch this off to compare against the literal evaluation
 
-# Which clip-half of a classifier-free-guidance batch the CURRENT call evaluates when the two halves run as two kernel queues
-# (UNet3DConditionModel.forward_nhwc, two_queues): None = the whole batch (rows [0, M/2) unconditional, the rest conditional);
-# 0 = unconditional rows only (the bank is ignored: reference src/models/mutual_mix_attention.py:181-201);
-# 1 = conditional rows only (every row reads the bank).  Set and reset by the UNet around each half's launches: the host enqueues
-# the two halves one after the other (one Python thread), only the GPU runs them side by side.
-CHAIN = None
+
+@dataclass(frozen=True)
+class SelfAttnCall:
+    """How the spatial self-attention of ONE UNet call differs from the plain one; handed unchanged to every TransformerBlock of the call.
+    half: which rows of a classifier-free-guidance batch the call holds.  None: the whole batch (rows [0, M/2) unconditional, the rest
+      conditional); 0: the unconditional rows only (the bank is ignored: reference src/models/mutual_mix_attention.py:181-201); 1: the
+      conditional rows only (every row reads the bank).  0 / 1 are the two kernel queues of UNet3DConditionModel._forward_two_queues.
+    identity: None, or the TransformerBlocks whose attention map softmax(q k^T d^-1/2) is the identity (perturbed-attention guidance, Ahn et
+      al., arXiv 2403.17377; diffusers PAGIdentitySelfAttnProcessor2_0): attn1(x) = to_out(to_v(norm1(x) + bank)) + x, no q, no k, no
+      attention launch, V row-major.
+    blur: None, or (blocks, sigma): the TransformerBlocks whose QUERIES are blurred over the token grid (smoothed-energy guidance, Hong, arXiv
+      2408.00760): q = to_q(norm1(x)) goes through ops.token_blur (sigma a positive float: Gaussian with reflect padding; math.inf: the
+      frame's mean query; channel-wise, so the head split needs no handling); K, V and the attention launch are unchanged.
+    Either of the two makes this a PERTURBED evaluation, a call of its own beside the main one: all rows are conditional rows and read the
+    bank, with or without ref_cfg (half = 1's meaning, so half stays None), and no block may be in write mode.  A block that is not selected
+    issues the conditional half's calls.
+    pool: None, or {TransformerBlock: (s, mode)}: token downsampling of the self-attention K / V (ToDo, Smith et al., arXiv 2402.13573).  q
+      keeps every token; the K / V source -- norm1(x), or norm1(x) + bank on the rows that read the bank, pooled AFTER the add -- goes through
+      ops.token_pool (s per axis, mode "nearest" or "mean") in front of to_k / to_v, and the attention runs with Lk = (Hh // s) * (Ww // s)
+      keys at kv_stride = roundup8(Lk).  The bank written is the full-resolution norm1(x).  An identity map has no attention to shorten: no
+      effect there."""
+    half: int = None
+    identity: tuple = None
+    blur: tuple = None
+    pool: dict = None
+
+    def __post_init__(self):
+        if self.identity is not None and self.blur is not None:
+            raise ValueError("SelfAttnCall: pag and seg are two perturbations of one evaluation: give one of them")
+        if self.perturbed and self.half is not None:
+            raise ValueError("SelfAttnCall: a perturbed evaluation is a call of its own: not one clip-half of a two-queue call")
+
+    @property
+    def perturbed(self):
+        return self.identity is not None or self.blur is not None
+
+
+PLAIN = SelfAttnCall()
 
 
 class TransformerBlock(_Packed):
@@ -297,90 +331,56 @@ class TransformerBlock(_Packed):
             self._kv_cache = (cross.root, ops.gemm(cross.ctx, pk["k2"]), ops.gemm(cross.ctx, pk["v2"], transpose_out=True), {})
         return self._kv_cache[1:]
 
-    def forward(self, h, B, L, cross, pag=None, kv_pool=None, seg=None):
-        """h: [B*L, C] tokens.  Returns tokens.
-        seg: None, or (blocks, Hh, Ww, sigma) with Hh * Ww == L: smoothed-energy guidance (SEG, Hong, arXiv 2408.00760).  Not None has pag's
-        meaning -- ALL rows of h are a perturbed CONDITIONAL evaluation, every row reads the bank -- with pag's refusals, and in a block that is
-        in `blocks` the QUERIES are blurred over the token grid: q = to_q(norm1(x)) from the q-only GEMM goes through ops.token_blur (sigma a
-        positive float: Gaussian with reflect padding; math.inf: the frame's mean query; channel-wise, so the head split needs no handling),
-        K and V come unblurred from norm1(x) + bank, and the attention launch and everything behind it are unchanged; kv_pool still shortens
-        K / V there.  A block that is not in `blocks` issues the conditional half's calls.  Not together with pag.
-        kv_pool: None, or (Hh, Ww, s, mode) with Hh * Ww == L: token downsampling of the self-attention K / V (ToDo, Smith et al., arXiv
-        2402.13573).  q = to_q(norm1(x)) keeps every token; the K / V source -- norm1(x), or norm1(x) + bank on the rows that read the bank,
-        pooled AFTER the add -- goes through ops.token_pool (s per axis, mode "nearest" or "mean") in front of to_k / to_v, and the attention
-        runs with Lk = (Hh // s) * (Ww // s) keys at kv_stride = roundup8(Lk).  The bank written is the full-resolution norm1(x).  A block whose
-        self-attention is perturbed has no attention to shorten: kv_pool has no effect there.  None: exactly the operator calls below.
-        pag: None, or the collection of TransformerBlocks whose self-attention is perturbed (perturbed-attention guidance, Ahn et al.,
-        arXiv 2403.17377; diffusers PAGIdentitySelfAttnProcessor2_0).  Not None says that ALL rows of h are a perturbed CONDITIONAL evaluation:
-        every row reads the bank (the conditional-only read below, with or without ref_cfg), and in a block that is in `pag` the attention map
-        softmax(q k^T d^-1/2) is the identity, attn1(x) = to_out(to_v(norm1(x) + bank)) + x: no q, no k, no attention launch, V row-major."""
+    def forward(self, h, B, L, cross, sa=PLAIN, grid=None):
+        """h: [B*L, C] tokens.  Returns tokens.  sa: the call's SelfAttnCall; grid: (Hh, Ww) of the L tokens, for a block that pools or blurs."""
         pk = self.packed()
         C, H = self.dim, self.heads
         D = C // H
-        if pag is not None and seg is not None:
-            raise ValueError("TransformerBlock: pag and seg are two perturbations of one evaluation: give one of them")
-        if (pag is not None or seg is not None) and (CHAIN is not None or self.ref_mode == "write"):
-            raise ValueError("TransformerBlock: a perturbed evaluation is a call of its own: not one clip-half of a two-queue call, not a bank write")
-        perturbed = pag is not None and any(self is b for b in pag)
-        blur = seg is not None and any(self is b for b in seg[0])
-        if blur and seg[1] * seg[2] != L:
-            raise ValueError(f"TransformerBlock: seg grid {seg[1]} x {seg[2]} does not hold L = {L} tokens")
-        pool = kv_pool is not None and not perturbed
-        if pool and kv_pool[0] * kv_pool[1] != L:
-            raise ValueError(f"TransformerBlock: kv_pool grid {kv_pool[0]} x {kv_pool[1]} does not hold L = {L} tokens")
-        if self.ref_mode == "read" and len(self.bank) == 1 and not (self.ref_cfg and CHAIN == 0):
-            bank = self.bank[0]
-            brows = bank.shape[0] * bank.shape[1] if bank.dim() == 3 else bank.shape[0]
-            M = h.shape[0]
-            if pag is not None or seg is not None or (self.ref_cfg and CHAIN == 1):
-                # the conditional half on its own: every row reads the bank (the conditional frames' part of a literal 2f-frame bank)
-                begin, b2 = 0, bank.reshape(-1, C)
-                if brows == 2 * M:
-                    b2 = b2[M:]
-                assert b2.shape[0] == M, (b2.shape, M)
-            elif self.ref_cfg:
-                # unconditional rows (first half) ignore the bank (mutual_mix_attention.py:181-201)
-                begin = M // 2
-                b2 = bank.reshape(-1, C)
-                if brows == M:
-                    b2 = b2[begin:]
-                assert b2.shape[0] == M - begin, (b2.shape, M)
-            else:
-                begin, b2 = 0, bank.reshape(-1, C)
-                assert b2.shape[0] == M
-            n, kv = ops.layernorm(h, pk["n1w"], pk["n1b"], add=b2.contiguous(), add_mode=1, add_row_begin=begin)
-            if not perturbed:
-                q = ops.gemm(n, pk["q1"])
-                if not pool:
-                    k = ops.gemm(kv, pk["k1"])
-                    vt = ops.gemm(kv, pk["v1"], transpose_out=True)
+        if sa.perturbed and self.ref_mode == "write":
+            raise ValueError("TransformerBlock: a perturbed evaluation is a call of its own: not a bank write")
+        identity = sa.identity is not None and any(self is b for b in sa.identity)
+        sigma = sa.blur[1] if sa.blur is not None and any(self is b for b in sa.blur[0]) else None
+        pool = None if sa.pool is None or identity else sa.pool.get(self)
+        if (sigma is not None or pool is not None) and (grid is None or grid[0] * grid[1] != L):
+            raise ValueError(f"TransformerBlock: grid {grid} does not hold L = {L} tokens")
+        # 1. source: n = norm1(x) feeds q, kv feeds k and v; rows [begin, M) read the bank (kv = n + bank there), None: no row does
+        M = h.shape[0]
+        if self.ref_mode != "read" or len(self.bank) != 1 or (self.ref_cfg and sa.half == 0):
+            begin = None
+        elif sa.perturbed or sa.half == 1 or not self.ref_cfg:
+            begin = 0
         else:
+            begin = M // 2                                               # the unconditional rows (first half) ignore the bank
+        if begin is None:
             n = kv = ops.layernorm(h, pk["n1w"], pk["n1b"])
             if self.ref_mode == "write":
                 self.bank.append(n.view(B, L, C))
                 if self.stop_after_bank:
                     return h
-            if pool:
-                q = ops.gemm(n, pk["q1"])                                # q alone: the fused q|k GEMM has no k to make here
-            elif blur:
-                q = ops.gemm(n, pk["q1"])                                # q alone and contiguous: it goes through the blur
-                k = ops.gemm(kv, pk["k1"])
-                vt = ops.gemm(kv, pk["v1"], transpose_out=True)
-            elif not perturbed:
-                qk = ops.gemm(n, pk["qk1"])
-                q, k = qk[:, :C], qk[:, C:]
-                vt = ops.gemm(n, pk["v1"], transpose_out=True)
-        if blur:
-            q = ops.token_blur(q, B, seg[1], seg[2], seg[3])
-        if pool:
-            # K / V from the downsampled grid (its pad rows are zeros and to_k / to_v have no bias: zero K rows, zero V^T columns)
-            kvp, Lk, stride = ops.token_pool(kv, B, kv_pool[0], kv_pool[1], kv_pool[2], kv_pool[3])
-            k = ops.gemm(kvp, pk["k1"])
-            vt = ops.gemm(kvp, pk["v1"], transpose_out=True)
-            a = ops.attention(q, k, vt, B, H, D, L, Lk, kv_stride=stride)
         else:
-            # identity attention map: every query row takes its own V row
-            a = ops.gemm(kv, pk["v1"]) if perturbed else ops.attention(q, k, vt, B, H, D, L, L)
+            b2 = self.bank[0].reshape(-1, C)
+            if (self.ref_cfg or sa.perturbed) and b2.shape[0] == 2 * (M - begin):
+                b2 = b2[M - begin:]                                      # a literal bank of both halves' frames: the conditional frames' part
+            assert b2.shape[0] == M - begin, (b2.shape, M)
+            n, kv = ops.layernorm(h, pk["n1w"], pk["n1b"], add=b2.contiguous(), add_mode=1, add_row_begin=begin)
+        if identity:
+            # 2. no q, no k;  3. identity attention map: every query row takes its own V row
+            a = ops.gemm(kv, pk["v1"])
+        else:
+            # 2. projections: q from n (blurred where selected), k and v^T from kv or from its downsampled grid
+            if n is kv and pool is None and sigma is None:
+                qk = ops.gemm(n, pk["qk1"])
+                q, k, src, Lk, stride = qk[:, :C], qk[:, C:], kv, L, None
+            else:
+                q = ops.gemm(n, pk["q1"])                                # q alone and contiguous: k is not made from n, or q goes through the blur
+                if sigma is not None:
+                    q = ops.token_blur(q, B, grid[0], grid[1], sigma)
+                # (the pooled grid's pad rows are zeros and to_k / to_v have no bias: zero K rows, zero V^T columns)
+                src, Lk, stride = (kv, L, None) if pool is None else ops.token_pool(kv, B, grid[0], grid[1], pool[0], pool[1])
+                k = ops.gemm(src, pk["k1"])
+            vt = ops.gemm(src, pk["v1"], transpose_out=True)
+            # 3. attention
+            a = ops.attention(q, k, vt, B, H, D, L, Lk, kv_stride=stride)
         kv2 = self.context_kv(cross)
         zf = min(cross.zero_frames, B) if ZERO_CONTEXT_SKIP else 0
         if zf:
@@ -420,25 +420,13 @@ class SpatialTransformer(_Packed):
                     pi=packing.conv1x1_weight(self.proj_in.weight, dev), pib=packing.vec(self.proj_in.bias, dev),
                     po=packing.conv1x1_weight(self.proj_out.weight, dev), pob=packing.vec(self.proj_out.bias, dev))
 
-    def forward(self, x, cross, out=None, pag=None, kv_pool=None, seg=None):
-        """pag: handed on to the block (TransformerBlock.forward); None everywhere but in a perturbed evaluation.
-        seg: None, or (blocks, sigma) -- or (blocks, Hh, Ww, sigma) with this tensor's own grid: smoothed-energy guidance, handed on to the
-        block as (blocks, Hh, Ww, sigma) (the block only knows L).
-        kv_pool: None, or (s, mode) -- or (Hh, Ww, s, mode) with this tensor's own grid: K / V token downsampling, handed on to the block as
-        (Hh, Ww, s, mode) (the block only knows L)."""
+    def forward(self, x, cross, out=None, sa=PLAIN):
+        """sa: the call's SelfAttnCall, handed on to the block with this tensor's token grid."""
         pk = self.packed()
         B, Hh, Ww, C = x.shape
         blk = self.transformer_blocks[0]
         h = gn_linear(x, pk["nw"], pk["nb"], 1e-6, pk["pi"], pk["pib"])
-        if kv_pool is not None:
-            if len(kv_pool) == 4 and tuple(kv_pool[:2]) != (Hh, Ww):
-                raise ValueError(f"SpatialTransformer: kv_pool grid {tuple(kv_pool[:2])} is not this tensor's {Hh} x {Ww}")
-            kv_pool = (Hh, Ww) + tuple(kv_pool[-2:])
-        if seg is not None:
-            if len(seg) == 4 and tuple(seg[1:3]) != (Hh, Ww):
-                raise ValueError(f"SpatialTransformer: seg grid {tuple(seg[1:3])} is not this tensor's {Hh} x {Ww}")
-            seg = (seg[0], Hh, Ww, seg[-1])
-        h = blk(h, B, Hh * Ww, cross, pag=pag, kv_pool=kv_pool, seg=seg)
+        h = blk(h, B, Hh * Ww, cross, sa=sa, grid=(Hh, Ww))
         if blk.ref_mode == "write" and blk.stop_after_bank:
             return x
         if out is not None:

@@ -7,7 +7,7 @@ Internally frames are folded into the batch and everything runs NHWC fp16 on the
 """
 import json
 import re
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from pathlib import Path
 from typing import Optional
 
@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, packing
-from .blocks import (Affine, Conv, ConvSampler, CrossContext, MotionModule, ResnetBlock, SpatialTransformer,
+from .blocks import (Affine, Conv, ConvSampler, CrossContext, MotionModule, ResnetBlock, SelfAttnCall, SpatialTransformer,
                      TimestepEmbedding, _Packed, groupnorm_frames, timestep_sinusoid, tokens)
 
 
@@ -426,16 +426,12 @@ class UNet3DConditionModel(_UNetBase):
     # ------------------------------------------------------------------------------------------ internal NHWC forward
     def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None, kv_downsample=None, seg=None):
         """x: (nb*f, h, w, 64) fp16 (4 latent channels, zero padded); returns pred tokens [(nb*f*h*w), 4].
-        seg: None, or (blocks, sigma) with the blocks of pag_blocks(): this call is then the perturbed evaluation of smoothed-energy guidance
-        (SEG, arXiv 2408.00760), a call of its own like pag= and with the same conditions; in the selected blocks the self-attention QUERIES are
-        blurred over the block's own token grid (sigma: a positive float, or math.inf for the mean query; TransformerBlock.forward(seg=)).
-        Not together with pag.
-        kv_downsample: None, or the plan of kv_downsample_plan(): the spatial transformers it names compute their self-attention K / V from the
-        downsampled token grid (SpatialTransformer.forward(kv_pool=)), on one queue and on two, in the main and in a perturbed evaluation.
-        pag: None, or the blocks of pag_blocks(): this call is then the PERTURBED evaluation of perturbed-attention guidance (arXiv 2403.17377), a
-        call of its own beside the main one: nb must be 1, x the conditional frames, cross their context (the main call's context or its
-        rows(f, 2f): the cached K / V projections are shared, nothing of the main call is touched).  Every row reads the bank, and the selected
-        blocks' self-attention map is the identity (TransformerBlock.forward).  Not with two_queues: one clip-half has nothing to run beside.
+        pag: None, or the blocks of pag_blocks(): this call is then the PERTURBED evaluation of perturbed-attention guidance, a call of its own
+        beside the main one: nb must be 1, x the conditional frames, cross their context (the main call's context or its rows(f, 2f): the
+        cached K / V projections are shared, nothing of the main call is touched).  Not with two_queues: one clip-half has nothing to run beside.
+        seg: None, or (blocks, sigma) with the blocks of pag_blocks(): the perturbed evaluation of smoothed-energy guidance, under pag's conditions.
+        kv_downsample: None, or the plan of kv_downsample_plan(): K / V token downsampling in the spatial transformers it names.
+        What each does in the blocks: blocks.SelfAttnCall, which carries the three through this call.
         halves_identical: the caller GUARANTEES that the two clip-halves of x hold the same latents (classifier-free guidance: the loop of
         src/pipelines/pipeline_mikudance.py:626-633 feeds `torch.cat([latents] * 2)`) -- with equal timesteps, conv_in and the first resnet
         (no attention in front of them: nothing has seen the context or the bank yet) then produce the same tensor for both halves, so
@@ -443,9 +439,8 @@ class UNet3DConditionModel(_UNetBase):
         two_queues (with halves_identical): behind those shared layers the unconditional and the conditional half are independent all the way
         to the output (per-image GroupNorm, per-row attention and LayerNorm, per-clip-half temporal attention: src/models/unet_3d_mix.py:
         418-598, src/models/mutual_mix_attention.py:173-201), and they are evaluated as TWO KERNEL QUEUES (_forward_two_queues)."""
-        if pag is not None and seg is not None:
-            raise ValueError("forward_nhwc: pag= and seg= are two perturbations of one evaluation: give one of them")
-        if (pag is not None or seg is not None) and (nb != 1 or two_queues or halves_identical):
+        sa = SelfAttnCall(identity=pag, blur=seg, pool=kv_downsample and {st.transformer_blocks[0]: sm for st, sm in kv_downsample.items()})
+        if sa.perturbed and (nb != 1 or two_queues or halves_identical):
             raise ValueError(f"forward_nhwc: the perturbed evaluation ({'pag' if seg is None else 'seg'}=) is one clip-half on one queue: "
                              "nb == 1, no two_queues, no halves_identical")
         pk = self.packed()
@@ -460,7 +455,7 @@ class UNet3DConditionModel(_UNetBase):
         share = bool(halves_identical and nb == 2 and float(tt[0]) == float(tt[-1]))
         b0 = self.down_blocks[0]
         if share and two_queues and x.is_cuda and (b0.has_cross_attention or b0.motion_modules[0] is not None):
-            return self._forward_two_queues(x, f, trows, cross, pk, gf, force_size, kv_downsample=kv_downsample)
+            return self._forward_two_queues(x, f, trows, cross, pk, gf, force_size, sa)
         skips = _Skips(self._skip_plan())
         first = None
         if share:
@@ -479,13 +474,12 @@ class UNet3DConditionModel(_UNetBase):
                 first = dst
         else:
             x = ops.conv3x3(x, pk["cin"], c0, bias=pk["cinb"], out=skips.slot(B, hh, ww, c0, dev))
-        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, first, pag=pag, kv_downsample=kv_downsample, seg=seg))
+        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first))
 
-    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, first=None, out=None, pag=None, kv_downsample=None, seg=None):
-        """Everything behind conv_in.  x: conv_in's output (nb*f, h, w, C0), already in its skip slot; `first`: the first resnet's output when
-        the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes, (nb*f, h, w, 4); `pag`, `kv_downsample`,
-        `seg`: see forward_nhwc."""
-        kvp = (lambda a: None) if kv_downsample is None else kv_downsample.get
+    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first=None, out=None):
+        """Everything behind conv_in.  x: conv_in's output (nb*f, h, w, C0), already in its skip slot; `sa`: the call's blocks.SelfAttnCall;
+        `first`: the first resnet's output when the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes,
+        (nb*f, h, w, 4)."""
         dev = x.device
         B = x.shape[0]
         for bi, blk in enumerate(self.down_blocks):
@@ -501,14 +495,14 @@ class UNet3DConditionModel(_UNetBase):
                 if not last_op and first is not None and bi == 0 and j == 0:
                     dst = skips.slot(B, H_, W_, r.cout, dev)
                 if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag, kv_pool=kvp(blk.attentions[j]), seg=seg)
+                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, sa=sa)
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
             if blk.downsamplers is not None:
                 x = blk.downsamplers[0](x, out=skips.slot(B, (x.shape[1] + 1) // 2, (x.shape[2] + 1) // 2, blk.downsamplers[0].c, dev))
         mb = self.mid_block
         x = mb.resnets[0](x, self._temb(pk, trows, mb.resnets[0]), f * x.shape[1] * x.shape[2], gf)
-        x = mb.attentions[0](x, cross, pag=pag, kv_pool=kvp(mb.attentions[0]), seg=seg)
+        x = mb.attentions[0](x, cross, sa=sa)
         if mb.motion_modules[0] is not None:
             x = mb.motion_modules[0](x, nb, f)
         x = mb.resnets[1](x, self._temb(pk, trows, mb.resnets[1]), f * x.shape[1] * x.shape[2], gf, out=skips.hidden_slot())
@@ -522,7 +516,7 @@ class UNet3DConditionModel(_UNetBase):
                 dst = skips.hidden_slot() if len(skips) and not (last and blk.upsamplers is not None) else None
                 x = r(x, self._temb(pk, trows, r), f * H_ * W_, gf, out=None if (blk.has_cross_attention or mm is not None) else dst)
                 if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, pag=pag, kv_pool=kvp(blk.attentions[j]), seg=seg)
+                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, sa=sa)
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
             if blk.upsamplers is not None:
@@ -530,7 +524,7 @@ class UNet3DConditionModel(_UNetBase):
         x = groupnorm_frames(x, pk["ow"], pk["ob"], self.norm_eps, True, gf)
         return ops.conv3x3(x, pk["co"], 4, bias=pk["cob"], out=out)
 
-    def _forward_two_queues(self, x, f, trows, cross, pk, gf, force_size, kv_downsample=None):
+    def _forward_two_queues(self, x, f, trows, cross, pk, gf, force_size, sa):
         """The two clip-halves of a classifier-free-guidance batch as two kernel queues (stage B, without CU masks).
 
         One queue of B = 2f kernels leaves the chip idle wherever a launch cannot fill it -- partial last rounds of the persistent GEMM / conv
@@ -539,8 +533,8 @@ class UNet3DConditionModel(_UNetBase):
         same launches back to back).  Layout of one call:
           calling stream : time rows, conv_in and the first resnet on ONE half (shared: halves_identical); the cross-attention K / V of every
                            block if this context is new (they are read by both queues); fork event
-          queue 0        : the unconditional half -- blocks.CHAIN = 0: no bank, zero-context rows (the to_out bias as a row term)
-          queue 1        : the conditional half   -- blocks.CHAIN = 1: every row reads the bank and the CLIP tokens
+          queue 0        : the unconditional half -- sa.half = 0: no bank, zero-context rows (the to_out bias as a row term)
+          queue 1        : the conditional half   -- sa.half = 1: every row reads the bank and the CLIP tokens
           calling stream : waits for both; the prediction of both halves sits in ONE buffer allocated before the fork.
         One Python thread enqueues queue 0, then queue 1 (the host runs several steps ahead of the GPU either way).  Memory: everything a queue
         allocates comes from that stream's pool of the caching allocator; the few tensors that cross streams (first-resnet output, time rows, the
@@ -551,7 +545,6 @@ class UNet3DConditionModel(_UNetBase):
         Results: each half goes through the same kernels with B = f instead of B = 2f; where the tile dispatch picks another flavour for the
         smaller problem the fp32 summation order differs (bits may differ from the one-queue evaluation, error against fp32 is the same:
         tests/test_two_queues_gpu.py); run to run the two-queue evaluation is bitwise reproducible (no atomics, no order dependence)."""
-        from . import blocks
         dev = x.device
         _, hh, ww, _ = x.shape
         c0 = self.conv_in.weight.shape[0]
@@ -579,12 +572,8 @@ class UNet3DConditionModel(_UNetBase):
                         qs[1].wait_event(done[0])
                     slot1 = sk[1].slot(f, hh, ww, c0, dev)
                     slot1.copy_(slot0)
-                blocks.CHAIN = c
-                try:
-                    self._body(slot0 if c == 0 else slot1, sk[c], 1, f, trows[c:c + 1], cross.rows(c * f, (c + 1) * f), pk, gf, force_size,
-                               first=first, out=pred[c * f:(c + 1) * f], kv_downsample=kv_downsample)
-                finally:
-                    blocks.CHAIN = None
+                self._body(slot0 if c == 0 else slot1, sk[c], 1, f, trows[c:c + 1], cross.rows(c * f, (c + 1) * f), pk, gf, force_size,
+                           replace(sa, half=c), first=first, out=pred[c * f:(c + 1) * f])
                 ev = torch.cuda.Event()
                 ev.record(qs[c])
                 done.append(ev)

@@ -11,6 +11,7 @@ import torch
 import torch.distributed as dist
 
 import mikudance_amd as M
+from mikudance_amd import blocks
 from mikudance_amd.selftest import SCHED_KWARGS
 from oracle import cpu_ref as O
 
@@ -225,7 +226,7 @@ def test_block_refuses_a_grid_that_is_not_its_token_count(monkeypatch):
     T.install(monkeypatch)
     st = T.block_setup(64, 64, 4, 4, 1, torch.device("cpu"))
     with pytest.raises(ValueError, match="does not hold L = 16"):
-        st.blk(st.x.reshape(-1, 64), 2, 16, st.cross, kv_pool=(4, 5, 2, "nearest"))
+        st.blk(st.x.reshape(-1, 64), 2, 16, st.cross, sa=blocks.SelfAttnCall(pool={st.blk: (2, "nearest")}), grid=(4, 5))
 
 
 def test_perturbed_block_ignores_kv_pool(monkeypatch):
@@ -234,14 +235,14 @@ def test_perturbed_block_ignores_kv_pool(monkeypatch):
     blk = st.blk
     blk.ref_mode, blk.ref_cfg, blk.bank = "read", True, [st.bank]
     h = st.x[1:].reshape(-1, 64)
-    blk(h.clone(), 1, 16, st.cross.rows(1, 2), pag=(blk,))                 # first call: projects the context K / V
+    blk(h.clone(), 1, 16, st.cross.rows(1, 2), sa=blocks.SelfAttnCall(identity=(blk,)))                 # first call: projects the context K / V
     del fake_ops.CALLS[:]
-    a = blk(h.clone(), 1, 16, st.cross.rows(1, 2), pag=(blk,))
+    a = blk(h.clone(), 1, 16, st.cross.rows(1, 2), sa=blocks.SelfAttnCall(identity=(blk,)))
     log = list(fake_ops.CALLS)
     del fake_ops.CALLS[:]
-    b = blk(h.clone(), 1, 16, st.cross.rows(1, 2), pag=(blk,), kv_pool=(4, 4, 2, "nearest"))
+    b = blk(h.clone(), 1, 16, st.cross.rows(1, 2), sa=blocks.SelfAttnCall(identity=(blk,), pool={blk: (2, "nearest")}), grid=(4, 4))
     assert torch.equal(a, b) and fake_ops.CALLS == log and "token_pool" not in [n for n, _ in log]
-    c = blk(h.clone(), 1, 16, st.cross.rows(1, 2), pag=(), kv_pool=(4, 4, 2, "nearest"))          # unselected: pools as in the main evaluation
+    c = blk(h.clone(), 1, 16, st.cross.rows(1, 2), sa=blocks.SelfAttnCall(identity=(), pool={blk: (2, "nearest")}), grid=(4, 4))   # unselected: pools as in the main evaluation
     assert "token_pool" in [n for n, _ in fake_ops.CALLS] and not torch.equal(a, c)
     blk.bank = []
 

@@ -17,7 +17,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import mikudance_amd as M  # noqa: E402
-from mikudance_amd import _lib, ops  # noqa: E402
+from mikudance_amd import _lib, blocks, ops  # noqa: E402
 from mikudance_amd.selftest import SCHED_KWARGS, build_models, cosine, rel_l2  # noqa: E402
 from mikudance_amd.synth import synth_inputs  # noqa: E402
 
@@ -147,7 +147,7 @@ def test_block_matches_restatement_in_every_reference_mode(Hh, Ww, mode):
     h = st.x.reshape(-1, 320).to(DEV)
     with torch.no_grad():
         a = st.blk(h.clone(), 4, Hh * Ww, st.cross)
-        b = st.blk(h.clone(), 4, Hh * Ww, st.cross, kv_pool=None)
+        b = st.blk(h.clone(), 4, Hh * Ww, st.cross, sa=blocks.SelfAttnCall(pool=None))
     torch.cuda.synchronize()
     assert torch.equal(a, b) and torch.equal(a.float().cpu().view(4, Hh * Ww, 320), plain["plain"][0])
 

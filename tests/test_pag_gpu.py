@@ -192,7 +192,7 @@ def test_transformer_block_perturbed_rows():
     with torch.no_grad():
         h_cond = x.reshape(f * L, dim).to(DEV)
         # perturbed and selected: the identity attention map, against the restated block
-        got = blk(h_cond.clone(), f, L, cross.rows(f, 2 * f), pag=(blk,))
+        got = blk(h_cond.clone(), f, L, cross.rows(f, 2 * f), sa=blocks.SelfAttnCall(identity=(blk,)))
         want = P._read_identity(sdf, "", x.float(), ctx.float().repeat(f, 1, 1), bank.float())
         _close(got.view(f, L, dim), want, "perturbed, selected vs pag_ref")
         plain = P.O.transformer_block_read(sdf, "", x.float(), ctx.float().repeat(f, 1, 1), bank.float(), cfg=False)
@@ -202,7 +202,7 @@ def test_transformer_block_perturbed_rows():
         # depend on the kernel flavour alone, not on how many rows the launch has; at these sizes (128 rows in the perturbed call, 256 in the
         # CFG call, K = 320, L = 64) the pinned dispatch gives both calls the same flavours.  A wrong bank row or a wrong first bank row on
         # the perturbed path changes the bits.  (At sizes where the smaller call gets another tile flavour the two agree to fp16 rounding only.)
-        un = blk(h_cond.clone(), f, L, cross.rows(f, 2 * f), pag=())
+        un = blk(h_cond.clone(), f, L, cross.rows(f, 2 * f), sa=blocks.SelfAttnCall(identity=()))
         both = blk(torch.cat([h_cond, h_cond]).contiguous(), 2 * f, L, cross)
         torch.cuda.synchronize()
         print(f"\nPAG_BLOCK unselected vs the CFG call's conditional half: max |difference| {float((un.float() - both[f * L:].float()).abs().max()):.3g}")

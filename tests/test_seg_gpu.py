@@ -123,7 +123,7 @@ def test_transformer_block_blurred_queries(Hh, Ww, sigma):
     try:
         with torch.no_grad():
             h = st.x[f:].reshape(f * L, dim).to(DEV)
-            got = blk(h.clone(), f, L, cross, seg=((blk,), Hh, Ww, sigma))
+            got = blk(h.clone(), f, L, cross, sa=blocks.SelfAttnCall(blur=((blk,), sigma)), grid=(Hh, Ww))
             want = S.block_read(st.sd, "", x, ctx, bank, Hh, Ww, sigma)
             bound = _close(got.view(f, L, dim), want, f"{Hh}x{Ww} sigma {sigma}: selected vs seg_ref")
             plain = S.O.transformer_block_read(st.sd, "", x, ctx, bank, cfg=False)
@@ -131,18 +131,18 @@ def test_transformer_block_blurred_queries(Hh, Ww, sigma):
             print(f"\nSEG_BLOCK {Hh}x{Ww} sigma {sigma}: restated perturbed vs unperturbed {moved:.4g} = {moved / bound:.1f} x the bound")
             assert moved > 10 * bound                                       # of the references alone: the perturbation is far above the bound
             # unselected: the conditional half of a normal CFG call on the same rows, bitwise (same kernel flavours at these sizes, as PAG's test)
-            un = blk(h.clone(), f, L, cross, seg=((), Hh, Ww, sigma))
+            un = blk(h.clone(), f, L, cross, sa=blocks.SelfAttnCall(blur=((), sigma)), grid=(Hh, Ww))
             both = blk(st.x.reshape(2 * f * L, dim).to(DEV), 2 * f, L, st.cross)
             torch.cuda.synchronize()
             assert torch.equal(un, both[f * L:])
             _close(un.view(f, L, dim), plain, f"{Hh}x{Ww}: unselected vs the oracle's conditional read")
             # with K / V token downsampling the selected block still attends: blurred q, pooled k / v
-            got = blk(h.clone(), f, L, cross, seg=((blk,), Hh, Ww, sigma), kv_pool=(Hh, Ww, 2, "mean"))
+            got = blk(h.clone(), f, L, cross, sa=blocks.SelfAttnCall(blur=((blk,), sigma), pool={blk: (2, "mean")}), grid=(Hh, Ww))
             _close(got.view(f, L, dim), S.block_read(st.sd, "", x, ctx, bank, Hh, Ww, sigma, kv_pool=(2, "mean")),
                    f"{Hh}x{Ww} sigma {sigma}: selected with kv_pool (2, mean)")
-            for kw in (dict(pag=(blk,)),):
+            for kw in (dict(identity=(blk,)),):
                 with pytest.raises(ValueError):
-                    blk(h.clone(), f, L, cross, seg=((blk,), Hh, Ww, sigma), **kw)
+                    blk(h.clone(), f, L, cross, sa=blocks.SelfAttnCall(blur=((blk,), sigma), **kw), grid=(Hh, Ww))
     finally:
         blk.ref_mode, blk.ref_cfg, blk.bank = None, False, []
 

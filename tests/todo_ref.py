@@ -205,7 +205,7 @@ def block_setup(dim, dctx, Hh, Ww, f, device, seed=21):
 
 def block_runs(st, kv_pool):
     """The block of block_setup in every reference mode with `kv_pool` ((Hh, Ww, s, mode) or None) -> {case: (got, want)} on the host, fp32:
-    plain, write (with the bank it wrote), read + ref_cfg on the whole batch, and its two clip-halves as blocks.CHAIN = 0 / 1."""
+    plain, write (with the bank it wrote), read + ref_cfg on the whole batch, and its two clip-halves as SelfAttnCall(half=0 / 1)."""
     from mikudance_amd import blocks
     blk, f, L, dim, dev = st.blk, st.f, st.L, st.dim, st.device
     h = st.x.reshape(2 * f * L, dim).to(dev)
@@ -214,7 +214,8 @@ def block_runs(st, kv_pool):
         ref = lambda bank, cfg: O.transformer_block_read(st.sd, "", xf, st.ctx_f, bank, cfg=cfg)
     else:
         ref = lambda bank, cfg: block_read(st.sd, "", xf, st.ctx_f, bank, cfg, *kv_pool)
-    kw = {} if kv_pool is None else dict(kv_pool=kv_pool)
+    pool, grid = (None, None) if kv_pool is None else ({blk: tuple(kv_pool[2:])}, tuple(kv_pool[:2]))
+    kw = dict(sa=blocks.SelfAttnCall(pool=pool), grid=grid)
     out = {}
     with torch.no_grad():
         want_plain = ref(None, False)
@@ -227,11 +228,7 @@ def block_runs(st, kv_pool):
         blk.ref_mode, blk.ref_cfg, blk.bank = "read", True, [st.bank.to(dev)]
         out["read-cfg"] = (blk(h.clone(), 2 * f, L, st.cross, **kw), want_read)
         for c in (0, 1):
-            blocks.CHAIN = c
-            try:
-                got = blk(h[c * f * L:(c + 1) * f * L].clone(), f, L, st.cross.rows(c * f, (c + 1) * f), **kw)
-            finally:
-                blocks.CHAIN = None
+            got = blk(h[c * f * L:(c + 1) * f * L].clone(), f, L, st.cross.rows(c * f, (c + 1) * f), sa=blocks.SelfAttnCall(half=c, pool=pool), grid=grid)
             out[f"read-cfg-chain{c}"] = (got, want_read[c * f:(c + 1) * f])
         blk.ref_mode, blk.ref_cfg, blk.bank = None, False, []
     return {k: (g.float().cpu().reshape(w.shape), w) for k, (g, w) in out.items()}
