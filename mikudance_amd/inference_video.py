@@ -64,6 +64,11 @@ def _factors(text):
         raise argparse.ArgumentTypeError(f"expected comma-separated integers, got {text!r}") from None
 
 
+def _layer_names(text):
+    """--pag_layers / --seg_layers: "mid, up_blocks.1" -> a tuple of names (their form is the pipeline's business)."""
+    return tuple(n.strip() for n in text.split(",") if n.strip())
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--config")
@@ -237,11 +242,9 @@ def main(argv=None):
                free_init_filter=args.free_init_filter, free_init_order=args.free_init_order, free_init_spatial_stop=args.free_init_spatial_stop,
                free_init_temporal_stop=args.free_init_temporal_stop, free_init_fast=args.free_init_fast,
                apg=args.apg, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum,
-               pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale,
-               pag_applied_layers=tuple(n.strip() for n in args.pag_layers.split(",") if n.strip()),
+               pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale, pag_applied_layers=_layer_names(args.pag_layers),
                kv_downsample=args.kv_downsample, kv_downsample_mode=args.kv_downsample_mode,
-               seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma,
-               seg_applied_layers=tuple(n.strip() for n in args.seg_layers.split(",") if n.strip()))
+               seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma, seg_applied_layers=_layer_names(args.seg_layers))
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

@@ -17,8 +17,8 @@ Result-preserving reductions (proven identical on the
 """
 import math
 import os
-from dataclasses import dataclass
-from typing import Callable, List, Optional, Union
+from dataclasses import dataclass, replace
+from typing import Callable, List, NamedTuple, Optional, Union
 
 import numpy as np
 import torch
@@ -62,6 +62,36 @@ def slerp(v0, v1, t, DOT_THRESHOLD=0.9995):
 @dataclass
 class MikuDanceVideoPipelineOutput:
     videos: Union[torch.Tensor, np.ndarray]
+
+
+# ---- the sampling plan: what denoise()'s keywords resolve to, once every refusal has been made (MikuDanceVideoPipeline.sampling_plan).
+# The step forms its v in exactly one way -- plain, or one of:
+#   Rescale  v * (1 - phi + phi std(c) / std(v)): md_cfg_guidance_rescale, then the step with vscale=
+#   APG      adaptive projected guidance: md_cfg_apg_prepare, then md_cfg_*_step_apg
+#   Perturb  a second, perturbed conditional evaluation p of the selected `blocks` (layer names until _resolve_plan has asked the UNet) and
+#            v + s_t (c - p) through md_cfg_*_step_pag: PAG (kind "identity", the scale decaying by `adaptive` per timestep, sigma None) or
+#            SEG (kind "blur" with `sigma` in tokens, adaptive 0)
+Rescale = NamedTuple("Rescale", [("phi", float)])
+APG = NamedTuple("APG", [("momentum", float), ("eta", float), ("threshold", float)])
+Perturb = NamedTuple("Perturb", [("kind", str), ("scale", float), ("adaptive", float), ("blocks", tuple), ("sigma", Optional[float])])
+
+
+@dataclass(frozen=True)
+class SamplingPlan:
+    fuse: str                  # "flat" | "pyramid"
+    free_init: tuple           # (iters, filter, order, spatial_stop, temporal_stop, fast)
+    strength: float
+    kv: Union[None, tuple, dict]   # None: no K / V downsampling; (factors, mode), resolved: UNet3DConditionModel.kv_downsample_plan
+    guide: Union[None, Rescale, APG, Perturb]      # None: plain (u + g (c - u), or c without CFG)
+
+
+# the step forms v in ONE way: (asked for, beside, why not), in the order the refusals are made
+_ONE_GUIDE = (("apg=True", "guidance_rescale > 0", "the rescale would need a second statistics pass over APG's guided output"),
+              ("pag_scale > 0", "guidance_rescale > 0", "the rescale would need its statistics taken over the PAG-guided output"),
+              ("pag_scale > 0", "apg=True", "APG's statistics would have to be taken over the PAG-guided output"),
+              ("seg_scale > 0", "pag_scale > 0", "the loop carries one perturbed plane"),
+              ("seg_scale > 0", "guidance_rescale > 0", "the rescale would need its statistics taken over the SEG-guided output"),
+              ("seg_scale > 0", "apg=True", "APG's statistics would have to be taken over the SEG-guided output"))
 
 
 def _pil_to_tensor(img, height, width, normalize):
@@ -255,38 +285,24 @@ class MikuDanceVideoPipeline:
         seg_applied_layers  as pag_applied_layers
         returns latents (1, 4, F, h, w) in the input dtype.
         """
-        self._check_fuse(context_fuse)
-        n_fi = free_init_iters
-        free_init.check_arguments(n_fi, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
-                                  init_latents is not None, (latents.shape[2],) + tuple(latents.shape[3:]) if latents.dim() == 5 else None)
-        phi = float(guidance_rescale)
-        if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
-            raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale}")
-        self._check_strength(strength, init_latents is not None, num_inference_steps)
-        self._check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale)
-        pag_s, pag_a, pag_names = self._check_pag(pag_scale, pag_adaptive_scale, pag_applied_layers, guidance_rescale, apg)
-        kv_factors, kv_mode = self._check_kv_downsample(kv_downsample, kv_downsample_mode, latents.shape[-2], latents.shape[-1])
-        seg_s, seg_sigma, seg_names = self._check_seg(seg_scale, seg_blur_sigma, seg_applied_layers, pag_scale, guidance_rescale, apg)
+        plan = self.sampling_plan(
+            num_inference_steps, guidance_scale, init_latents is not None, tuple(latents.shape[2:]), guidance_rescale=guidance_rescale, strength=strength, context_fuse=context_fuse, free_init_iters=free_init_iters,
+            free_init_filter=free_init_filter, free_init_order=free_init_order, free_init_spatial_stop=free_init_spatial_stop,
+            free_init_temporal_stop=free_init_temporal_stop, free_init_fast=free_init_fast, apg=apg, apg_eta=apg_eta,
+            apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
+            pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode, seg_scale=seg_scale,
+            seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers)
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
-        dev = latents.device
         ops.require_gpu(latents, "MikuDanceVideoPipeline.denoise")
+        plan = self._resolve_plan(plan)                                  # a name that selects no block, too many factors: raised here
+        rescale, projected, pert = (plan.guide if isinstance(plan.guide, kind) else None for kind in (Rescale, APG, Perturb))
+        n_fi, *fi_filter, fi_fast = plan.free_init
+        dev = latents.device
         context_frames = context_frames or self.default_context_frames
         do_cfg = guidance_scale > 1.0
         nb = 2 if do_cfg else 1
         den, refu, sch = self.denoising_unet, self.reference_unet, self.scheduler
-        # PAG: the selected blocks (a name that selects none raises here, before anything runs); off: nothing below changes
-        pag_on = pag_s > 0.0
-        pag_sel = den.pag_blocks(pag_names) if pag_on else None
-        # SEG: PAG's perturbed evaluation with blurred queries in the selected blocks, PAG's plane and PAG's step (never both: _check_seg)
-        seg_on = seg_s > 0.0
-        if seg_on:
-            seg_sel = den.pag_blocks(seg_names, "seg_applied_layers", "smoothed-energy guidance")
-        pert_on = pag_on or seg_on
-        pert_kw = dict(seg=(seg_sel, seg_sigma)) if seg_on else dict(pag=pag_sel)
-        # K / V token downsampling: the per-block plan (too many factors / a level without attention raise here); all ones: no plan, no keyword
-        kv_plan = den.kv_downsample_plan(kv_factors, kv_mode) if any(s > 1 for s in kv_factors) else None
-        kv_kw = {} if kv_plan is None else dict(kv_downsample=kv_plan)
         from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
         multistep = isinstance(sch, DPMSolverMultistepScheduler)
         if not multistep and not isinstance(sch, DDIMScheduler):
@@ -295,12 +311,12 @@ class MikuDanceVideoPipeline:
         if multistep and eta > 0:
             raise ValueError("eta applies to DDIMScheduler only; for stochastic DPM-Solver++ sampling use "
                              "DPMSolverMultistepScheduler(algorithm_type='sde-dpmsolver++')")
-        fi_steps = [free_init.pass_steps(num_inference_steps, n_fi, i, free_init_fast) for i in range(n_fi)]
+        fi_steps = [free_init.pass_steps(num_inference_steps, n_fi, i, fi_fast) for i in range(n_fi)]
         sch.set_timesteps(fi_steps[0])
         timesteps = [int(t) for t in sch.timesteps]
         t_start = 0
         if init_latents is not None:                                     # video-to-video: the tail of the schedule (DPM: begin index set)
-            timesteps = [int(t) for t in sch.get_timesteps(num_inference_steps, strength)[0]]
+            timesteps = [int(t) for t in sch.get_timesteps(num_inference_steps, plan.strength)[0]]
             t_start = num_inference_steps - len(timesteps)
         _, c, F_, hh, ww = latents.shape
         HW = hh * ww
@@ -317,15 +333,17 @@ class MikuDanceVideoPipeline:
             ops.add_noise(lat, ops.pack_nhwc(x0, F_, F_, (0, sx[2], sx[1], sx[3], sx[4]), 0, c, 4, hh, ww), *sch.noise_coefficients(timesteps[0]))
         if n_fi > 1:                                                     # FreeInit: the packed initial noise, the table, (a, b) of t = T
             noise0 = lat.clone()
-            lpf = free_init.freq_filter(F_, hh, ww, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop).to(dev)
+            lpf = free_init.freq_filter(F_, hh, ww, *fi_filter).to(dev)
             fi_ab = sch.noise_coefficients(sch.num_train_timesteps - 1)
-        # PAG: the perturbed prediction is one more plane of the accumulator (the all_reduce carries it), summed by the same kernels at
-        # halves = 1 against a scratch counter (they add to their counter: the real one would count every window twice)
-        noise_sum = torch.zeros((nb + 1 if pert_on else nb, F_, HW, 4), device=dev, dtype=torch.float32)
+        # a perturbation (PAG / SEG): its prediction is one more plane of the accumulator (the all_reduce carries it), summed by the same kernels
+        # at halves = 1 against a scratch counter (they add to their counter: the real one would count every window twice)
+        noise_sum = torch.zeros((nb + 1 if pert else nb, F_, HW, 4), device=dev, dtype=torch.float32)
         counter = torch.zeros((F_,), device=dev, dtype=torch.float32)
-        ns_main, ns_pag, pag_counter = noise_sum, None, None
-        if pert_on:
-            ns_main, ns_pag, pag_counter = noise_sum[:nb], noise_sum[nb:], torch.zeros((F_,), device=dev, dtype=torch.float32)
+        ns_main, ns_pert, pert_counter = noise_sum, None, None
+        if pert:
+            ns_main, ns_pert, pert_counter = noise_sum[:nb], noise_sum[nb:], torch.zeros((F_,), device=dev, dtype=torch.float32)
+            pert_kw = dict(pag=pert.blocks) if pert.kind == "identity" else dict(seg=(pert.blocks, pert.sigma))
+        kv_kw = {} if plan.kv is None else dict(kv_downsample=plan.kv)             # no plan: no keyword
         windows = [list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
                                                                             context_stride, context_overlap)]
         mm_len = getattr(den, "temporal_position_encoding_max_len", None)
@@ -338,24 +356,49 @@ class MikuDanceVideoPipeline:
         win_dev = [torch.tensor(accumulate_slots(w), dtype=torch.int32, device=dev) for w in windows]
         # pyramid fuse: every rank normalises over ALL windows of the step, its own or not (float64 on the host, fp32 on the device)
         wts_dev = None
-        if context_fuse == "pyramid":
+        if plan.fuse == "pyramid":
             wts_dev = [torch.tensor(w, dtype=torch.float64).to(device=dev, dtype=torch.float32) for w in fuse_weights(windows, F_, "pyramid")]
         win_long = [torch.tensor(w, dtype=torch.long, device=dev) for w in windows]     # gather indices: the real frames
         whole = len(windows) == 1 and windows[0] == list(range(F_))
         embeds = image_prompt_embeds
         # DPM-Solver++: the previous step's data prediction, fp32, per call (under window_parallel every rank keeps its own identical copy)
         history = torch.zeros((F_, HW, 4), device=dev, dtype=torch.float32) if multistep else None
-        # guidance rescale: one fp32 factor per step, computed and consumed on the device (no host sync); phi = 0 or no CFG: the unscaled
-        # entry points, called exactly as without the keyword
-        rescale = do_cfg and phi > 0.0
-        scaled = dict(vscale=torch.empty((1,), device=dev, dtype=torch.float32)) if rescale else {}
-        # APG: the momentum buffer and the per-frame (S, K), both written and read on the device (no host sync); off or no CFG: the plain
-        # entry points, called exactly as without the keywords
-        apg_on = do_cfg and bool(apg)
-        if apg_on:
+        # guidance rescale: one fp32 factor per step; APG: the momentum buffer and the per-frame (S, K).  All written and read on the device
+        # (no host sync); another guide: none of them, and the other entry points called exactly as without the keywords
+        if rescale:
+            vscale = torch.empty((1,), device=dev, dtype=torch.float32)
+        if projected:
             apg_m = torch.zeros((F_, HW, 4), device=dev, dtype=torch.float32)
             apg_coef = torch.empty((F_, 2), device=dev, dtype=torch.float32)
-            apg_kw = (float(apg_momentum), float(apg_eta), float(apg_norm_threshold))
+
+        def accumulate(pred, planes, count, wi, halves):
+            if wts_dev is None:
+                ops.window_accumulate(pred, planes, count, win_dev[wi], len(windows[wi]), F_, HW, halves=halves)
+            else:
+                ops.window_accumulate_weighted(pred, planes, count, win_dev[wi], wts_dev[wi], len(windows[wi]), F_, HW, halves=halves)
+
+        def step(step_i, t, s_t):
+            """The CFG + scheduler update of lat from the accumulated planes: ops.cfg_ddim_step / ops.cfg_multistep_step, or the guide's flavour
+            of it (_apg, _pag).  The same statistics on every rank: same buffers, same arithmetic."""
+            if multistep:
+                z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
+                co = sch.multistep_coefficients(t_start + step_i)
+                name, state, (a, s), kw = "cfg_multistep_step", (history,), co[:2], dict(variance_noise=z)
+            else:
+                co = sch.step_coefficients(t)                                          # (abar_t, abar_prev)
+                z = self._draw_noise(latents, generator) if eta > 0 else None
+                name, state, (a, s), kw = "cfg_ddim_step", (), (math.sqrt(co[0]), math.sqrt(1.0 - co[0])), dict(eta=float(eta), variance_noise=z)
+            if projected:
+                ops.cfg_apg_prepare(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, a, s, *projected)
+                getattr(ops, name + "_apg")(lat, noise_sum, counter, *state, apg_m, apg_coef, F_, HW, guidance_scale, *co, **kw)
+            elif s_t > 0.0:
+                getattr(ops, name + "_pag")(lat, ns_main, counter, *state, ns_pert[0], F_, HW, guidance_scale, s_t, *co, halves=nb, **kw)
+            else:
+                if rescale:
+                    ops.cfg_guidance_rescale(noise_sum, counter, F_, HW, guidance_scale, rescale.phi, out=vscale)
+                    kw["vscale"] = vscale
+                getattr(ops, name)(lat, ns_main, counter, *state, F_, HW, guidance_scale, *co, halves=nb, **kw)
+
         bank_cache = {}
         refu.skip_dead_tail = True
         den.clear_context_cache()
@@ -367,12 +410,12 @@ class MikuDanceVideoPipeline:
                     ops.free_init_mix(lat, lat, noise0, z, lpf, *fi_ab)
                     sch.set_timesteps(fi_steps[fi])
                     timesteps = [int(t) for t in sch.timesteps]
-                if apg_on:
+                if projected:
                     apg_m.zero_()                                        # the running average starts over with every pass
                 for step_i, t in enumerate(timesteps):
                     noise_sum.zero_()
                     counter.zero_()
-                    s_t = self._pag_scale_at(pag_s, pag_a, t) if pag_on else seg_s    # a pure function of t: no sync (SEG: constant, 0 = off)
+                    s_t = self._pag_scale_at(pert.scale, pert.adaptive, t) if pert else 0.0     # a pure function of t: no sync
                     for wi, win in enumerate(windows):
                         if window_parallel is not None and not window_parallel.mine(wi):
                             continue                                         # another rank's window (its share arrives in the all_reduce)
@@ -394,53 +437,18 @@ class MikuDanceVideoPipeline:
                         # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
                         pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
                                                 two_queues=self.two_queues, **kv_kw)
-                        if wts_dev is None:
-                            ops.window_accumulate(pred, ns_main, counter, win_dev[wi], f, F_, HW, halves=nb)
-                        else:
-                            ops.window_accumulate_weighted(pred, ns_main, counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=nb)
+                        accumulate(pred, ns_main, counter, wi, nb)
                         if s_t > 0.0:
                             # ---- PAG / SEG: the conditional frames once more (the banks are still in place), the selected self-attention maps
                             # = identity / from blurred queries
                             pred = den.forward_nhwc(x[(nb - 1) * f:], 1, f, torch.full((1,), float(t)), cross.rows(f, 2 * f) if do_cfg else cross,
                                                     **pert_kw, **kv_kw)
-                            if wts_dev is None:
-                                ops.window_accumulate(pred, ns_pag, pag_counter, win_dev[wi], f, F_, HW, halves=1)
-                            else:
-                                ops.window_accumulate_weighted(pred, ns_pag, pag_counter, win_dev[wi], wts_dev[wi], f, F_, HW, halves=1)
+                            accumulate(pred, ns_pert, pert_counter, wi, 1)
                         reader.clear()
                         writer.clear()
                     if window_parallel is not None:
                         window_parallel.reduce(noise_sum, counter)
-                    if rescale:                                              # the same factor on every rank: same buffer, same arithmetic
-                        ops.cfg_guidance_rescale(noise_sum, counter, F_, HW, guidance_scale, phi, out=scaled["vscale"])
-                    if multistep:
-                        z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
-                        co = sch.multistep_coefficients(t_start + step_i)
-                        if apg_on:                                           # the same statistics on every rank: same buffers, same arithmetic
-                            ops.cfg_apg_prepare(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, co[0], co[1], *apg_kw)
-                            ops.cfg_multistep_step_apg(lat, noise_sum, counter, history, apg_m, apg_coef, F_, HW, guidance_scale, *co,
-                                                       variance_noise=z)
-                        elif s_t > 0.0:
-                            ops.cfg_multistep_step_pag(lat, ns_main, counter, history, ns_pag[0], F_, HW, guidance_scale, s_t, *co, halves=nb,
-                                                       variance_noise=z)
-                        else:
-                            ops.cfg_multistep_step(lat, ns_main, counter, history, F_, HW, guidance_scale, *co, halves=nb, variance_noise=z,
-                                                   **scaled)
-                    else:
-                        a_t, a_prev = sch.step_coefficients(t)
-                        z = None
-                        if eta > 0:
-                            z = self._draw_noise(latents, generator)
-                        if apg_on:
-                            ops.cfg_apg_prepare(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, math.sqrt(a_t), math.sqrt(1.0 - a_t), *apg_kw)
-                            ops.cfg_ddim_step_apg(lat, noise_sum, counter, apg_m, apg_coef, F_, HW, guidance_scale, a_t, a_prev, eta=float(eta),
-                                                  variance_noise=z)
-                        elif s_t > 0.0:
-                            ops.cfg_ddim_step_pag(lat, ns_main, counter, ns_pag[0], F_, HW, guidance_scale, s_t, a_t, a_prev, halves=nb,
-                                                  eta=float(eta), variance_noise=z)
-                        else:
-                            ops.cfg_ddim_step(lat, ns_main, counter, F_, HW, guidance_scale, a_t, a_prev, halves=nb, eta=float(eta),
-                                              variance_noise=z, **scaled)
+                    step(step_i, t, s_t)
                     if callback is not None and step_i % callback_steps == 0:
                         callback(step_i, t, self._latents_out(lat, latents))
         finally:
@@ -452,13 +460,40 @@ class MikuDanceVideoPipeline:
         return self._latents_out(lat, latents)
 
     @staticmethod
-    def _check_fuse(context_fuse):
+    def sampling_plan(num_inference_steps, guidance_scale, has_init, shape, *, guidance_rescale, strength, context_fuse,
+                      free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop, free_init_fast, apg, apg_eta,
+                      apg_norm_threshold, apg_momentum, pag_scale, pag_adaptive_scale, pag_applied_layers, kv_downsample, kv_downsample_mode,
+                      seg_scale, seg_blur_sigma, seg_applied_layers):
+        """Every refusal of denoise()'s sampling keywords (see its docstring) that needs no model -- every value is checked whether or not its
+        feature is on, and neither UNet is called -- then what they resolve to -> SamplingPlan, still holding the layer names and the
+        (factors, mode) that _resolve_plan hands to the denoising UNet.  has_init: there is a clip to start from (init_latents / video);
+        shape: the latents' shape behind (batch, channels), (F, h, w)."""
+        from .unet_3d_mix import check_kv_downsample, check_kv_downsample_grid, check_pag_layer_names
+        asked = []
+
+        def ask(guide):                                                  # one more of the ways to form v is asked for
+            for new, old, why in _ONE_GUIDE:
+                if new == guide and old in asked:
+                    raise ValueError(f"{new} cannot be combined with {old}: {why}")
+            asked.append(guide)
+
         if context_fuse not in ("flat", "pyramid"):
             raise ValueError(f"context_fuse must be 'flat' or 'pyramid', got {context_fuse!r}")
-
-    @staticmethod
-    def _check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale):
-        """The refusals of the apg* keywords (the values are checked whether or not apg is on, like guidance_rescale without CFG)."""
+        free_init.check_arguments(free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop, has_init, shape if len(shape) == 3 else None)
+        phi = float(guidance_rescale)
+        if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
+            raise ValueError(f"guidance_rescale must be a finite number in [0, 1], got {guidance_rescale}")
+        if phi > 0.0:
+            ask("guidance_rescale > 0")
+        # video-to-video (diffusers' wording for a schedule with no step left)
+        st = float(strength)
+        if not (math.isfinite(st) and 0.0 < st <= 1.0):
+            raise ValueError(f"strength must be a finite number in (0, 1], got {strength}")
+        if st < 1.0 and not has_init:
+            raise ValueError(f"strength={strength} < 1 needs a clip to start from: pass init_latents (denoise) or video (__call__)")
+        if has_init and min(int(num_inference_steps * strength), num_inference_steps) < 1:
+            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
+                             f"{min(int(num_inference_steps * strength), num_inference_steps)} which is < 1 and not appropriate for this pipeline.")
         e, r, b = float(apg_eta), float(apg_norm_threshold), float(apg_momentum)
         if not (math.isfinite(e) and 0.0 <= e <= 1.0):
             raise ValueError(f"apg_eta must be a finite number in [0, 1], got {apg_eta}")
@@ -466,80 +501,58 @@ class MikuDanceVideoPipeline:
             raise ValueError(f"apg_norm_threshold must be a finite number >= 0, got {apg_norm_threshold}")
         if not (math.isfinite(b) and -1.0 < b < 1.0):
             raise ValueError(f"apg_momentum must be a finite number in (-1, 1), got {apg_momentum}")
-        if apg and float(guidance_rescale) > 0.0:
-            raise ValueError("apg=True cannot be combined with guidance_rescale > 0: the rescale would need a second statistics pass over "
-                             "APG's guided output")
-
-    @staticmethod
-    def _check_pag(pag_scale, pag_adaptive_scale, pag_applied_layers, guidance_rescale, apg):
-        """The refusals of the pag_* keywords that need no model -> (pag_scale, pag_adaptive_scale, layer names).  The values and the form of
-        the names are checked whether or not PAG is on; which blocks the names select is the UNet's business (pag_blocks)."""
-        from .unet_3d_mix import check_pag_layer_names
-        s, a = float(pag_scale), float(pag_adaptive_scale)
-        if not (math.isfinite(s) and s >= 0.0):
+        if apg:
+            ask("apg=True")
+        pag_s, pag_a = float(pag_scale), float(pag_adaptive_scale)
+        if not (math.isfinite(pag_s) and pag_s >= 0.0):
             raise ValueError(f"pag_scale must be a finite number >= 0, got {pag_scale}")
-        if not (math.isfinite(a) and a >= 0.0):
+        if not (math.isfinite(pag_a) and pag_a >= 0.0):
             raise ValueError(f"pag_adaptive_scale must be a finite number >= 0, got {pag_adaptive_scale}")
-        names = check_pag_layer_names(pag_applied_layers)
-        if s > 0.0 and not names:
+        pag_names = check_pag_layer_names(pag_applied_layers)
+        if pag_s > 0.0 and not pag_names:
             raise ValueError("pag_applied_layers is empty: perturbed-attention guidance needs at least one attention block")
-        if s > 0.0 and float(guidance_rescale) > 0.0:
-            raise ValueError("pag_scale > 0 cannot be combined with guidance_rescale > 0: the rescale would need its statistics taken over the "
-                             "PAG-guided output")
-        if s > 0.0 and apg:
-            raise ValueError("pag_scale > 0 cannot be combined with apg=True: APG's statistics would have to be taken over the PAG-guided output")
-        return s, a, names
-
-    @staticmethod
-    def _check_seg(seg_scale, seg_blur_sigma, seg_applied_layers, pag_scale, guidance_rescale, apg):
-        """The refusals of the seg_* keywords that need no model -> (seg_scale, sigma, layer names).  The values and the form of the names are
-        checked whether or not SEG is on; which blocks the names select is the UNet's business (pag_blocks)."""
-        from .unet_3d_mix import check_pag_layer_names
+        if pag_s > 0.0:
+            ask("pag_scale > 0")
+        kv_factors, kv_mode = check_kv_downsample(kv_downsample, kv_downsample_mode)
+        check_kv_downsample_grid(kv_factors, int(shape[-2]), int(shape[-1]))      # every selected level keeps at least one s x s block
         try:
-            s, sigma = float(seg_scale), float(seg_blur_sigma)
+            seg_s, sigma = float(seg_scale), float(seg_blur_sigma)
         except (TypeError, ValueError):
             raise ValueError(f"seg_scale and seg_blur_sigma must be numbers, got {seg_scale!r} and {seg_blur_sigma!r}") from None
-        if not (math.isfinite(s) and s >= 0.0):
+        if not (math.isfinite(seg_s) and seg_s >= 0.0):
             raise ValueError(f"seg_scale must be a finite number >= 0, got {seg_scale}")
         if math.isnan(sigma) or not sigma > 0.0:
             raise ValueError(f"seg_blur_sigma must be a finite number > 0 or math.inf, got {seg_blur_sigma}")
-        names = check_pag_layer_names(seg_applied_layers, "seg_applied_layers")
-        if s > 0.0 and not names:
+        seg_names = check_pag_layer_names(seg_applied_layers, "seg_applied_layers")
+        if seg_s > 0.0 and not seg_names:
             raise ValueError("seg_applied_layers is empty: smoothed-energy guidance needs at least one attention block")
-        if s > 0.0 and float(pag_scale) > 0.0:
-            raise ValueError("seg_scale > 0 cannot be combined with pag_scale > 0: the loop carries one perturbed plane")
-        if s > 0.0 and float(guidance_rescale) > 0.0:
-            raise ValueError("seg_scale > 0 cannot be combined with guidance_rescale > 0: the rescale would need its statistics taken over the "
-                             "SEG-guided output")
-        if s > 0.0 and apg:
-            raise ValueError("seg_scale > 0 cannot be combined with apg=True: APG's statistics would have to be taken over the SEG-guided output")
-        return s, sigma, names
+        if seg_s > 0.0:
+            ask("seg_scale > 0")
+        guide = None
+        if pag_s > 0.0:
+            guide = Perturb("identity", pag_s, pag_a, pag_names, None)
+        elif seg_s > 0.0:                                                # PAG's evaluation, plane and step with blurred queries in the selected blocks
+            guide = Perturb("blur", seg_s, 0.0, seg_names, sigma)
+        elif apg and guidance_scale > 1.0:                               # APG and the rescale act on CFG's v: without CFG, the plain step
+            guide = APG(b, e, r)
+        elif phi > 0.0 and guidance_scale > 1.0:
+            guide = Rescale(phi)
+        return SamplingPlan(context_fuse, (free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
+                                           free_init_fast), strength, (kv_factors, kv_mode) if any(f > 1 for f in kv_factors) else None, guide)
 
-    @staticmethod
-    def _check_kv_downsample(kv_downsample, kv_downsample_mode, h, w):
-        """The refusals of kv_downsample / kv_downsample_mode that need no model -> (factors, mode): the values, the mode, and every selected
-        level of an h x w latent keeping at least one s x s block.  How many levels there are is the UNet's business (kv_downsample_plan)."""
-        from .unet_3d_mix import check_kv_downsample, check_kv_downsample_grid
-        factors, mode = check_kv_downsample(kv_downsample, kv_downsample_mode)
-        check_kv_downsample_grid(factors, int(h), int(w))
-        return factors, mode
+    def _resolve_plan(self, plan):
+        """The refusals only the denoising UNet can make (a layer name that selects no block, more factors than levels, a level without
+        attention) -> the plan with the selected blocks for the names and the per-block K / V plan for (factors, mode)."""
+        den, guide = self.denoising_unet, plan.guide
+        if isinstance(guide, Perturb):
+            what = () if guide.kind == "identity" else ("seg_applied_layers", "smoothed-energy guidance")
+            guide = guide._replace(blocks=den.pag_blocks(guide.blocks, *what))
+        return replace(plan, guide=guide, kv=None if plan.kv is None else den.kv_downsample_plan(*plan.kv))
 
     @staticmethod
     def _pag_scale_at(pag_scale, pag_adaptive_scale, t):
         """diffusers PAGMixin._get_pag_scale: the scale decays linearly as t falls from 1000 and stops at 0."""
         return max(pag_scale - pag_adaptive_scale * (1000 - int(t)), 0.0)
-
-    @staticmethod
-    def _check_strength(strength, has_init, num_inference_steps):
-        """The video-to-video argument checks (diffusers' wording for a schedule with no step left)."""
-        s = float(strength)
-        if not (math.isfinite(s) and 0.0 < s <= 1.0):
-            raise ValueError(f"strength must be a finite number in (0, 1], got {strength}")
-        if s < 1.0 and not has_init:
-            raise ValueError(f"strength={strength} < 1 needs a clip to start from: pass init_latents (denoise) or video (__call__)")
-        if has_init and min(int(num_inference_steps * strength), num_inference_steps) < 1:
-            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
-                             f"{min(int(num_inference_steps * strength), num_inference_steps)} which is < 1 and not appropriate for this pipeline.")
 
     @staticmethod
     def _draw_noise(latents, generator):
@@ -715,36 +728,19 @@ class MikuDanceVideoPipeline:
         # no behaviour to reproduce: the windows are evaluated one at a time here, which is what the sum over a batch would be.
         if context_batch_size < 1:
             raise ValueError(f"context_batch_size must be >= 1, got {context_batch_size}")
-        # context_schedule / context_fuse: see denoise(); both names are checked here, before the CLIP tower and the VAE run
-        self._check_fuse(context_fuse)
-        get_context_scheduler(context_schedule)
+        get_context_scheduler(context_schedule)                          # the name is checked here, before the CLIP tower and the VAE run
         # video / strength: video-to-video (denoise's init_latents), `video` = video_length PIL frames preprocessed like the reference image
         if video is not None and len(video) != video_length:
             raise ValueError(f"video has {len(video)} frames, video_length is {video_length}: they must be equal")
-        self._check_strength(strength, video is not None, num_inference_steps)
-        # free_init_*: FreeInit passes (denoise()); checked here too, the clip's latent shape included, before anything runs
-        fi_kw = dict(free_init_iters=free_init_iters, free_init_filter=free_init_filter, free_init_order=free_init_order,
-                     free_init_spatial_stop=free_init_spatial_stop, free_init_temporal_stop=free_init_temporal_stop, free_init_fast=free_init_fast)
-        free_init.check_arguments(free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
-                                  video is not None, (video_length, (height or 768) // 8, (width or 768) // 8))
-        # apg*: adaptive projected guidance (denoise()); checked here too, before anything runs
-        self._check_apg(apg, apg_eta, apg_norm_threshold, apg_momentum, guidance_rescale)
-        apg_kw = dict(apg=apg, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum)
-        # pag_*: perturbed-attention guidance (denoise()); checked here too, the layer names against the UNet's blocks included
-        pag_s, _, pag_names = self._check_pag(pag_scale, pag_adaptive_scale, pag_applied_layers, guidance_rescale, apg)
-        if pag_s > 0.0:
-            self.denoising_unet.pag_blocks(pag_names)
-        pag_kw = dict(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, pag_applied_layers=pag_applied_layers)
-        # kv_downsample*: K / V token downsampling (denoise()); checked here too, against the clip's latent size and the UNet's levels
-        kv_factors, kv_mode = self._check_kv_downsample(kv_downsample, kv_downsample_mode, (height or 768) // 8, (width or 768) // 8)
-        if any(s > 1 for s in kv_factors):
-            self.denoising_unet.kv_downsample_plan(kv_factors, kv_mode)
-        kv_kw = dict(kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode)
-        # seg_*: smoothed-energy guidance (denoise()); checked here too, and a name that selects no block raises before CLIP / VAE run
-        seg_s, _, seg_names = self._check_seg(seg_scale, seg_blur_sigma, seg_applied_layers, pag_scale, guidance_rescale, apg)
-        if seg_s > 0.0:
-            self.denoising_unet.pag_blocks(seg_names, "seg_applied_layers", "smoothed-energy guidance")
-        seg_kw = dict(seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers)
+        # denoise()'s sampling keywords: every refusal is made here too, against the clip's latent shape and the UNet's blocks, before anything runs
+        loop_kw = dict(guidance_rescale=guidance_rescale, strength=strength, context_fuse=context_fuse, free_init_iters=free_init_iters,
+                       free_init_filter=free_init_filter, free_init_order=free_init_order, free_init_spatial_stop=free_init_spatial_stop,
+                       free_init_temporal_stop=free_init_temporal_stop, free_init_fast=free_init_fast, apg=apg, apg_eta=apg_eta,
+                       apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
+                       pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode,
+                       seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers)
+        self._resolve_plan(self.sampling_plan(num_inference_steps, guidance_scale, video is not None,
+                                              (video_length, (height or 768) // 8, (width or 768) // 8), **loop_kw))
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -778,8 +774,7 @@ class MikuDanceVideoPipeline:
         ref_latents = torch.cat([ref_image_latents, pose_ref_latents, pose_tgt, face_tgt, hand_tgt, tracker], dim=1)[None]
         latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
                                context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
-                               guidance_rescale=guidance_rescale, init_latents=init_latents, strength=strength,
-                               context_fuse=context_fuse, **fi_kw, **apg_kw, **pag_kw, **kv_kw, **seg_kw)
+                               init_latents=init_latents, **loop_kw)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)

@@ -2,12 +2,12 @@
 on the data prediction, with PER-FRAME statistics and a momentum state -- stated in torch at the caller's dtype, the denoising loop of
 oracle/cpu_ref.py restated with it (rebuilt from the oracle's own parts exactly as tests/rescale_ref.py does: oracle.cpu_ref.denoise_loop hands
 only the guided v to its scheduler, APG also needs c, x and the step's abar), and CPU emulations of the three operators the feature adds to
-mikudance_amd.ops, to be patched in beside tests/fake_ops.py.
+mikudance_amd.ops, which tests/fake_ops.py installs with its own.
 
     apg(u, c, x, a, s, g, eta, r, beta, m_prev, dims)   the definition: -> dict(v, m, S, proj, K, D_c, D_g, N2, Q)
     coefficients(N2, P, Q, eta, r)                       (S, proj, K) from a frame's three sums
     denoise_loop(..., apg_on=, apg_eta=, ...)            oracle.cpu_ref.denoise_loop's signature; apg_on=False is that loop op for op
-    cfg_apg_prepare / cfg_ddim_step_apg / cfg_multistep_step_apg, install(monkeypatch), install_process()
+    cfg_apg_prepare / cfg_ddim_step_apg / cfg_multistep_step_apg   the operators' emulations (installed by fake_ops.install)
 """
 import torch
 
@@ -172,18 +172,3 @@ def cfg_multistep_step_apg(latents, noise_sum, counter, history, momentum_buf, c
     del fake_ops.CALLS[n:]
     fake_ops._log("cfg_multistep_step_apg", dict(variance_noise=variance_noise), ftot=ftot, hw=hw, guidance=guidance, alpha_s=alpha_s,
                   sigma_s=sigma_s, c_x=c_x, c_m0=c_m0, c_m1=c_m1, c_z=c_z)
-
-
-def install(monkeypatch):
-    """fake_ops.install plus the three operators above, for the duration of a test."""
-    from mikudance_amd import ops
-    fake_ops.install(monkeypatch)
-    for name in NAMES:
-        monkeypatch.setattr(ops, name, globals()[name], raising=False)
-
-
-def install_process():
-    """The same for a spawned worker process (after loop_helpers.worker_setup, which installs fake_ops)."""
-    from mikudance_amd import ops
-    for name in NAMES:
-        setattr(ops, name, globals()[name])

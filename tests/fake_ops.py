@@ -263,9 +263,11 @@ def concat_channels(a, b):
 
 
 # ------------------------------------------------------------------ the sampling-step tail: accumulate -> rescale -> CFG + scheduler step
-# The complete CPU emulation of the tail (md_window_accumulate[_weighted], md_cfg_guidance_rescale, md_cfg_ddim_step*, md_cfg_multistep_step*,
-# md_add_noise_f16): fp32 arithmetic, one rounding of the latents.  Each call is logged as (name, dict): the scalar arguments and, under
-# "keywords", the names of the optional tensors (variance_noise, vscale) that were given.
+# The CPU emulation of the tail (md_window_accumulate[_weighted], md_cfg_guidance_rescale, md_cfg_ddim_step*, md_cfg_multistep_step*,
+# md_add_noise_f16): fp32 arithmetic, one rounding of the latents.  The APG and PAG flavours of the steps (tests/apg_ref.py, tests/pag_ref.py)
+# form their v and run the two step emulations below on it; install() installs them, token_pool, token_blur and free_init_mix with these.
+# Each call is logged as (name, dict): the scalar arguments and, under "keywords", the names of the optional tensors (variance_noise,
+# vscale) that were given.
 TAIL = ("window_accumulate", "window_accumulate_weighted", "cfg_guidance_rescale", "cfg_ddim_step", "cfg_multistep_step", "add_noise")
 
 
@@ -402,17 +404,33 @@ _NAMES = ("gemm", "gemm_ln_plan", "gemm_ln", "gemm_affine_plan", "groupnorm_tabl
           "attention", "softmax_rows_", "temporal_attention", "pack_nhwc", "unpack_nhwc", "concat_channels", "require_gpu") + TAIL
 
 
+def _emulations():
+    """{name: emulation} of every operator the UNets and the sampling loop can call: the ones above and the ones that live beside their
+    feature's restatement (imported here and not at the top, because those modules import this one)."""
+    import apg_ref
+    import free_init_ref
+    import pag_ref
+    import seg_ref
+    import todo_ref
+    table = {name: globals()[name] for name in _NAMES}
+    table.update({name: getattr(apg_ref, name) for name in apg_ref.NAMES})          # cfg_apg_prepare, cfg_*_step_apg
+    table.update({name: getattr(pag_ref, name) for name in pag_ref.NAMES})          # cfg_*_step_pag
+    table.update(token_pool=todo_ref.token_pool, token_blur=seg_ref.token_blur, free_init_mix=free_init_ref.free_init_mix)
+    return table
+
+
 def install_process():
     """The same replacement for a whole (spawned worker) process: no monkeypatch fixture there, and nothing to restore when it exits."""
     from mikudance_amd import ops
-    for name in _NAMES:
-        setattr(ops, name, globals()[name])
+    for name, fn in _emulations().items():
+        setattr(ops, name, fn)
     del CALLS[:]
 
 
 def install(monkeypatch):
-    """Replace the functions of mikudance_amd.ops by the emulations above for the duration of a test."""
+    """Replace the functions of mikudance_amd.ops by their emulations for the duration of a test: every operator, whichever features the
+    test turns on, and one call log (CALLS)."""
     from mikudance_amd import ops
-    for name in _NAMES:
-        monkeypatch.setattr(ops, name, globals()[name])
+    for name, fn in _emulations().items():
+        monkeypatch.setattr(ops, name, fn)
     del CALLS[:]

@@ -123,7 +123,7 @@ def random_case(F, h, w, seed):
     return x0, torch.randn((F, h, w, 4), generator=g).half(), torch.randn((F, h, w, 4), generator=g).half()
 
 
-# ---- the operator emulated for the CPU loop tests (installed next to fake_ops.install with monkeypatch.setattr(ops, ...))
+# ---- the operator emulated for the CPU loop tests (installed by fake_ops.install)
 def free_init_mix(out, x0, noise0, z, lpf, a, b):
     import fake_ops
     fake_ops.CALLS.append(("free_init_mix", dict(a=a, b=b)))

@@ -1,6 +1,7 @@
-"""TEST INFRASTRUCTURE shared by the CPU tests of the sampling loop (DPM-Solver++, guidance rescale, video-to-video, window fusion): the
-small models and inputs, a UNet stand-in that counts calls, the two parity measures, the three-rank gloo harness and the script's input tree.
-The operators themselves are emulated in tests/fake_ops.py."""
+"""TEST INFRASTRUCTURE shared by the CPU tests of the sampling loop (DPM-Solver++, guidance rescale, video-to-video, window fusion, FreeInit, APG,
+PAG, K / V downsampling, SEG): the small models and inputs, a UNet stand-in that counts calls, the two parity measures, the three-rank gloo harness
+(worker_setup installs every emulated operator) and the script's input tree.  The operators themselves are emulated in tests/fake_ops.py and, beside
+their feature's restatement, in tests/*_ref.py; fake_ops.install / install_process install all of them."""
 import os
 import socket
 import sys

@@ -1,13 +1,13 @@
 """TEST INFRASTRUCTURE: perturbed-attention guidance (PAG; Ahn et al., arXiv 2403.17377; diffusers PAGMixin) as this project defines it, stated
-in torch at the caller's dtype on top of oracle/cpu_ref.py, and CPU emulations of the two operators the feature adds to mikudance_amd.ops, to
-be patched in beside tests/fake_ops.py.
+in torch at the caller's dtype on top of oracle/cpu_ref.py, and CPU emulations of the two operators the feature adds to mikudance_amd.ops,
+which tests/fake_ops.py installs with its own.
 
     combine(u, c, p, g, s) / combine_sum(c_sum, p_sum, s)   the combination rule, under CFG and without
     pag_scale_at(scale, adaptive, t)                        diffusers' _get_pag_scale
     block_prefixes(sd), select(prefixes, names)             the attention blocks of a state dict and the layer-name matching, on strings
     perturbed_forward(den_sd, x, t, ctx, banks, names)      oracle.cpu_ref.denoising_unet_forward as the perturbed conditional evaluation
     denoise_loop(..., pag_scale=, pag_adaptive_scale=, pag_layers=)   tests/fusion_ref.denoise_loop with PAG; pag_scale=0 is that loop op for op
-    cfg_ddim_step_pag / cfg_multistep_step_pag, install(monkeypatch), install_process()
+    cfg_ddim_step_pag / cfg_multistep_step_pag              the operators' emulations (installed by fake_ops.install)
 The oracle is not edited: inside `perturbed(...)`, and in this process only, its transformer_block_read is swapped for one that takes the
 identity in place of the self-attention map for the selected prefixes.
 """
@@ -211,18 +211,3 @@ def cfg_multistep_step_pag(latents, noise_sum, counter, history, perturbed_sum, 
     del fake_ops.CALLS[n:]
     fake_ops._log("cfg_multistep_step_pag", dict(variance_noise=variance_noise), ftot=ftot, hw=hw, halves=halves, guidance=guidance,
                   pag_scale=pag_scale, alpha_s=alpha_s, sigma_s=sigma_s, c_x=c_x, c_m0=c_m0, c_m1=c_m1, c_z=c_z)
-
-
-def install(monkeypatch):
-    """fake_ops.install plus the two operators above, for the duration of a test."""
-    from mikudance_amd import ops
-    fake_ops.install(monkeypatch)
-    for name in NAMES:
-        monkeypatch.setattr(ops, name, globals()[name], raising=False)
-
-
-def install_process():
-    """The same for a spawned worker process (after loop_helpers.worker_setup, which installs fake_ops)."""
-    from mikudance_amd import ops
-    for name in NAMES:
-        setattr(ops, name, globals()[name])

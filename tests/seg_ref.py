@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: smoothed-energy guidance (SEG; Hong, arXiv 2408.00760) as this project defines it -- the float64 definition of the query
 blur, a float32 restatement of the separable algorithm the kernel runs, the perturbed block and the loop stated in torch on top of
-oracle/cpu_ref.py, and a CPU emulation of ops.token_blur to be patched in beside tests/fake_ops.py.
+oracle/cpu_ref.py, and a CPU emulation of ops.token_blur, which tests/fake_ops.py installs with its own.
 
     kernel_size(sigma, n), taps(sigma, n), reflect(i, n)    the clamp rule, the normalised Gaussian (float64), torch's "reflect" index
     blur64(x, B, Hh, Ww, sigma)                             the definition: a direct 2-D reflect-padded convolution with the outer-product
@@ -8,7 +8,7 @@ oracle/cpu_ref.py, and a CPU emulation of ops.token_blur to be patched in beside
     blur32(x, B, Hh, Ww, sigma)                             float32, separable, x axis first, taps added in ascending order, fp32 between the axes
     block_read(sd, p, x, ctx, bank, Hh, Ww, sigma, kv_pool) the perturbed conditional read block with blurred queries
     perturbed_forward(...), denoise_loop(..., seg_scale=, seg_blur_sigma=, seg_layers=)   tests/pag_ref.denoise_loop with SEG's perturbation
-    token_blur, install(monkeypatch), install_process()    the operator's emulation
+    token_blur                                              the operator's emulation (installed by fake_ops.install)
 The oracle is not edited: inside `perturbed(...)`, and in this process only, its transformer_3d is wrapped to note the grid and its
 transformer_block_read is swapped for block_read on the selected prefixes.
 """
@@ -190,19 +190,3 @@ def token_blur(x, B, Hh, Ww, sigma, out=None):
     assert out.is_contiguous() and out.shape == x.shape and out.data_ptr() != x.data_ptr()
     out.copy_(y)
     return out
-
-
-def install(monkeypatch):
-    """tests/pag_ref.install (fake_ops and the two *_pag steps), tests/todo_ref's token_pool, and the operator above, for one test."""
-    from mikudance_amd import ops
-    P.install(monkeypatch)
-    monkeypatch.setattr(ops, "token_pool", T.token_pool, raising=False)
-    monkeypatch.setattr(ops, "token_blur", token_blur, raising=False)
-
-
-def install_process():
-    """The same for a spawned worker process (after loop_helpers.worker_setup, which installs fake_ops)."""
-    from mikudance_amd import ops
-    P.install_process()
-    T.install_process()
-    ops.token_blur = token_blur

@@ -128,7 +128,7 @@ def _threshold(ref_sd, den_sd, inputs, steps, rs, momentum, **win):
 
 @pytest.mark.parametrize("sampler", ["ddim", "2m"])
 def test_host_loop_matches_restatement(monkeypatch, small_cpu, sampler):
-    A.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, ref_sd, den_sd = small_cpu
     lat, rl, emb = small_inputs(4, 17)
     mk_rs = lambda: None if sampler == "ddim" else R.Restated(2, "dpmsolver++", "midpoint")
@@ -158,7 +158,7 @@ def test_host_loop_matches_restatement(monkeypatch, small_cpu, sampler):
 
 @pytest.mark.parametrize("sampler", ["ddim", "2m"])
 def test_default_makes_no_apg_call_and_keeps_the_bits(monkeypatch, small_cpu, sampler):
-    A.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 19))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim() if sampler == "ddim" else _dpm())
@@ -174,7 +174,7 @@ def test_default_makes_no_apg_call_and_keeps_the_bits(monkeypatch, small_cpu, sa
 
 
 def test_apg_without_cfg_runs_the_plain_path(monkeypatch, small_cpu):
-    A.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 21))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
@@ -184,7 +184,7 @@ def test_apg_without_cfg_runs_the_plain_path(monkeypatch, small_cpu):
 
 
 def test_eta_and_sde_draws_reach_the_apg_steps(monkeypatch, small_cpu):
-    A.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(2, 22))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
@@ -197,10 +197,7 @@ def test_eta_and_sde_draws_reach_the_apg_steps(monkeypatch, small_cpu):
 
 
 def test_momentum_buffer_is_zeroed_once_per_free_init_pass(monkeypatch, small_cpu):
-    import free_init_ref as FR
-    from mikudance_amd import ops
-    A.install(monkeypatch)
-    monkeypatch.setattr(ops, "free_init_mix", FR.free_init_mix, raising=False)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 23))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
@@ -223,7 +220,7 @@ BAD = [(dict(apg_eta=-0.1), "apg_eta"), (dict(apg_eta=1.0001), "apg_eta"), (dict
 @pytest.mark.parametrize("kw,msg", BAD)
 @pytest.mark.parametrize("make", [_ddim, _dpm], ids=["ddim", "dpm"])
 def test_bad_arguments_raise_before_any_unet(monkeypatch, kw, msg, make):
-    A.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     refu, den = CountingUNet(), CountingUNet()
     pipe = M.MikuDanceVideoPipeline(None, None, refu, den, make())
     with pytest.raises(ValueError, match=msg):
@@ -262,11 +259,9 @@ def test_call_refuses_before_clip_and_vae_and_forwards_the_keywords(monkeypatch)
 # ---- 5. window parallelism: three gloo ranks, every rank its own identical momentum buffer
 def _wp_worker(rank, world, port, q):
     worker_setup(rank, world, port)
-    import apg_ref
     from mikudance_amd import MikuDanceVideoPipeline, dp
     from mikudance_amd.selftest import build_models
     from mikudance_amd.synth import synth_inputs
-    apg_ref.install_process()
     ref, den, _, _ = build_models(device="cpu", keep_state_dicts=False)
     lat, rl, emb = (t.half() for t in synth_inputs(16, 16, 16, ctx_len=5, ctx_dim=64, seed=521))
     # 3 windows, the last one wraps

@@ -31,11 +31,6 @@ def _dpm(**kw):
     return M.DPMSolverMultistepScheduler(**SCHED_KWARGS, **kw)
 
 
-def _install(monkeypatch):
-    fake_ops.install(monkeypatch)
-    monkeypatch.setattr(ops, "free_init_mix", FR.free_init_mix, raising=False)
-
-
 def _log():
     """The tail operators and the mixes, in call order."""
     return [(n, d) for n, d in fake_ops.CALLS if n in fake_ops.TAIL or n == "free_init_mix"]
@@ -88,7 +83,7 @@ def test_kernel_form_equals_the_literal_mix(shape, kind):
 # ---- 2. the loop on the emulated operators
 @pytest.mark.parametrize("sampler", ["ddim", "2m"])
 def test_default_makes_no_mix_call_and_keeps_the_bits(monkeypatch, small_cpu, sampler):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 81))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim() if sampler == "ddim" else _dpm())
@@ -103,7 +98,7 @@ def test_default_makes_no_mix_call_and_keeps_the_bits(monkeypatch, small_cpu, sa
 
 
 def test_three_iterations_log_two_mixes_and_three_full_passes(monkeypatch, small_cpu):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 82))
     sch = _ddim()
@@ -118,7 +113,7 @@ def test_three_iterations_log_two_mixes_and_three_full_passes(monkeypatch, small
 
 
 def test_banks_are_written_once_for_all_passes(monkeypatch, small_cpu):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 83))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
@@ -131,7 +126,7 @@ def test_banks_are_written_once_for_all_passes(monkeypatch, small_cpu):
 
 @pytest.mark.parametrize("sampler", ["ddim", "2m"])
 def test_fast_sampling_runs_2_4_6_steps(monkeypatch, small_cpu, sampler):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(2, 84))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim() if sampler == "ddim" else _dpm())
@@ -149,7 +144,7 @@ def test_fast_sampling_runs_2_4_6_steps(monkeypatch, small_cpu, sampler):
 
 @pytest.mark.parametrize("sampler", ["ddim", "ddim-eta", "2m"])
 def test_host_loop_matches_oracle_with_literal_mix(monkeypatch, small_cpu, sampler):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, ref_sd, den_sd = small_cpu
     lat, rl, emb = small_inputs(4, 85)
     eta = 0.5 if sampler == "ddim-eta" else 0.0
@@ -168,7 +163,7 @@ def test_host_loop_matches_oracle_with_literal_mix(monkeypatch, small_cpu, sampl
 
 
 def test_z_is_the_first_draw_of_a_pass(monkeypatch, small_cpu):
-    _install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(2, 86))
     seen = []
@@ -285,12 +280,9 @@ def test_script_flags_reach_the_pipeline(monkeypatch, tmp_path):
 # ---- 5. window parallelism: three gloo ranks, the mix replicated on every rank
 def _wp_worker(rank, world, port, q):
     worker_setup(rank, world, port)
-    import free_init_ref
     from mikudance_amd import MikuDanceVideoPipeline, dp
-    from mikudance_amd import ops as worker_ops
     from mikudance_amd.selftest import build_models
     from mikudance_amd.synth import synth_inputs
-    worker_ops.free_init_mix = free_init_ref.free_init_mix
     ref, den, _, _ = build_models(device="cpu", keep_state_dicts=False)
     lat, rl, emb = (t.half() for t in synth_inputs(16, 16, 16, ctx_len=5, ctx_dim=64, seed=421))
     # F = 16, windows of 8 with overlap 2, open: [0..7], [6..13], [8..15] -- one per rank, every fp32 sum has at most two non-zero terms

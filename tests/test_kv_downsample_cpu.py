@@ -139,7 +139,7 @@ BAD = [(dict(kv_downsample=0), "1..8"), (dict(kv_downsample=9), "1..8"), (dict(k
 @pytest.mark.parametrize("kw,msg", BAD)
 @pytest.mark.parametrize("make", [_ddim, _dpm], ids=["ddim", "dpm"])
 def test_bad_arguments_raise_before_any_unet(monkeypatch, kw, msg, make):
-    T.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     refu, den = CountingUNet(), CountingUNet()
     pipe = M.MikuDanceVideoPipeline(None, None, refu, den, make())
     with pytest.raises(ValueError, match=msg):
@@ -159,7 +159,7 @@ def test_levels_halve_with_ceil():
 
 
 def test_too_many_factors_raise_before_anything_runs(monkeypatch, small_cpu):
-    T.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
     lat, rl, emb = (t.half() for t in small_inputs(2, 3))
@@ -203,7 +203,7 @@ def test_call_refuses_before_clip_and_vae_and_forwards_the_keywords(monkeypatch)
 # ---- 3. one TransformerBlock on the emulated operators, every reference mode
 @pytest.mark.parametrize("Hh,Ww,s,mode", [(8, 8, 2, "nearest"), (5, 7, 2, "mean"), (6, 4, 3, "nearest")])
 def test_block_matches_restatement_in_every_reference_mode(monkeypatch, Hh, Ww, s, mode):
-    T.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     st = T.block_setup(64, 64, Hh, Ww, 2, torch.device("cpu"))
     del fake_ops.CALLS[:]
     plain = T.block_runs(st, None)
@@ -223,14 +223,14 @@ def test_block_matches_restatement_in_every_reference_mode(monkeypatch, Hh, Ww, 
 
 
 def test_block_refuses_a_grid_that_is_not_its_token_count(monkeypatch):
-    T.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     st = T.block_setup(64, 64, 4, 4, 1, torch.device("cpu"))
     with pytest.raises(ValueError, match="does not hold L = 16"):
         st.blk(st.x.reshape(-1, 64), 2, 16, st.cross, sa=blocks.SelfAttnCall(pool={st.blk: (2, "nearest")}), grid=(4, 5))
 
 
 def test_perturbed_block_ignores_kv_pool(monkeypatch):
-    T.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     st = T.block_setup(64, 64, 4, 4, 1, torch.device("cpu"))
     blk = st.blk
     blk.ref_mode, blk.ref_cfg, blk.bank = "read", True, [st.bank]
@@ -267,7 +267,7 @@ def _inputs10(frames, seed):
 
 
 def test_default_is_the_same_call_log_and_the_same_bits(monkeypatch, small_cpu):
-    T.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     _attention_logged(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 19))
@@ -290,7 +290,7 @@ def test_default_is_the_same_call_log_and_the_same_bits(monkeypatch, small_cpu):
 def test_host_graph_attention_calls_bank_and_values(monkeypatch, small_cpu, factors, mode):
     """One step of denoise() on a 2-frame 10 x 10 latent under CFG: which attention launch gets which Lk / kv_stride, what token_pool is
     handed, the bank it finds, and the result against the restated loop."""
-    T.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     _attention_logged(monkeypatch)
     ref, den, ref_sd, den_sd = small_cpu
     lat, rl, emb = _inputs10(2, 41)
@@ -350,9 +350,7 @@ LOOPS = {"ddim-cfg": dict(frames=4, steps=3, guidance=3.5, kv=(2,), mode="neares
 
 @pytest.mark.parametrize("case", list(LOOPS))
 def test_host_loop_matches_restatement(monkeypatch, small_cpu, case):
-    P.install(monkeypatch)
-    from mikudance_amd import ops
-    monkeypatch.setattr(ops, "token_pool", T.token_pool, raising=False)
+    fake_ops.install(monkeypatch)
     cfg = LOOPS[case]
     ref, den, ref_sd, den_sd = small_cpu
     lat, rl, emb = small_inputs(cfg["frames"], 170 + cfg["frames"])
@@ -393,11 +391,9 @@ def test_restated_loop_with_factor_one_is_the_oracle_loop(small_cpu):
 # ---- 6. window parallelism: three gloo ranks
 def _wp_worker(rank, world, port, q):
     worker_setup(rank, world, port)
-    import todo_ref
     from mikudance_amd import MikuDanceVideoPipeline, dp
     from mikudance_amd.selftest import build_models
     from mikudance_amd.synth import synth_inputs
-    todo_ref.install_process()
     ref, den, _, _ = build_models(device="cpu", keep_state_dicts=False)
     lat, rl, emb = (t.half() for t in synth_inputs(16, 16, 16, ctx_len=5, ctx_dim=64, seed=521))
     kw = dict(context_frames=8, context_stride=1, context_overlap=2, kv_downsample=(2, 2))      # 3 windows, the last one wraps

@@ -61,7 +61,7 @@ BAD = [(dict(pag_scale=-0.1), "pag_scale"), (dict(pag_scale=nan), "pag_scale"), 
 @pytest.mark.parametrize("kw,msg", BAD)
 @pytest.mark.parametrize("make", [_ddim, _dpm], ids=["ddim", "dpm"])
 def test_bad_arguments_raise_before_any_unet(monkeypatch, kw, msg, make):
-    P.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     refu, den = CountingUNet(), CountingUNet()
     pipe = M.MikuDanceVideoPipeline(None, None, refu, den, make())
     with pytest.raises(ValueError, match=msg):
@@ -70,7 +70,7 @@ def test_bad_arguments_raise_before_any_unet(monkeypatch, kw, msg, make):
 
 
 def test_a_name_that_selects_no_block_raises_before_anything_runs(monkeypatch, small_cpu):
-    P.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
     lat, rl, emb = (t.half() for t in small_inputs(2, 3))
@@ -176,7 +176,7 @@ def test_schedule_matches_the_restatement_and_skips_the_evaluation_at_zero(monke
     got = [M.MikuDanceVideoPipeline._pag_scale_at(3.0, adaptive, t) for t in ts]
     assert got == want and [M.MikuDanceVideoPipeline._pag_scale_at(3.0, 0.0, t) for t in ts] == [3.0] * 20
     # the loop: 20 steps on a 2-frame 8 x 8 clip, the perturbed evaluation runs at the first eight timesteps only
-    P.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     spy = _Spy(den, monkeypatch)
     lat, rl, emb = (t.half() for t in _inputs8(2, 31))
@@ -190,7 +190,7 @@ def test_schedule_matches_the_restatement_and_skips_the_evaluation_at_zero(monke
 
 
 def test_scale_zero_never_runs_the_perturbed_evaluation_and_keeps_the_bits(monkeypatch, small_cpu):
-    P.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     spy = _Spy(den, monkeypatch)
     lat, rl, emb = (t.half() for t in small_inputs(4, 19))
@@ -230,7 +230,7 @@ def _launches():
 def read_state(request, monkeypatch, small_cpu):
     """The denoising UNet in read mode with the banks of one 2-frame window, as denoise() sets it up under CFG.  8 x 8 unless the test asks
     for another size (indirect parameter)."""
-    P.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     _attention_logged(monkeypatch)
     ref, den, ref_sd, den_sd = small_cpu
     f, t = 2, 601
@@ -338,7 +338,7 @@ LOOPS = {"ddim-1win": dict(frames=4, steps=3, guidance=3.5), "wrap-flat": dict(f
 
 @pytest.mark.parametrize("case", list(LOOPS))
 def test_host_loop_matches_restatement(monkeypatch, small_cpu, case):
-    P.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     cfg = LOOPS[case]
     ref, den, ref_sd, den_sd = small_cpu
     lat, rl, emb = small_inputs(cfg["frames"], 70 + cfg["frames"])
@@ -384,7 +384,7 @@ def test_combination_rule_limits():
 
 
 def test_eta_and_sde_draws_reach_the_pag_steps(monkeypatch, small_cpu):
-    P.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(2, 22))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
@@ -397,10 +397,7 @@ def test_eta_and_sde_draws_reach_the_pag_steps(monkeypatch, small_cpu):
 
 
 def test_every_free_init_pass_is_guided(monkeypatch, small_cpu):
-    import free_init_ref as FRI
-    from mikudance_amd import ops
-    P.install(monkeypatch)
-    monkeypatch.setattr(ops, "free_init_mix", FRI.free_init_mix, raising=False)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 23))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
@@ -413,7 +410,7 @@ def test_literal_reference_pass_reads_the_conditional_part_of_the_bank(monkeypat
     """reference_reuse off: the banks hold 2f frames and the perturbed rows read the conditional part.  The literal writer runs 2f frames
     through torch's CPU matmul, whose summation order depends on the row count, so the banks (and the result) agree to fp16 rounding, not bitwise:
     the host-graph bound.  Reading the unconditional part instead (banks of the zero context) is far outside it."""
-    P.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(2, 24))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
@@ -426,11 +423,9 @@ def test_literal_reference_pass_reads_the_conditional_part_of_the_bank(monkeypat
 # ---- 6. window parallelism: three gloo ranks
 def _wp_worker(rank, world, port, q):
     worker_setup(rank, world, port)
-    import pag_ref
     from mikudance_amd import MikuDanceVideoPipeline, dp
     from mikudance_amd.selftest import build_models
     from mikudance_amd.synth import synth_inputs
-    pag_ref.install_process()
     ref, den, _, _ = build_models(device="cpu", keep_state_dicts=False)
     lat, rl, emb = (t.half() for t in synth_inputs(16, 16, 16, ctx_len=5, ctx_dim=64, seed=521))
     # 3 windows, the last one wraps

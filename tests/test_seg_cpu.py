@@ -97,7 +97,7 @@ BAD = [(dict(seg_scale=-0.1), "seg_scale"), (dict(seg_scale=nan), "seg_scale"), 
 @pytest.mark.parametrize("kw,msg", BAD)
 @pytest.mark.parametrize("make", [_ddim, _dpm], ids=["ddim", "dpm"])
 def test_bad_arguments_raise_before_any_unet(monkeypatch, kw, msg, make):
-    S.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     refu, den = CountingUNet(), CountingUNet()
     pipe = M.MikuDanceVideoPipeline(None, None, refu, den, make())
     with pytest.raises(ValueError, match=msg):
@@ -106,7 +106,7 @@ def test_bad_arguments_raise_before_any_unet(monkeypatch, kw, msg, make):
 
 
 def test_a_name_that_selects_no_block_raises_before_anything_runs(monkeypatch, small_cpu):
-    S.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 19))
     pipe = M.MikuDanceVideoPipeline(None, None, ref, den, _ddim())
@@ -118,7 +118,7 @@ def test_a_name_that_selects_no_block_raises_before_anything_runs(monkeypatch, s
 
 # ---- 3. the default
 def test_default_is_the_plain_loop_call_for_call(monkeypatch, small_cpu):
-    S.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     ref, den, _, _ = small_cpu
     lat, rl, emb = (t.half() for t in small_inputs(4, 19))
     for make, step in ((_ddim, "cfg_ddim_step"), (_dpm, "cfg_multistep_step")):
@@ -189,7 +189,7 @@ LOOPS = {"ddim": dict(guidance=3.5, sigma=100.0), "no-cfg-inf": dict(guidance=1.
 
 @pytest.mark.parametrize("case", list(LOOPS))
 def test_host_loop_matches_restatement(monkeypatch, small_cpu, case):
-    S.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     cfg = LOOPS[case]
     ref, den, ref_sd, den_sd = small_cpu
     lat, rl, emb = small_inputs(4, 74)
@@ -219,11 +219,9 @@ def test_host_loop_matches_restatement(monkeypatch, small_cpu, case):
 # ---- 6. window parallelism: three gloo ranks
 def _wp_worker(rank, world, port, q):
     worker_setup(rank, world, port)
-    import seg_ref
     from mikudance_amd import MikuDanceVideoPipeline, dp
     from mikudance_amd.selftest import build_models
     from mikudance_amd.synth import synth_inputs
-    seg_ref.install_process()
     ref, den, _, _ = build_models(device="cpu", keep_state_dicts=False)
     lat, rl, emb = (t.half() for t in synth_inputs(16, 16, 16, ctx_len=5, ctx_dim=64, seed=521))
     kw = dict(context_frames=8, context_stride=1, context_overlap=2, seg_scale=3.0, seg_blur_sigma=1.5, seg_applied_layers=("mid", "up_blocks.1"))

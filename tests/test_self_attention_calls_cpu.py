@@ -38,7 +38,6 @@ import torch
 from mikudance_amd import blocks, ops
 
 import fake_ops
-import seg_ref as S
 import todo_ref as T
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "self_attention_calls.json")
@@ -87,7 +86,7 @@ def _recorded(name, fn, log, names):
 
 def trace_all(monkeypatch, kind, call):
     """{"mode/pool": [call, ...]} of the block of todo_ref.block_setup under the emulated operators, each case from a block with nothing cached."""
-    S.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     st = T.block_setup(DIM, DIM, HH, WW, F, torch.device("cpu"))
     blk, L = st.blk, st.L
     blk.kind = kind
@@ -144,7 +143,7 @@ def test_block_issues_the_recorded_calls(monkeypatch, recorded, kind):
 
 
 def test_refused_combinations(monkeypatch):
-    S.install(monkeypatch)
+    fake_ops.install(monkeypatch)
     st = T.block_setup(DIM, DIM, HH, WW, F, torch.device("cpu"))
     blk, L = st.blk, st.L
     h, cross = st.x[F:].reshape(F * L, DIM), st.cross.rows(F, 2 * F)

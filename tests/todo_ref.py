@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: K / V token downsampling in spatial self-attention (ToDo: Token Downsampling, Smith et al., arXiv 2402.13573) as this
 project defines it, stated in torch at the caller's dtype on top of oracle/cpu_ref.py, and a CPU emulation of the operator the feature adds
-to mikudance_amd.ops, to be patched in beside tests/fake_ops.py.
+to mikudance_amd.ops, which tests/fake_ops.py installs with its own.
 
     pool(tokens, B, Hh, Ww, s, mode)                       the definition: F.interpolate(nearest) / F.avg_pool2d on the token grid
     level_of(prefix, levels), factor_of(...)               which resolution level a block's key prefix belongs to, on strings
@@ -9,7 +9,7 @@ to mikudance_amd.ops, to be patched in beside tests/fake_ops.py.
     unet_forward(den_sd, x, t, ctx, banks, factors, mode, cfg)
     denoise_loop(..., kv_downsample=, mode=)               tests/fusion_ref.denoise_loop (tests/pag_ref.denoise_loop when pag_scale > 0);
                                                            with every factor 1 it is that loop op for op
-    token_pool, install(monkeypatch), install_process()    the operator's emulation
+    token_pool                                             the operator's emulation (installed by fake_ops.install)
     block_setup(...), block_runs(st, kv_pool)              one product TransformerBlock in every reference mode beside its restatement
 The oracle is not edited: inside `pooled(...)`, and in this process only, its transformer_3d is wrapped to note the grid and its
 transformer_block_read is swapped for block_read on the selected prefixes.
@@ -163,19 +163,6 @@ def token_pool(x, B, Hh, Ww, s, mode="nearest", out=None):
     o[:, Lk:] = 0
     fake_ops.CALLS.append(("token_pool", (B, Hh, Ww, C, s, mode)))
     return out, Lk, stride
-
-
-def install(monkeypatch):
-    """fake_ops.install plus the operator above, for the duration of a test."""
-    from mikudance_amd import ops
-    fake_ops.install(monkeypatch)
-    monkeypatch.setattr(ops, "token_pool", token_pool, raising=False)
-
-
-def install_process():
-    """The same for a spawned worker process (after loop_helpers.worker_setup, which installs fake_ops)."""
-    from mikudance_amd import ops
-    ops.token_pool = token_pool
 
 
 # ------------------------------------------------------------------ one TransformerBlock in every reference mode (CPU-emulated and GPU tests)
