@@ -547,8 +547,7 @@ static void launch_variant(GemmParams& p, hipStream_t stream) {
   hipLaunchKernelGGL((gemm_kernel<CONV, BK, NSTAGE, WM, WPS, GEGLU, NJ, MI>), dim3(p.tiles_total), dim3(WM * 128), smem, stream, p);
 }
 
-static int env_int(const char* name, int dflt) { return md_env_int(name, dflt); }
-
+static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // Streams created with a CU mask (hipExtStreamCreateWithCUMask) own fewer CUs than the device has: the persistent launchers size their
 // grids -- and the rounds model its tile choice -- for md_set_cu_limit's count instead (process-wide; 0 = the device's own count).
@@ -622,8 +621,7 @@ static void launch_ws(const GemmParams& g, hipStream_t stream) {
 static bool ws_geglu_eligible(const GemmParams& p) {
   if (p.act != ACT_GEGLU || p.K != 320 || p.N % 256 || p.N / 256 > 16 || p.M < 32768 || p.M % 16) return false;
   if (p.lda % 8 || p.ldc % 8) return false;
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return al(p.A) && al(p.W) && al(p.C) && al(p.bias);
+  return al16(p.A) && al16(p.W) && al16(p.C) && al16(p.bias);
 }
 
 static void launch_ws_geglu(const GemmParams& g, hipStream_t stream) {
@@ -644,7 +642,6 @@ static void launch_ws_geglu(const GemmParams& g, hipStream_t stream) {
 static bool ws_fused_shape(int M, int N, int K, int lda, int ldc) {
   return K == 320 && N % 320 == 0 && N / 320 <= 8 && M >= 32768 && M % 16 == 0 && lda % 8 == 0 && ldc % 8 == 0;
 }
-static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 template <int TPR, bool RA, int PRO>
 static void launch_ws_fused(const WsParams& p, hipStream_t stream) {
@@ -711,139 +708,125 @@ static bool ws_eligible(const GemmParams& p) {
   const bool k640 = p.K == 640 && p.N % 128 == 0 && p.N / 128 <= 16;
   if (!k320 && !k640) return false;
   if (p.lda % 8 || p.ldc % 8 || (p.residual && p.ldr % 8) || (p.rowadd && p.ldra % 8)) return false;
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return al(p.A) && al(p.W) && al(p.C) && al(p.bias) && al(p.residual) && al(p.rowadd);
+  return al16(p.A) && al16(p.W) && al16(p.C) && al16(p.bias) && al16(p.residual) && al16(p.rowadd);
 }
 
-// Plan codes (returned by dispatch_any; md_gemm_plan / md_conv3x3_plan expose them so that the table is testable without a GPU):
-//   1MN  gemm_sp_kernel with wave tile (MT, NT) = (M, N): 135 = 192 x 320, 134 = 192 x 256, 124 = 128 x 256, 144 = 256 x 256 GEGLU;
+// Plan codes (GemmKernel::code, chosen by gemm_choose; md_gemm_plan / md_conv3x3_plan expose them so that the table is testable without a GPU):
+//   1MN  gemm_sp_kernel with wave tile (MT, NT) = (M, N), one row of sp_tiles each: 135 = 192 x 320, 134 = 192 x 256, 124 = 128 x 256,
+//        132 = 192 x 128, 142 = 256 x 128, 144 = 256 x 256 GEGLU;
 //        +1000 when it runs on swapped operands (transposed output); +2000 when the residual enters through the matrix core (RESM: K tiles >
 //        sub-tiles of the wave tile; gemm_sp.h)
 //   210 / 220 / 230  wsgemm_kernel K = 320 / K = 640 / GEGLU
 //   301 / 302 / 303  gemm_kernel 64-column tiles / 256 x 128 / 128 x 128
-template <bool CONV, bool GEGLU, bool DRY>
-static int dispatch_any(GemmParams& p, hipStream_t stream, const int sp, const int force_nt, const int ncu) {
+// The gemm_sp_kernel tiles, one row per wave tile: sp_tile<.., MT, NT> derives the plan code, the tile shape, the eligibility test, the
+// RESM rule and the launcher from the same two numbers, so a row cannot name one tile and launch another.
+struct SpTile {
+  int code, bm, bn;                                               // 100 + 10 MT + NT; 64 MT rows x 64 NT columns
+  double t_k;                                                     // the model's time per 64-deep K tile, us (0: GEGLU has one tile, no model)
+  int pin;                                                        // the MD_GEMM_SP_NT value that pins it
+  bool (*eligible)(const GemmParams&);
+  bool (*resm)(const GemmParams&);                                // null: the GEGLU flavour takes no residual
+  void (*launch)(GemmParams&, bool resm, int ncu, hipStream_t);
+};
+template <bool CONV, bool GEGLU, int MT, int NT>
+static SpTile sp_tile(double t_k, int pin) {
+  return {100 + 10 * MT + NT, 64 * MT, 64 * NT, t_k, pin, sp_eligible<CONV, GEGLU, NT>, GEGLU ? nullptr : sp_resm<MT, NT>,
+          launch_sp<CONV, GEGLU, NT, MT>};
+}
+enum { T135, T134, T124, T142, T132, T144, SP_TILES };
+static const SpTile& sp_tiles(bool conv, int t) {
+  // t_k = 1.56 / 1.28 / 0.95 us per 64-deep K tile (15 / 12 / 8 MFMAs per k-step; profiles/r03_ab_gemm_sp_tiles.log)
+  static const double tk32 = md_env_int("MD_GEMM_SP_TK32", 800) * 1e-3;
+  static const SpTile rows[2][SP_TILES] = {
+      {sp_tile<false, false, 3, 5>(1.56, 5), sp_tile<false, false, 3, 4>(1.28, 4), sp_tile<false, false, 2, 4>(0.95, 2),
+       sp_tile<false, false, 4, 2>(0.95, 42), sp_tile<false, false, 3, 2>(tk32, 32), sp_tile<false, true, 4, 4>(0, 0)},
+      {sp_tile<true, false, 3, 5>(1.56, 5), sp_tile<true, false, 3, 4>(1.28, 4), sp_tile<true, false, 2, 4>(0.95, 2),
+       sp_tile<true, false, 4, 2>(0.95, 42), sp_tile<true, false, 3, 2>(tk32, 32), {}}};        // no GEGLU conv
+  return rows[conv][t];
+}
+
+// The model: rounds x (T0 + K tiles x t_k): rounds = ceil(tiles / CUs) of the persistent grid, T0 ~ 4 us per output tile outside its K loop.
+// N = 1280 on M = 18 432 tokens: 384 tiles of 192 x 320 are 1.5 rounds (2 paid), 480 tiles of 192 x 256 are 1.9;
+// on M = 4608 (the 12 x 12 level) 120 tiles of 192 x 256 leave half of the CUs idle, 180 tiles of 128 x 256 less than a third.
+static long sp_tile_count(const SpTile& t, const GemmParams& p) { return (long)cdiv(p.M, t.bm) * (p.N / t.bn); }
+static double sp_cost(const SpTile& t, const GemmParams& p, int ncu) {
+  return (double)cdiv(sp_tile_count(t, p), ncu) * (4.0 + (p.K / 64) * t.t_k);
+}
+
+// Transposed output (V^T of the attention kernels, bias only): gemm_sp_kernel on SWAPPED operands -- C^T[N][M] = W[N][K] . A[M][K]^T
+// is a plain GEMM whose "A" is the weight, whose "W" is the token matrix (row pitch K required) and whose bias runs along the
+// output rows; M must be a multiple of 256 (it is the swapped problem's N).
+static GemmParams gemm_swapped(const GemmParams& p) {
+  GemmParams q = p;
+  q.A = p.W; q.W = p.A; q.lda = p.K; q.M = p.N; q.N = p.M; q.transpose_out = 0; q.bias_rows = 1;
+  return q;
+}
+struct GemmKernel {                                               // one launch
+  int code = 0;                                                   // plan code; 2xx / 3xx name their flavour themselves
+  const SpTile* tile = nullptr;                                   // 1xx: the row of sp_tiles
+  bool swapped = false, resm = false;
+};
+struct GemmPlan {
+  GemmKernel k, tail;                                             // the problem or each full-size row block; the last block (k again if not split)
+  int blocks = 1, rows = 0;                                       // row blocks and rows per block (1, M: not split)
+  bool conv = false;
+  int ncu = 0;
+};
+static GemmKernel sp_kernel(const SpTile& t, const GemmParams& p, bool swapped) {
+  const bool resm = t.resm && t.resm(p);
+  return {t.code + (swapped ? 1000 : 0) + (resm ? 2000 : 0), &t, swapped, resm};
+}
+
+static GemmKernel gemm_choose_kernel(const GemmParams& p, const bool conv, const int sp, const int force_nt, const int ncu) {
   // Dispatch table, from same-box A/B runs on MI355X (profiles/r0*_ab_*.log).  One knob survives, used by the
   // parity tests: MD_GEMM_SP = 0 off | 1 every eligible problem | 2 automatic (default).  (The two-waves-per-SIMD ping-pong
   // kernels of rounds 1-2, gemm_pp.h, lost every shape they used to win to gemm_sp_kernel and were removed in round 3.)
-  // gemm_sp_kernel's tile: 256 x 256 for GEGLU; 192 x 320, 192 x 256 or 128 x 256 otherwise, whichever needs least time by the model
-  // rounds x (T0 + K tiles x t_k): rounds = ceil(tiles / CUs) of the persistent grid, T0 ~ 4 us per output tile outside its K loop,
-  // t_k = 1.56 / 1.28 / 0.95 us per 64-deep K tile (15 / 12 / 8 MFMAs per k-step; profiles/r03_ab_gemm_sp_tiles.log).
-  // N = 1280 on M = 18 432 tokens: 384 tiles of 192 x 320 are 1.5 rounds (2 paid), 480 tiles of 192 x 256 are 1.9;
-  // on M = 4608 (the 12 x 12 level) 120 tiles of 192 x 256 leave half of the CUs idle, 180 tiles of 128 x 256 less than a third.
-  // Transposed output (V^T of the attention kernels, bias only): the same kernel on SWAPPED operands -- C^T[N][M] = W[N][K] . A[M][K]^T
-  // is a plain GEMM whose "A" is the weight, whose "W" is the token matrix (row pitch K required) and whose bias runs along the
-  // output rows; M must be a multiple of 256 (it is the swapped problem's N).
-  if constexpr (!CONV && !GEGLU) {
-    if (p.transpose_out && sp > 0 && p.lda == p.K && p.act == ACT_NONE && !p.residual && !p.rowadd) {
-      GemmParams q = p;
-      q.A = p.W; q.W = p.A; q.lda = p.K; q.M = p.N; q.N = p.M; q.transpose_out = 0; q.bias_rows = 1;
-      if (sp_eligible<false, false, 4>(q)) {
-        auto cost = [&](int bm, double tk) {
-          const long tiles = (long)cdiv(q.M, bm) * (q.N / 256);
-          return (double)cdiv(tiles, ncu) * (4.0 + (q.K / 64) * tk);
-        };
-        const bool small = force_nt == 2 || (force_nt != 4 && cost(128, 0.95) < cost(192, 1.28));
-        const long tiles = (long)cdiv(q.M, small ? 128 : 192) * (q.N / 256);
-        if (sp == 1 || (tiles >= 112 && q.K >= 256)) {
-          if constexpr (!DRY) {
-            if (small) launch_sp<false, false, 4, 2>(q, stream);
-            else launch_sp<false, false, 4>(q, stream);
-          }
-          return small ? 1124 : 1134;
-        }
-      }
+  // gemm_sp_kernel's tile: 256 x 256 for GEGLU; 192 x 320, 192 x 256 or 128 x 256 otherwise, whichever needs least time by sp_cost.
+  const bool geglu = !conv && p.act == ACT_GEGLU;
+  auto tile = [&](int t) -> const SpTile& { return sp_tiles(conv, t); };
+  if (!conv && p.transpose_out && sp > 0 && p.lda == p.K && p.act == ACT_NONE && !p.residual && !p.rowadd) {
+    const GemmParams q = gemm_swapped(p);
+    if (tile(T134).eligible(q)) {
+      const bool small = force_nt == 2 || (force_nt != 4 && sp_cost(tile(T124), q, ncu) < sp_cost(tile(T134), q, ncu));
+      const SpTile& t = tile(small ? T124 : T134);
+      if (sp == 1 || (sp_tile_count(t, q) >= 112 && q.K >= 256)) return sp_kernel(t, q, true);
     }
   }
-  int nt = GEGLU ? 4 : 0;                                         // 5, 4: 192-row tiles; 2: 128 x 256
-  if constexpr (!GEGLU) {
-    auto cost = [&](int bm, int bn, double tk) {
-      const long tiles = (long)cdiv(p.M, bm) * (p.N / bn);
-      return (double)cdiv(tiles, ncu) * (4.0 + (p.K / 64) * tk);
-    };
-    const bool ok5 = (force_nt == 0 || force_nt == 5) && sp_eligible<CONV, false, 5>(p);
-    const bool ok4 = sp_eligible<CONV, false, 4>(p);
-    const double c5 = ok5 ? cost(192, 320, 1.56) : 1e30, c4 = ok4 && (force_nt == 0 || force_nt == 4) ? cost(192, 256, 1.28) : 1e30,
-                 c2 = ok4 && (force_nt == 0 || force_nt == 2) ? cost(128, 256, 0.95) : 1e30;
-    if (c5 < 1e30 || c4 < 1e30 || c2 < 1e30) nt = c5 <= c4 && c5 <= c2 ? 5 : (c4 <= c2 ? 4 : 2);
-    const bool ok128 = sp_eligible<CONV, false, 2>(p);
+  const SpTile* t = nullptr;
+  if (geglu) {
+    if (tile(T144).eligible(p)) t = &tile(T144);
+  } else {
+    auto cand = [&](int i) { return (force_nt == 0 || force_nt == tile(i).pin) && tile(i).eligible(p) ? sp_cost(tile(i), p, ncu) : 1e30; };
+    const double c5 = cand(T135), c4 = cand(T134), c2 = cand(T124);
+    if (c5 < 1e30 || c4 < 1e30 || c2 < 1e30) t = &tile(c5 <= c4 && c5 <= c2 ? T135 : (c4 <= c2 ? T134 : T124));
     // N a multiple of 128 only (the 128-channel convs of the AutoencoderKL at full resolution): the 256 x 128 tile, wave tile 128 x 64
-    const double c42 = ok128 && (force_nt == 0 || force_nt == 42) ? cost(256, 128, 0.95) : 1e30;
-    if (nt == 0 && c42 < 1e30) nt = 42;
+    const double c42 = cand(T142);
+    if (!t && c42 < 1e30) t = &tile(T142);
     // 192 x 128 (wave tile 96 x 64, 6 MFMAs per k-step): more and smaller tiles for the launches that cannot fill the chip once with
     // the larger ones -- the 12 x 12 level: M = 4608, N = 1280 gives 24 x 10 = 240 tiles on 256 CUs where 128 x 256 gives 180.
-    static const double tk32 = env_int("MD_GEMM_SP_TK32", 800) * 1e-3;
-    if (ok128 && (force_nt == 0 || force_nt == 32)) {
+    if ((force_nt == 0 || force_nt == 32) && tile(T132).eligible(p)) {
       const double best = std::min(std::min(c5, c42), std::min(c4, c2));
-      if (force_nt == 32 || cost(192, 128, tk32) < best) nt = 32;
+      if (force_nt == 32 || sp_cost(tile(T132), p, ncu) < best) t = &tile(T132);
     }
-  } else if (!sp_eligible<CONV, true>(p)) {
-    nt = 0;
   }
-  auto run_sp = [&]() {
-    if constexpr (!DRY) {
-      if constexpr (GEGLU) launch_sp<CONV, true>(p, stream);
-      else if (nt == 4) launch_sp<CONV, false, 4>(p, stream);
-      else if (nt == 2) launch_sp<CONV, false, 4, 2>(p, stream);
-      else if (nt == 42) launch_sp<CONV, false, 2, 4>(p, stream);
-      else if (nt == 32) launch_sp<CONV, false, 2, 3>(p, stream);
-      else launch_sp<CONV, false, 5>(p, stream);
-    }
-    if constexpr (GEGLU) return 144;
-    const bool resm = nt == 4 ? sp_resm<3, 4>(p) : (nt == 2 ? sp_resm<2, 4>(p) : (nt == 42 ? sp_resm<4, 2>(p) : (nt == 32 ? sp_resm<3, 2>(p) : sp_resm<3, 5>(p))));
-    return (resm ? 2000 : 0) + (nt == 4 ? 134 : (nt == 2 ? 124 : (nt == 42 ? 142 : (nt == 32 ? 132 : 135))));
-  };
-  if (sp == 1 && nt) return run_sp();
+  if (sp == 1 && t) return sp_kernel(*t, p, false);
   // 1. HBM-bound short-K projections on long token matrices: W-stationary streaming kernel (gemm_ws.h), plain and GEGLU (K = 320)
-  if constexpr (!CONV && !GEGLU) {
-    if (ws_eligible(p)) {
-      if constexpr (!DRY) {
-        if (p.K == 320) launch_ws<10, 5>(p, stream);
-        else launch_ws<20, 2>(p, stream);
-      }
-      return p.K == 320 ? 210 : 220;
-    }
-  }
-  if constexpr (!CONV && GEGLU) {
-    if (ws_geglu_eligible(p)) {
-      if constexpr (!DRY) launch_ws_geglu(p, stream);
-      return 230;
-    }
-  }
+  if (!conv && !geglu && ws_eligible(p)) return {p.K == 320 ? 210 : 220};
+  if (geglu && ws_geglu_eligible(p)) return {230};
   // 2. one-wave-per-SIMD flavour (gemm_sp.h), same-box table in profiles/r03_ab_gemm_sp_tiles.log: every 3x3 conv and every plain
   //    GEMM with K >= 640 that gives it at least 112 tiles (with the 192 x 256 tile the 12 x 12 level's 120 tiles run +15..25 % over
   //    the 128 x 128 kernel, M = 4608 GEMMs +1..18 %, M = 18 432 x N = 1280 +19..34 %); GEGLU GEMMs with K >= 640 (+24..29 %; at
   //    K = 320 the W-stationary kernel above is 9 % faster)
-  if (sp > 0 && nt) {
-    const long tiles = (long)cdiv(p.M, GEGLU || nt == 42 ? 256 : (nt == 2 ? 128 : 192)) * (p.N / (nt == 5 ? 320 : (nt == 42 || nt == 32 ? 128 : 256)));
-    const bool pick = GEGLU ? p.K >= 640 : (tiles >= 112 && (CONV || p.K >= 640));
-    if (pick) return run_sp();
-  }
+  if (sp > 0 && t && (geglu ? p.K >= 640 : (sp_tile_count(*t, p) >= 112 && (conv || p.K >= 640)))) return sp_kernel(*t, p, false);
   // 3. the occupancy flavours of gemm_kernel
-  if constexpr (!GEGLU) {
-    if (p.N <= 64) {                                              // 64-column tiles: conv_out (N = 4), MAN's first conv
-      if constexpr (!DRY) {
-        if (CONV) launch_variant<CONV, false, 1, 64, 2>(p, stream);
-        else launch_variant<CONV, false, 1, 64, 1, 2, 3>(p, stream);
-      }
-      return 301;
-    }
-  }
+  if (!geglu && p.N <= 64) return {301};                          // 64-column tiles: conv_out (N = 4), MAN's first conv
   // 256x128 tile, 4 waves x (128x64 per wave = 4x2 MFMA tiles, 8 independent accumulators), single 48-KiB stage, 2
   // workgroups/CU: 0.75 LDS fragment reads and 0.75x the DMA bytes per MFMA of the 128x128 tile.  Same-box A/B on MI355X:
   // +5..11 % on the 3x3 convs with >= 1024 such tiles and on every GEGLU GEMM, but slower on the HBM-bound skinny Linear GEMMs
   // and on the 24x24 / 12x12 convs (too few tiles to fill 256 CUs twice); plain Linear GEMMs only with a deep K loop
   const long tiles256 = (long)cdiv(p.M, 256) * cdiv(p.N, 128);
-  if (tiles256 >= 1024 && (CONV || GEGLU || p.K >= 2048)) {
-    if constexpr (!DRY) launch_variant<CONV, GEGLU, 2, 64, 1, 2, 2, 4>(p, stream);
-    return 302;
-  }
-  // 128x128: Linear GEMMs single 32-KiB stage at 3 workgroups/CU (occupancy hides the DMA latency), 3x3 convs a 2-deep ring
-  if constexpr (!DRY) {
-    if (CONV) launch_variant<CONV, GEGLU, 2, 64, 2>(p, stream);
-    else launch_variant<CONV, GEGLU, 2, 64, 1, 2, 3>(p, stream);
-  }
-  return 303;
+  if (tiles256 >= 1024 && (conv || geglu || p.K >= 2048)) return {302};
+  return {303};
 }
 
 // gemm_sp_kernel addresses A through a buffer descriptor with 32-bit byte offsets (< 2^31).  A token matrix beyond that (configs[4]:
@@ -860,50 +843,70 @@ static int sp_row_blocks(const GemmParams& p, int* rows_per_block) {
   return cdiv(p.M, rows);
 }
 
-// Row blocks are only worth their extra launches when the blocks really run on the sp kernel: the first (full-size) block is
-// dispatched DRY first; anything but a 1xx plan (N not a multiple of 256 / 320 / 128, too few tiles) leaves the GEMM whole, on the
-// multi-workgroup kernel that addresses A with 64-bit pointers.
-template <bool GEGLU>
-static int sp_row_block_plan(const GemmParams& p, int sp, int force_nt, int ncu, int* rows) {
-  const int nb = sp > 0 ? sp_row_blocks(p, rows) : 1;
-  if (nb <= 1) return 1;
+// The whole decision; launches nothing and touches no device.  Row blocks are only worth their extra launches when the blocks really run
+// on the sp kernel: anything but a 1xx choice for the first (full-size) block (N not a multiple of 256 / 320 / 128, too few tiles) leaves
+// the GEMM whole, on the multi-workgroup kernel that addresses A with 64-bit pointers.  The shorter last block is chosen on its own M
+// (same rules, possibly a smaller tile); a block starts a multiple of 3840 rows in, so every operand keeps its alignment.
+static GemmPlan gemm_choose(const GemmParams& p, bool conv, int sp, int force_nt, int ncu) {
+  GemmPlan plan;
+  plan.conv = conv; plan.ncu = ncu; plan.rows = p.M;
+  int rows;
+  const int nb = !conv && sp > 0 ? sp_row_blocks(p, &rows) : 1;
   GemmParams c = p;
-  c.M = *rows;
-  const int plan = dispatch_any<false, GEGLU, true>(c, nullptr, sp, force_nt, ncu);
-  return plan % 1000 / 100 == 1 ? nb : 1;      // 1xx, with or without the +2000 of the residual-through-the-matrix-core flavour
+  if (nb > 1) {
+    c.M = rows;
+    plan.k = gemm_choose_kernel(c, false, sp, force_nt, ncu);
+    if (plan.k.tile) {
+      plan.blocks = nb; plan.rows = rows;
+      c.M = p.M - (nb - 1) * rows;
+      plan.tail = c.M == rows ? plan.k : gemm_choose_kernel(c, false, sp, force_nt, ncu);
+      return plan;
+    }
+  }
+  plan.k = plan.tail = gemm_choose_kernel(p, conv, sp, force_nt, ncu);
+  return plan;
 }
 
 template <bool CONV, bool GEGLU>
-static void launch_any(GemmParams& p, hipStream_t stream) {
-  static const int sp = env_int("MD_GEMM_SP", 2);
-  static const int force_nt = env_int("MD_GEMM_SP_NT", 0);        // A/B runs only: 5 / 4 / 2 / 32 / 42 pin 192x320 / 192x256 / 128x256 / 192x128 / 256x128
-  if constexpr (!CONV) {
-    int rows;
-    const int nb = sp_row_block_plan<GEGLU>(p, sp, force_nt, md_device_cus(), &rows);
-    if (nb > 1) {
-      for (int b = 0; b < nb; ++b) {
-        GemmParams c = p;
-        const size_t off = (size_t)b * rows;
-        c.A = p.A + off * p.lda;
-        c.C = p.C + off * p.ldc;
-        if (p.residual) c.residual = p.residual + off * p.ldr;
-        c.M = b + 1 < nb ? rows : p.M - (int)off;
-        dispatch_any<false, GEGLU, false>(c, stream, sp, force_nt, md_device_cus());
-      }
-      return;
-    }
+static void launch_occupancy(int code, GemmParams& p, hipStream_t stream) {
+  if constexpr (!GEGLU) {
+    if (code == 301) return CONV ? launch_variant<CONV, false, 1, 64, 2>(p, stream) : launch_variant<CONV, false, 1, 64, 1, 2, 3>(p, stream);
   }
-  dispatch_any<CONV, GEGLU, false>(p, stream, sp, force_nt, md_device_cus());
+  if (code == 302) return launch_variant<CONV, GEGLU, 2, 64, 1, 2, 2, 4>(p, stream);
+  // 128x128: Linear GEMMs single 32-KiB stage at 3 workgroups/CU (occupancy hides the DMA latency), 3x3 convs a 2-deep ring
+  return CONV ? launch_variant<CONV, GEGLU, 2, 64, 2>(p, stream) : launch_variant<CONV, GEGLU, 2, 64, 1, 2, 3>(p, stream);
 }
-
+static void gemm_launch_kernel(const GemmKernel& k, bool conv, int ncu, GemmParams& p, hipStream_t stream) {
+  if (k.tile) {
+    GemmParams q = k.swapped ? gemm_swapped(p) : p;
+    return k.tile->launch(q, k.resm, ncu, stream);
+  }
+  if (k.code == 210) return launch_ws<10, 5>(p, stream);
+  if (k.code == 220) return launch_ws<20, 2>(p, stream);
+  if (k.code == 230) return launch_ws_geglu(p, stream);
+  if (conv) launch_occupancy<true, false>(k.code, p, stream);
+  else if (p.act == ACT_GEGLU) launch_occupancy<false, true>(k.code, p, stream);
+  else launch_occupancy<false, false>(k.code, p, stream);
+}
+static void gemm_launch(const GemmPlan& plan, GemmParams& p, hipStream_t stream) {
+  for (int b = 0; b < plan.blocks; ++b) {
+    GemmParams c = p;
+    const size_t off = (size_t)b * plan.rows;
+    c.A = p.A + off * p.lda;
+    c.C = p.C + off * p.ldc;
+    if (p.residual) c.residual = p.residual + off * p.ldr;
+    c.M = b + 1 < plan.blocks ? plan.rows : p.M - (int)off;
+    gemm_launch_kernel(b + 1 < plan.blocks ? plan.k : plan.tail, plan.conv, plan.ncu, c, stream);
+  }
+}
 
 static int launch_gemm(GemmParams& p, bool conv, hipStream_t stream) {
   MD_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0, "md_gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
   MD_CHECK_ARG(p.K % 64 == 0, "md_gemm: K=%d must be a multiple of 64 (pad channels when packing)", p.K);
-  MD_CHECK_ARG((reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.W) & 15) == 0, "md_gemm: A/W must be 16-byte aligned");
+  MD_CHECK_ARG(al16(p.A) && al16(p.W), "md_gemm: A/W must be 16-byte aligned");
   MD_CHECK_ARG(conv || p.lda % 8 == 0, "md_gemm: lda=%d must be a multiple of 8", p.lda);
   if (p.act == ACT_GEGLU) {
-    MD_CHECK_ARG(p.N % 64 == 0 && !p.transpose_out && !p.residual && !p.rowadd && p.ldc % 8 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0,
+    MD_CHECK_ARG(p.N % 64 == 0 && !p.transpose_out && !p.residual && !p.rowadd && p.ldc % 8 == 0 && al16(p.C),
                  "md_gemm: GEGLU needs N %% 64 == 0 (N=%d), ldc %% 8 == 0, a 16-byte aligned output and no residual/rowadd/transpose", p.N);
   }
   if (p.transpose_out) MD_CHECK_ARG(!p.residual && !p.rowadd && p.act == ACT_NONE, "md_gemm: transposed store supports bias only");
@@ -924,12 +927,9 @@ static int launch_gemm(GemmParams& p, bool conv, hipStream_t stream) {
   } else if (p.residual) {
     MD_CHECK_ARG(p.ldr == p.ldc, "md_gemm: in-place residual needs ldr == ldc");
   }
-  if (conv)
-    launch_any<true, false>(p, stream);
-  else if (p.act == ACT_GEGLU)
-    launch_any<false, true>(p, stream);
-  else
-    launch_any<false, false>(p, stream);
+  static const int sp = md_env_int("MD_GEMM_SP", 2);
+  static const int force_nt = md_env_int("MD_GEMM_SP_NT", 0);     // A/B runs only: 5 / 4 / 2 / 32 / 42 pin 192x320 / 192x256 / 128x256 / 192x128 / 256x128
+  gemm_launch(gemm_choose(p, conv, sp, force_nt, md_device_cus()), p, stream);
   MD_CHECK_LAUNCH("md_gemm");
   return MD_OK;
 }
@@ -992,35 +992,31 @@ extern "C" int md_conv_nhwc_f16(const void* X, int ldx, const void* W, void* Y, 
 // Which kernel the AUTOMATIC dispatch (MD_GEMM_SP = 2, no pinned tile) picks for a problem on a chip with `ncu` compute units; nothing
 // is launched and no device is touched, so the table is pinned by CPU tests (tests/test_host_cpu.py).  epi: bit 0 residual, bit 1
 // row-broadcast operand, bit 2 bias.  Operands are taken as 16-byte aligned with dense rows (lda = K, ldc = N or M).
-static const half_t* plan_ptr(int which) { return reinterpret_cast<const half_t*>((uintptr_t)0x100000 * (which + 1)); }
+static void plan_operands(GemmParams& p, int epi) {                // aligned dummies: gemm_choose reads alignment, never memory
+  alignas(16) static half_t dummy[8];
+  p.A = p.W = p.C = dummy;
+  p.residual = (epi & 1) ? dummy : nullptr; p.rowadd = (epi & 2) ? dummy : nullptr; p.bias = (epi & 4) ? dummy : nullptr;
+}
 
 extern "C" int md_gemm_plan(int M, int N, int K, int act, int transpose_out, int epi, int ncu) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 64 || ncu <= 0) return MD_ERR_ARG;
   GemmParams p = {};
-  p.A = plan_ptr(0); p.W = plan_ptr(1); p.C = const_cast<half_t*>(plan_ptr(2));
-  p.residual = (epi & 1) ? plan_ptr(3) : nullptr; p.rowadd = (epi & 2) ? plan_ptr(4) : nullptr; p.bias = (epi & 4) ? plan_ptr(5) : nullptr;
+  plan_operands(p, epi);
   p.M = M; p.N = N; p.K = K; p.lda = K; p.ldc = transpose_out ? M : (act == ACT_GEGLU ? N / 2 : N); p.ldr = N; p.ldra = N;
   p.rows_per_group = M; p.act = act; p.transpose_out = transpose_out;
   // a token matrix beyond 2^31 bytes runs in row blocks when they take the sp kernel: the plan returned is that of the FIRST (full-size)
   // block; the shorter last block is dispatched on its own (same rule, possibly a smaller tile) -- query it with its own M
-  int rows;
-  if (act == ACT_GEGLU) {
-    if (sp_row_block_plan<true>(p, 2, 0, ncu, &rows) > 1) p.M = rows;
-    return dispatch_any<false, true, true>(p, nullptr, 2, 0, ncu);
-  }
-  if (sp_row_block_plan<false>(p, 2, 0, ncu, &rows) > 1) p.M = rows;
-  return dispatch_any<false, false, true>(p, nullptr, 2, 0, ncu);
+  return gemm_choose(p, false, 2, 0, ncu).k.code;
 }
 
 extern "C" int md_conv3x3_plan(int B, int Hin, int Win, int Cin, int Cout, int stride, int upsample, int epi, int ncu) {
   if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cin % 64 || Cout <= 0 || ncu <= 0 || (stride != 1 && stride != 2) || (upsample && stride != 1)) return MD_ERR_ARG;
   GemmParams p = {};
-  p.A = plan_ptr(0); p.W = plan_ptr(1); p.C = const_cast<half_t*>(plan_ptr(2));
-  p.residual = (epi & 1) ? plan_ptr(3) : nullptr; p.rowadd = (epi & 2) ? plan_ptr(4) : nullptr; p.bias = (epi & 4) ? plan_ptr(5) : nullptr;
+  plan_operands(p, epi);
   p.ldc = Cout; p.ldr = Cout; p.ldra = Cout; p.lda = Cin;
   p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.stride = stride; p.upsample = upsample; p.pad = 1; p.ldx = Cin; p.kw = 3;
   p.Hout = ((Hin << upsample) + 2 - 3) / stride + 1;
   p.Wout = ((Win << upsample) + 2 - 3) / stride + 1;
   p.M = B * p.Hout * p.Wout; p.N = Cout; p.K = 9 * Cin; p.rows_per_group = p.Hout * p.Wout; p.act = ACT_NONE;
-  return dispatch_any<true, false, true>(p, nullptr, 2, 0, ncu);
+  return gemm_choose(p, true, 2, 0, ncu).k.code;
 }

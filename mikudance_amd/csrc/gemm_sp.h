@@ -684,10 +684,9 @@ __global__ __launch_bounds__(256, 1) void gemm_sp_kernel(GemmParams p) {
 #endif
 }
 
-template <bool CONV, bool GEGLU, int NT = GEGLU ? 4 : 5>
+template <bool CONV, bool GEGLU, int NT>
 static bool sp_eligible(const GemmParams& p) {
   constexpr int BN = 64 * NT;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   // N <= 16384: the zero page standing in for absent column operands; the row-bias form (swapped operands) has no column operands
   if (p.transpose_out || p.N % BN != 0 || p.K % 64 != 0 || p.K < 128 || (p.N > 16384 && !p.bias_rows)) return false;
   if (p.bias_rows && (p.residual || p.rowadd || CONV || GEGLU)) return false;
@@ -713,8 +712,9 @@ static bool sp_resm(const GemmParams& p) {
          ((unsigned long long)(p.M - 1) * p.ldr + p.N) * 2 < (1ull << 31);
 }
 
-template <bool CONV, bool GEGLU, int NT = GEGLU ? 4 : 5, int MT = GEGLU ? 4 : 3>
-static void launch_sp(GemmParams& p, hipStream_t stream) {
+// resm and ncu come from the plan (gemm.hip gemm_choose): the launcher decides nothing about the kernel
+template <bool CONV, bool GEGLU, int NT, int MT>
+static void launch_sp(GemmParams& p, bool resm, int ncu, hipStream_t stream) {
   constexpr int BM = 64 * MT, BN = 64 * NT;
 #ifdef SP_TRACE
   constexpr size_t smem = (size_t)(3 * BM + 2 * BN) * 128 + (GEGLU ? 0 : 4 * SP_TRACE_N * 5 * 8);
@@ -736,10 +736,9 @@ static void launch_sp(GemmParams& p, hipStream_t stream) {
   static const int rev = md_env_int("MD_SP_REVERSE", 1);
   const bool big_a = (size_t)p.M * (size_t)p.lda * 2 > ((size_t)256 << 20);
   p.reverse = !CONV && !GEGLU && !p.bias_rows && big_a && (rev == 2 || (rev == 1 && p.K >= 4 * p.N));
-  const int ncu = md_device_cus();
   const int grid = p.tiles_total < ncu ? p.tiles_total : ncu;
   if constexpr (!GEGLU) {
-    if (sp_resm<MT, NT>(p)) {
+    if (resm) {
       md_ensure_dynamic_lds<gemm_sp_kernel<CONV, false, MT, NT, true>>((int)smem);
       hipLaunchKernelGGL((gemm_sp_kernel<CONV, false, MT, NT, true>), dim3(grid), dim3(256), smem, stream, p);
       return;

@@ -216,6 +216,48 @@ def test_gemm_and_conv_dispatch_table_of_the_benchmark_shapes():
     assert lib.md_gemm_plan(18432, 1280, 1280, 0, 0, 5, 192) in (2134, 2135, 2124)
 
 
+def _gemm_and_conv_plans_over_the_grid(lib):
+    """Every code md_gemm_plan / md_conv3x3_plan return over the grid below, one flat list per query in iteration order."""
+    from itertools import product
+    from mikudance_amd import ops
+    ncus = (256, 192, 64)
+    gemm = [lib.md_gemm_plan(M_, N, K, act, tr, epi, ncu)
+            for M_, N, K, act, tr, epi, ncu in product(
+                (4608, 18432, 294912, 983040), (4, 128, 320, 1280, 10240),
+                (64, 100, 128, 320, 640, 1280, 2560, 5120), (ops.ACT_NONE, ops.ACT_GEGLU), (0, 1), range(8), ncus)]
+    pairs = ((320, 320), (640, 320), (960, 320), (640, 640), (1920, 640), (1280, 1280), (2560, 1280), (320, 4), (64, 320), (64, 128),
+             (128, 128), (128, 256), (256, 256), (60, 320))
+    conv = [lib.md_conv3x3_plan(B, H, H, cin, cout, st, up, epi, ncu)
+            for B, H, (cin, cout), st, up, epi, ncu in product(
+                (2, 32), (12, 24, 96, 768), pairs, (1, 2), (0, 1), (0, 4, 5, 7), ncus)]
+    return {"gemm": gemm, "conv": conv}
+
+
+def test_gemm_and_conv_dispatch_over_a_grid_matches_the_recording(golden_dir):
+    """The decisions of the GEMM / 3x3-conv dispatch (gemm.hip gemm_choose, through md_gemm_plan / md_conv3x3_plan: no device touched) over a
+    grid of 15 360 GEMM and 5 376 conv problems on 256, 192 and 64 compute units: every K, activation, output form, epilogue and (Cin, Cout)
+    pair of the wider grid that profiles/gemm_dispatch_refactor.log compared once (10 M x 13 N; 5 B x 8 H), with M, N, B and H thinned to
+    the levels of the clip (12 x 12, 24 x 24, 96 x 96, the 983 040-token matrix that runs in row blocks) so that the recording stays
+    readable in a diff.  The recording was taken at the last commit whose dispatcher decided and launched in one function (the one before gemm_choose), with
+
+        from mikudance_amd import _lib; from tests.test_host_cpu import _gemm_and_conv_plans_over_the_grid as grid
+        g = grid(_lib.load()); rows = lambda v, n: ",\n".join(",".join(map(str, v[i:i + n])) for i in range(0, len(v), n))
+        open("tests/golden/gemm_plans.json", "w").write('{"gemm":[\n%s],\n"conv":[\n%s]}\n' % (rows(g["gemm"], 96), rows(g["conv"], 96)))
+
+    and holds every code the table above names plus 302 and the argument error: a change of a rule, a tie-break or a tile's row shows here
+    as the first problem that moved.  Record again only with a measurement that justifies the new decision."""
+    from mikudance_amd import _lib
+    want = json.load(open(os.path.join(golden_dir, "gemm_plans.json")))
+    got = _gemm_and_conv_plans_over_the_grid(_lib.load())
+    assert len(want["gemm"]) == 15360 and len(want["conv"]) == 5376
+    for q in ("gemm", "conv"):
+        assert len(got[q]) == len(want[q])
+        moved = [i for i, (g, w) in enumerate(zip(got[q], want[q])) if g != w]
+        assert not moved, (q, len(moved), "first at flat index", moved[0], "got", got[q][moved[0]], "recorded", want[q][moved[0]])
+    seen = set(want["gemm"]) | set(want["conv"])
+    assert {135, 134, 124, 132, 142, 144, 1124, 1134, 2135, 2134, 2132, 210, 220, 230, 301, 302, 303} <= seen and min(seen) < 0
+
+
 def test_attention_dispatch_table():
     """md_attention_plan runs the decision code of md_attention_fwd_f16 (launch_attn / launch_attn2 / attn2s_eligible) without touching a
     device: 400 = generic attn_kernel, 414 / 418 = attn2 DMA ring with 4 / 8 waves, 420 = attn2s (K / V^T resident in LDS).  Pinned: the
