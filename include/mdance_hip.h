@@ -373,6 +373,19 @@ int md_set_cu_limit(int ncu);
 int md_gemm_plan(int M, int N, int K, int act, int transpose_out, int epi, int ncu);
 int md_conv3x3_plan(int B, int Hin, int Win, int Cin, int Cout, int stride, int upsample, int epi, int ncu);
 
+/* The same question for a call AS IT IS MADE: the arguments of md_gemm_f16 / md_conv_nhwc_f16 without the stream.  They run what the launch
+ * runs up to, but not including, the launch itself: the same argument checks (the negative code the launch would return comes back), the
+ * same MD_GEMM_SP / MD_GEMM_SP_NT values (read once per process), the CU count of the current device or of md_set_cu_limit (256 without
+ * a device).  So a misaligned or sliced operand, an activation, a pinned tile or a CU limit shows in the answer.  Pointer values and pitches
+ * are read, memory is not; nothing is launched.  Returns the plan code (as md_gemm_plan); when the token matrix runs in row blocks the code
+ * is that of each full-size block, *blocks (> 1) their number and *tail_code the code of the shorter last block (both may be NULL). */
+int md_gemm_plan_call(const void* A, int lda, const void* W, void* C, int ldc, int M, int N, int K, const void* bias,
+                      const void* residual, int ldr, const void* rowadd, int ldra, int rows_per_group, int act,
+                      int transpose_out, int* blocks, int* tail_code);
+int md_conv_plan_call(const void* X, int ldx, const void* W, void* Y, int ldy, int B, int Hin, int Win, int Cin, int Cout, int kw,
+                      int stride, int upsample, int pad_lo, const void* bias, const void* residual, int ldr, const void* rowadd,
+                      int ldra, int rows_per_group, int act);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,10 @@ SIGNATURES = {
     "md_set_cu_limit": (c_int, [c_int]),
     "md_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "md_conv3x3_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "md_gemm_plan_call": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P, P, c_int, P, c_int, c_int, c_int, c_int,
+                                  ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "md_conv_plan_call": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P,
+                                  c_int, c_int, c_int]),
     "md_softmax_rows_f16": (c_int, [P, c_int, c_int, c_int, c_float, P]),
     "md_groupnorm_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "md_groupnorm_nhwc_f16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, c_size_t, P]),

@@ -900,7 +900,16 @@ static void gemm_launch(const GemmPlan& plan, GemmParams& p, hipStream_t stream)
   }
 }
 
-static int launch_gemm(GemmParams& p, bool conv, hipStream_t stream) {
+// MD_GEMM_SP / MD_GEMM_SP_NT, read once per process; the launch and the plan queries below share this one reading.
+static void gemm_knobs(int* sp, int* force_nt) {
+  static const int sp_ = md_env_int("MD_GEMM_SP", 2);
+  static const int force_nt_ = md_env_int("MD_GEMM_SP_NT", 0);    // A/B runs only: 5 / 4 / 2 / 32 / 42 pin 192x320 / 192x256 / 128x256 / 192x128 / 256x128
+  *sp = sp_; *force_nt = force_nt_;
+}
+
+// Everything launch_gemm does before gemm_launch: the argument checks, the knobs, the CU count (md_set_cu_limit honoured) and gemm_choose.
+// Reads pointer values and pitches, never memory; md_gemm_plan_call / md_conv_plan_call stop here.
+static int gemm_plan_checked(const GemmParams& p, bool conv, GemmPlan* plan) {
   MD_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0, "md_gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
   MD_CHECK_ARG(p.K % 64 == 0, "md_gemm: K=%d must be a multiple of 64 (pad channels when packing)", p.K);
   MD_CHECK_ARG(al16(p.A) && al16(p.W), "md_gemm: A/W must be 16-byte aligned");
@@ -927,26 +936,42 @@ static int launch_gemm(GemmParams& p, bool conv, hipStream_t stream) {
   } else if (p.residual) {
     MD_CHECK_ARG(p.ldr == p.ldc, "md_gemm: in-place residual needs ldr == ldc");
   }
-  static const int sp = md_env_int("MD_GEMM_SP", 2);
-  static const int force_nt = md_env_int("MD_GEMM_SP_NT", 0);     // A/B runs only: 5 / 4 / 2 / 32 / 42 pin 192x320 / 192x256 / 128x256 / 192x128 / 256x128
-  gemm_launch(gemm_choose(p, conv, sp, force_nt, md_device_cus()), p, stream);
+  int sp, force_nt;
+  gemm_knobs(&sp, &force_nt);
+  *plan = gemm_choose(p, conv, sp, force_nt, md_device_cus());
+  return MD_OK;
+}
+
+static int launch_gemm(GemmParams& p, bool conv, hipStream_t stream) {
+  GemmPlan plan;
+  const int rc = gemm_plan_checked(p, conv, &plan);
+  if (rc != MD_OK) return rc;
+  gemm_launch(plan, p, stream);
   MD_CHECK_LAUNCH("md_gemm");
   return MD_OK;
 }
 
-extern "C" int md_gemm_f16(const void* A, int lda, const void* W, void* C, int ldc, int M, int N, int K, const void* bias, const void* residual,
-                           int ldr, const void* rowadd, int ldra, int rows_per_group, int act, int transpose_out, void* stream) {
+// The problem of md_gemm_f16 / md_gemm_plan_call, built once: the query cannot describe another problem than the launch.
+static GemmParams gemm_params(const void* A, int lda, const void* W, void* C, int ldc, int M, int N, int K, const void* bias, const void* residual,
+                              int ldr, const void* rowadd, int ldra, int rows_per_group, int act, int transpose_out) {
   GemmParams p = {};
   p.A = (const half_t*)A; p.W = (const half_t*)W; p.C = (half_t*)C;
   p.bias = (const half_t*)bias; p.residual = (const half_t*)residual; p.rowadd = (const half_t*)rowadd;
   p.lda = lda; p.ldc = ldc; p.ldr = ldr; p.ldra = ldra;
   p.M = M; p.N = N; p.K = K; p.rows_per_group = rows_per_group; p.act = act; p.transpose_out = transpose_out; p.bias_rows = 0;
+  return p;
+}
+
+extern "C" int md_gemm_f16(const void* A, int lda, const void* W, void* C, int ldc, int M, int N, int K, const void* bias, const void* residual,
+                           int ldr, const void* rowadd, int ldra, int rows_per_group, int act, int transpose_out, void* stream) {
+  GemmParams p = gemm_params(A, lda, W, C, ldc, M, N, K, bias, residual, ldr, rowadd, ldra, rows_per_group, act, transpose_out);
   return launch_gemm(p, false, (hipStream_t)stream);
 }
 
-static int conv_common(const void* X, int ldx, const void* W, void* Y, int ldy, int B, int Hin, int Win, int Cin, int Cout, int kw, int stride,
-                       int upsample, int pad_lo, const void* bias, const void* residual, int ldr, const void* rowadd, int ldra,
-                       int rows_per_group, int act, void* stream) {
+// The problem of md_conv*_nhwc_f16 / md_conv_plan_call (argument checks of the conv form included), built once for both.
+static int conv_params(GemmParams* out, const void* X, int ldx, const void* W, void* Y, int ldy, int B, int Hin, int Win, int Cin, int Cout, int kw,
+                       int stride, int upsample, int pad_lo, const void* bias, const void* residual, int ldr, const void* rowadd, int ldra,
+                       int rows_per_group, int act) {
   MD_CHECK_ARG(Cin % 64 == 0, "md_conv3x3: Cin=%d must be a multiple of 64 (zero-pad channels when packing)", Cin);
   MD_CHECK_ARG(ldx >= Cin && ldx % 8 == 0, "md_conv3x3: ldx=%d must be a multiple of 8 and >= Cin=%d", ldx, Cin);
   MD_CHECK_ARG(stride == 1 || stride == 2, "md_conv3x3: stride must be 1 or 2");
@@ -967,6 +992,17 @@ static int conv_common(const void* X, int ldx, const void* W, void* Y, int ldy, 
   MD_CHECK_ARG(p.Hout > 0 && p.Wout > 0, "md_conv3x3: empty output %dx%d", p.Hout, p.Wout);
   p.M = B * p.Hout * p.Wout; p.N = Cout; p.K = 3 * kw * Cin;
   p.rows_per_group = rows_per_group; p.act = act; p.transpose_out = 0;
+  *out = p;
+  return MD_OK;
+}
+
+static int conv_common(const void* X, int ldx, const void* W, void* Y, int ldy, int B, int Hin, int Win, int Cin, int Cout, int kw, int stride,
+                       int upsample, int pad_lo, const void* bias, const void* residual, int ldr, const void* rowadd, int ldra,
+                       int rows_per_group, int act, void* stream) {
+  GemmParams p;
+  const int rc = conv_params(&p, X, ldx, W, Y, ldy, B, Hin, Win, Cin, Cout, kw, stride, upsample, pad_lo, bias, residual, ldr, rowadd, ldra,
+                             rows_per_group, act);
+  if (rc != MD_OK) return rc;
   return launch_gemm(p, true, (hipStream_t)stream);
 }
 
@@ -1019,4 +1055,33 @@ extern "C" int md_conv3x3_plan(int B, int Hin, int Win, int Cin, int Cout, int s
   p.Wout = ((Win << upsample) + 2 - 3) / stride + 1;
   p.M = B * p.Hout * p.Wout; p.N = Cout; p.K = 9 * Cin; p.rows_per_group = p.Hout * p.Wout; p.act = ACT_NONE;
   return gemm_choose(p, true, 2, 0, ncu).k.code;
+}
+
+// Which kernel THIS call would run: the arguments of md_gemm_f16 / md_conv_nhwc_f16 without the stream, through the same checks, knobs
+// (MD_GEMM_SP, MD_GEMM_SP_NT) and CU count (md_set_cu_limit) as the launch, up to but not including it.  Returns the plan code of the
+// problem (of each full-size row block when it is split; then *blocks > 1 and *tail_code is the last block's), or the negative error
+// the launch would return.  Pointer values and pitches are read, memory is not; nothing is launched.
+static int plan_call_result(const GemmParams& p, bool conv, int* blocks, int* tail_code) {
+  GemmPlan plan;
+  const int rc = gemm_plan_checked(p, conv, &plan);
+  if (rc != MD_OK) return rc;
+  if (blocks) *blocks = plan.blocks;
+  if (tail_code) *tail_code = plan.tail.code;
+  return plan.k.code;
+}
+
+extern "C" int md_gemm_plan_call(const void* A, int lda, const void* W, void* C, int ldc, int M, int N, int K, const void* bias, const void* residual,
+                                 int ldr, const void* rowadd, int ldra, int rows_per_group, int act, int transpose_out, int* blocks,
+                                 int* tail_code) {
+  return plan_call_result(gemm_params(A, lda, W, C, ldc, M, N, K, bias, residual, ldr, rowadd, ldra, rows_per_group, act, transpose_out), false,
+                          blocks, tail_code);
+}
+
+extern "C" int md_conv_plan_call(const void* X, int ldx, const void* W, void* Y, int ldy, int B, int Hin, int Win, int Cin, int Cout, int kw, int stride,
+                                 int upsample, int pad_lo, const void* bias, const void* residual, int ldr, const void* rowadd, int ldra,
+                                 int rows_per_group, int act) {
+  GemmParams p;
+  const int rc = conv_params(&p, X, ldx, W, Y, ldy, B, Hin, Win, Cin, Cout, kw, stride, upsample, pad_lo, bias, residual, ldr, rowadd, ldra,
+                             rows_per_group, act);
+  return rc != MD_OK ? rc : plan_call_result(p, true, nullptr, nullptr);
 }

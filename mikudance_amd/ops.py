@@ -1,6 +1,8 @@
 """Thin tensor-level wrappers over the C ABI (include/mdance_hip.h).  PyTorch supplies device memory and the
 stream; all arithmetic happens in the HIP kernels.  Every function requires CUDA(ROCm) fp16 tensors and raises
 otherwise -- there is no eager/CPU fallback."""
+import ctypes
+
 import torch
 
 from . import _lib
@@ -57,9 +59,8 @@ def _pixel_pitch(x, name, align=8):
     return ld
 
 
-def gemm(a, w, bias=None, residual=None, rowadd=None, rows_per_group=0, act=ACT_NONE, transpose_out=False, out=None,
-         ldc_t=None):
-    """out[M, N] = epi(a[M, K] @ w[N, K]^T).  transpose_out: out is [N, ldc_t] (V^T for attention)."""
+def _gemm_args(a, w, bias, residual, rowadd, rows_per_group, act, transpose_out, out, ldc_t):
+    """The argument list of md_gemm_f16 up to the stream (md_gemm_plan_call takes the same one) and the output tensor."""
     lda = _rowmajor(a, "a")
     _chk(w, "w")
     M, K = a.shape
@@ -74,20 +75,34 @@ def gemm(a, w, bias=None, residual=None, rowadd=None, rows_per_group=0, act=ACT_
     ldr = _rowmajor(residual, "residual") if residual is not None else 0
     ldra = _rowmajor(rowadd, "rowadd") if rowadd is not None else 0
     _chk(bias, "bias")
-    _lib.call("md_gemm_f16", a.data_ptr(), lda, w.data_ptr(), out.data_ptr(), ldc, M, N, K, _p(bias), _p(residual), ldr,
-              _p(rowadd), ldra, rows_per_group, act, int(transpose_out), _st(),
+    return (a.data_ptr(), lda, w.data_ptr(), out.data_ptr(), ldc, M, N, K, _p(bias), _p(residual), ldr, _p(rowadd), ldra, rows_per_group,
+            act, int(transpose_out)), out
+
+
+def gemm(a, w, bias=None, residual=None, rowadd=None, rows_per_group=0, act=ACT_NONE, transpose_out=False, out=None,
+         ldc_t=None):
+    """out[M, N] = epi(a[M, K] @ w[N, K]^T).  transpose_out: out is [N, ldc_t] (V^T for attention)."""
+    args, out = _gemm_args(a, w, bias, residual, rowadd, rows_per_group, act, transpose_out, out, ldc_t)
+    M, N, K = args[5:8]
+    _lib.call("md_gemm_f16", *args, _st(),
               meta=(f"gemm M={M} N={N} K={K}" + (" geglu" if act == ACT_GEGLU else "") + (" T" if transpose_out else ""),
                     2.0 * M * N * K, 2.0 * (M * K + N * K + M * N)))
     return out
 
 
-def conv3x3(x, w, cout, bias=None, residual=None, rowadd=None, rows_per_group=0, act=ACT_NONE, stride=1, upsample=False,
-            out=None, pad_lo=1, kw=3):
-    """x: (B, H, W, Cin) NHWC (contiguous or a channel slice: see _pixel_pitch); w: [Cout, 3*kw*Cin] packed (ky, kx, cin);
-    returns (B, Ho, Wo, Cout).
-    pad_lo=0 (stride 2 only): zero padding (0,1,0,1) instead of 1 all round (the AutoencoderKL downsampler).
-    kw=1: a 3 x 1 filter (taps along H only; Conv3d (3,1,1) of the temporal VAE decoder with H = frames, W = pixels).
-    `out` may be a channel slice of a wider NHWC tensor (row pitch = its last-dim stride)."""
+def gemm_plan(a, w, bias=None, residual=None, rowadd=None, rows_per_group=0, act=ACT_NONE, transpose_out=False, out=None,
+              ldc_t=None, blocks=False):
+    """The plan code (include/mdance_hip.h: md_gemm_plan) of the kernel ops.gemm would run for these very tensors and keywords, under the
+    process's MD_GEMM_SP / MD_GEMM_SP_NT and CU limit; nothing is launched.  A negative code is the error the call would raise with.
+    blocks=True: (code, row blocks, code of the last block)."""
+    args, _ = _gemm_args(a, w, bias, residual, rowadd, rows_per_group, act, transpose_out, out, ldc_t)
+    nb, tail = ctypes.c_int(1), ctypes.c_int(0)
+    code = _lib.load().md_gemm_plan_call(*args, ctypes.byref(nb), ctypes.byref(tail))
+    return (code, nb.value, tail.value) if blocks else code
+
+
+def _conv_args(x, w, cout, bias, residual, rowadd, rows_per_group, act, stride, upsample, out, pad_lo, kw):
+    """The argument list of md_conv_nhwc_f16 up to the stream (md_conv_plan_call takes the same one), the output tensor and (Ho, Wo)."""
     _chk(w, "w")
     assert x.dim() == 4
     ldx = _pixel_pitch(x, "x")
@@ -103,11 +118,30 @@ def conv3x3(x, w, cout, bias=None, residual=None, rowadd=None, rows_per_group=0,
     ldr = _rowmajor(r2, "residual") if r2 is not None else 0
     ldra = _rowmajor(rowadd, "rowadd") if rowadd is not None else 0
     _chk(bias, "bias")
-    _lib.call("md_conv_nhwc_f16", x.data_ptr(), ldx, w.data_ptr(), out.data_ptr(), ldy, B, H, W, Cin, cout, kw, stride,
-              int(upsample), int(pad_lo), _p(bias), _p(r2), ldr, _p(rowadd), ldra, rows_per_group, act, _st(),
+    return (x.data_ptr(), ldx, w.data_ptr(), out.data_ptr(), ldy, B, H, W, Cin, cout, kw, stride, int(upsample), int(pad_lo), _p(bias),
+            _p(r2), ldr, _p(rowadd), ldra, rows_per_group, act), out, (Ho, Wo)
+
+
+def conv3x3(x, w, cout, bias=None, residual=None, rowadd=None, rows_per_group=0, act=ACT_NONE, stride=1, upsample=False,
+            out=None, pad_lo=1, kw=3):
+    """x: (B, H, W, Cin) NHWC (contiguous or a channel slice: see _pixel_pitch); w: [Cout, 3*kw*Cin] packed (ky, kx, cin);
+    returns (B, Ho, Wo, Cout).
+    pad_lo=0 (stride 2 only): zero padding (0,1,0,1) instead of 1 all round (the AutoencoderKL downsampler).
+    kw=1: a 3 x 1 filter (taps along H only; Conv3d (3,1,1) of the temporal VAE decoder with H = frames, W = pixels).
+    `out` may be a channel slice of a wider NHWC tensor (row pitch = its last-dim stride)."""
+    args, out, (Ho, Wo) = _conv_args(x, w, cout, bias, residual, rowadd, rows_per_group, act, stride, upsample, out, pad_lo, kw)
+    B, H, W, Cin = x.shape
+    _lib.call("md_conv_nhwc_f16", *args, _st(),
               meta=(f"conv3x{kw} B={B} {H}x{W} Cin={Cin} Cout={cout} s={stride} up={int(upsample)}",
                     2.0 * B * Ho * Wo * cout * 3 * kw * Cin, 2.0 * (B * H * W * Cin + cout * 3 * kw * Cin + B * Ho * Wo * cout)))
     return out
+
+
+def conv_plan(x, w, cout, bias=None, residual=None, rowadd=None, rows_per_group=0, act=ACT_NONE, stride=1, upsample=False,
+              out=None, pad_lo=1, kw=3):
+    """The plan code of the kernel ops.conv3x3 would run for these very tensors and keywords (see gemm_plan); nothing is launched."""
+    args, _, _ = _conv_args(x, w, cout, bias, residual, rowadd, rows_per_group, act, stride, upsample, out, pad_lo, kw)
+    return _lib.load().md_conv_plan_call(*args)
 
 
 def _dense16(t):

@@ -258,6 +258,128 @@ def test_gemm_and_conv_dispatch_over_a_grid_matches_the_recording(golden_dir):
     assert {135, 134, 124, 132, 142, 144, 1124, 1134, 2135, 2134, 2132, 210, 220, 230, 301, 302, 303} <= seen and min(seen) < 0
 
 
+class _PlanCall:
+    """md_gemm_plan_call / md_conv_plan_call on made-up operand ADDRESSES (the queries read pointer values and pitches, never memory): every
+    operand 2^40 bytes from the next, so none overlaps another at any size of the grid."""
+    A, W, C, BIAS, RES, RADD = (i << 40 for i in range(1, 7))
+
+    def __init__(self):
+        from mikudance_amd import _lib
+        self.lib = _lib.load()
+        assert self.lib.md_set_cu_limit(0) == 0
+        assert not os.environ.get("MD_GEMM_SP") and not os.environ.get("MD_GEMM_SP_NT"), "the dispatch tests assume the default knobs"
+
+    def gemm(self, M, N, K, act=0, tr=0, epi=0, A=None, lda=None, C=None, ldc=None, res=None, ldr=None, radd=None, ldra=None, rpg=None, blocks=None):
+        ldc = ldc if ldc is not None else (M if tr else (N // 2 if act == 3 else N))
+        return self.lib.md_gemm_plan_call(A or self.A, K if lda is None else lda, self.W, C or self.C, ldc, M, N, K, self.BIAS if epi & 4 else None,
+                                          res or (self.RES if epi & 1 else None), N if ldr is None else ldr,
+                                          radd or (self.RADD if epi & 2 else None), N if ldra is None else ldra, M if rpg is None else rpg, act, tr,
+                                          blocks[0] if blocks else None, blocks[1] if blocks else None)
+
+    def conv(self, B, H, cin, cout, st=1, up=0, epi=0, act=0, kw=3, pad_lo=1, ldx=None, Y=None, ldy=None, res=None, ldr=None, Wd=None):
+        Wd = Wd or H
+        return self.lib.md_conv_plan_call(self.A, cin if ldx is None else ldx, self.W, Y or self.C, cout if ldy is None else ldy, B, H, Wd, cin, cout, kw,
+                                          st, up, pad_lo, self.BIAS if epi & 4 else None, res or (self.RES if epi & 1 else None),
+                                          cout if ldr is None else ldr, self.RADD if epi & 2 else None, cout, ((H << up) // st) * ((Wd << up) // st), act)
+
+
+def test_plan_of_the_call_agrees_with_the_table_query_on_dense_aligned_operands(golden_dir):
+    """md_gemm_plan_call / md_conv_plan_call run launch_gemm's own checks, knobs and gemm_choose (gemm.hip gemm_plan_checked).  On dense,
+    16-byte aligned operands with the default knobs they answer what md_gemm_plan / md_conv3x3_plan answer over the grid of
+    tests/golden/gemm_plans.json at 256 compute units (the count without a device, and the MI355X's own) -- except where the LAUNCH refuses the
+    call, which the table query never modelled: GEGLU with N % 64, a residual, a row term or a transposed store; a transposed store with a
+    residual or a row term.  There the call query is negative."""
+    from itertools import product
+    from mikudance_amd import ops
+    q = _PlanCall()
+    lib, G = q.lib, ops.ACT_GEGLU
+    want = json.load(open(os.path.join(golden_dir, "gemm_plans.json")))
+    n = refused = 0
+    for i, (M_, N, K, act, tr, epi, ncu) in enumerate(product((4608, 18432, 294912, 983040), (4, 128, 320, 1280, 10240),
+                                                              (64, 100, 128, 320, 640, 1280, 2560, 5120), (ops.ACT_NONE, G), (0, 1), range(8), (256, 192, 64))):
+        if ncu != 256:
+            continue
+        got = q.gemm(M_, N, K, act, tr, epi)
+        refuse = K % 64 != 0 or (act == G and (N % 64 != 0 or tr or epi & 3)) or (tr and epi & 3)
+        if refuse:
+            assert got < 0, ((M_, N, K, act, tr, epi), got)
+            refused += 1
+        else:
+            assert got == want["gemm"][i] == lib.md_gemm_plan(M_, N, K, act, tr, epi, 256), ((M_, N, K, act, tr, epi), got, want["gemm"][i])
+        n += 1
+    assert n == 5120 and 0 < refused < n
+    pairs = ((320, 320), (640, 320), (960, 320), (640, 640), (1920, 640), (1280, 1280), (2560, 1280), (320, 4), (64, 320), (64, 128),
+             (128, 128), (128, 256), (256, 256), (60, 320))
+    n = 0
+    for i, (B, H, (cin, cout), st, up, epi, ncu) in enumerate(product((2, 32), (12, 24, 96, 768), pairs, (1, 2), (0, 1), (0, 4, 5, 7), (256, 192, 64))):
+        if ncu != 256:
+            continue
+        got = q.conv(B, H, cin, cout, st, up, epi)
+        assert got == want["conv"][i], ((B, H, cin, cout, st, up, epi), got, want["conv"][i])
+        n += 1
+    assert n == 1792
+    # row blocks: 983 040 x 1280 fp16 is beyond the sp kernel's 2^31-byte reach
+    import ctypes
+    nb, tail = ctypes.c_int(0), ctypes.c_int(0)
+    assert q.gemm(983040, 320, 1280, epi=5, blocks=(ctypes.byref(nb), ctypes.byref(tail))) == 2135 and nb.value == 2 and tail.value == 2135
+    assert q.gemm(4608, 1280, 1280, epi=5, blocks=(ctypes.byref(nb), ctypes.byref(tail))) == 2132 and nb.value == 1 and tail.value == 2132
+
+
+def test_plan_of_the_call_sees_alignment_pitches_activation_and_the_cu_limit():
+    """One reason at a time moves an sp-eligible problem to gemm_kernel (30x): what md_gemm_plan cannot be asked."""
+    q = _PlanCall()
+    assert q.gemm(18432, 1280, 1280, epi=5) == 2134 and q.gemm(18432, 1280, 640, epi=4) == 134
+    assert q.gemm(18432, 1280, 1280, epi=5, C=q.C + 8) == 303                      # output base 8 bytes off a 16-byte boundary
+    assert q.gemm(18432, 1280, 1280, epi=5, ldc=1284) == 303                       # ldc % 8 == 4
+    assert q.gemm(18432, 1280, 1280, epi=5, res=q.RES + 8) == 303                  # misaligned residual
+    assert q.gemm(18432, 1280, 1280, epi=5, ldr=1284) == 303                       # residual pitch
+    assert q.gemm(18432, 1280, 1280, epi=6, radd=q.RADD + 8) == 303                # misaligned row term
+    assert q.gemm(18432, 1280, 1280, epi=4, act=1) == 303 and q.gemm(18432, 1280, 1280, epi=4, act=2) == 303      # SiLU / ReLU
+    assert q.gemm(18432, 1280, 1280, epi=4, lda=1280 + 64) == 134 and q.gemm(18432, 1280, 1280, epi=5, C=q.RES, ldr=1280) == 2134    # slices and in place stay
+    assert q.gemm(294912, 320, 320, epi=5) == 210 and q.gemm(294912, 320, 320, epi=5, C=q.C + 8) == 303
+    assert q.gemm(294912 + 8, 320, 320, epi=5) == 303                              # M % 16: not the streaming kernel, K < 640: not sp
+    assert q.conv(32, 96, 320, 320, epi=5) == 2135 and q.conv(32, 96, 320, 320, epi=4) == 135
+    assert q.conv(32, 96, 320, 320, epi=4, act=1) == 302 and q.conv(32, 96, 320, 320, epi=4, act=2) == 302       # an activation on a conv
+    assert q.conv(32, 24, 1280, 1280, epi=4, act=1) == 303
+    assert q.conv(32, 96, 320, 320, epi=4, ldy=321) == 302 and q.conv(32, 96, 320, 320, epi=4, Y=q.C + 8) == 302  # odd output pitch / base
+    assert q.conv(32, 96, 320, 320, epi=5, res=q.RES + 8) == 302
+    assert q.conv(32, 96, 320, 320, epi=4, ldx=640) == 135 and q.conv(32, 96, 320, 320, st=2, pad_lo=0, epi=4) == 135
+    assert q.conv(2, 16, 128, 128, kw=1, epi=4, Wd=4096) == 142
+    # md_set_cu_limit is honoured: on 8 CUs the 480 tiles of 192 x 256 are 60 rounds of 29.6 us, the 384 of 192 x 320 are 48 of 35.2 us
+    try:
+        assert q.lib.md_set_cu_limit(8) == 0
+        assert q.gemm(18432, 1280, 1280, epi=5) == 2135
+    finally:
+        assert q.lib.md_set_cu_limit(0) == 0
+    assert q.gemm(18432, 1280, 1280, epi=5) == 2134
+
+
+def test_plan_of_the_call_returns_every_refusal_of_the_launch():
+    q = _PlanCall()
+    G = 3
+    assert q.gemm(18432, 1280, 1280) > 0
+    assert q.gemm(18432, 1280, 1200) < 0 and q.gemm(18432, 1280, 0) < 0 and q.gemm(0, 1280, 1280) < 0            # bad K, empty problem
+    assert q.gemm(18432, 1280, 1280, A=q.A + 8) < 0 and q.gemm(18432, 1280, 1280, lda=1284) < 0                   # A alignment / pitch
+    assert q.gemm(18432, 2560, 1280, act=G, epi=4) == 144
+    assert q.gemm(18432, 2560, 1280, act=G, epi=5) < 0 and q.gemm(18432, 2560, 1280, act=G, epi=6) < 0            # GEGLU with a residual / row term
+    assert q.gemm(18432, 2560, 1280, act=G, tr=1) < 0 and q.gemm(18432, 2528, 1280, act=G) < 0                    # GEGLU transposed / N % 64
+    assert q.gemm(18432, 2560, 1280, act=G, C=q.C + 8) < 0 and q.gemm(18432, 2560, 1280, act=G, ldc=1284) < 0
+    assert q.gemm(18432, 1280, 1280, tr=1, epi=4) == 1134
+    assert q.gemm(18432, 1280, 1280, tr=1, epi=6) < 0 and q.gemm(18432, 1280, 1280, tr=1, epi=5) < 0              # transposed with a row term / residual
+    assert q.gemm(18432, 1280, 1280, tr=1, act=1) < 0
+    assert q.gemm(18432, 1280, 1280, epi=2, rpg=0) < 0                                                            # row term without rows_per_group
+    assert q.gemm(18432, 1280, 1280, epi=1, res=q.C + 2 * 1280 * 10) < 0                                          # residual ten rows into the output
+    assert q.gemm(18432, 1280, 1280, epi=1, res=q.C + 2 * 640, ldc=2560, ldr=2560) < 0                            # sibling slices that share columns
+    assert q.gemm(18432, 1280, 1280, epi=1, res=q.C + 2 * 1280, ldc=2560, ldr=2560) == 2134                       # sibling slices that do not
+    assert q.gemm(18432, 1280, 1280, epi=1, C=q.RES, ldc=1280, ldr=1288) < 0                                      # in place with another pitch
+    assert q.conv(32, 96, 60, 320) < 0 and q.conv(32, 96, 64, 320, ldx=60) < 0 and q.conv(32, 96, 64, 320, ldx=68) < 0
+    assert q.conv(32, 96, 64, 320, st=3) < 0 and q.conv(32, 96, 64, 320, st=2, up=1) < 0 and q.conv(32, 96, 64, 320, pad_lo=0) < 0
+    assert q.conv(32, 96, 64, 320, kw=1, st=2) < 0 and q.conv(32, 96, 64, 320, kw=2) < 0
+    assert q.conv(1, 4096, 64, 320, Wd=4096) < 0                                                                  # 2^24 pixels: the tap arithmetic
+    assert q.conv(32, 96, 320, 320, epi=1, res=q.C + 2 * 320 * 10) < 0
+    assert b"overlaps" in q.lib.md_last_error()
+
+
 def test_attention_dispatch_table():
     """md_attention_plan runs the decision code of md_attention_fwd_f16 (launch_attn / launch_attn2 / attn2s_eligible) without touching a
     device: 400 = generic attn_kernel, 414 / 418 = attn2 DMA ring with 4 / 8 waves, 420 = attn2s (K / V^T resident in LDS).  Pinned: the
