@@ -355,6 +355,23 @@ int md_token_blur_f16(const void* x, void* y, int B, int Hh, int Ww, int C, cons
                       void* stream);
 int md_token_mean_f16(const void* x, void* y, int B, int L, int C, void* workspace, void* stream);
 
+/* Shifted-tile reorder for tiled spatial self-attention (MSW-MSA of HiDiffusion, Zhang et al., arXiv 2311.17528; the pipeline's
+ * tile_attention=): every frame's Hh x Ww token grid is cut into t x t tiles of th x tw tokens, th = Hh / t, tw = Ww / t, Lt = th*tw, after
+ * a cyclic shift by (sy, sx); every tile is then one batch item of md_attention_fwd_f16 (B*t*t items of Lt tokens).
+ * Frame-major: [B*Hh*Ww][C] fp16 row-major and contiguous, row = (b*Hh + yy)*Ww + xx (the layout of md_token_pool_f16).
+ * Tile-major:  [B*t*t*tile_stride][C]; tile (b, j, i) with j, i < t is batch item (b*t + j)*t + i and its row r*tw + c holds the token
+ *              x[b, (j*th + r + sy) mod Hh, (i*tw + c + sx) mod Ww]: torch.roll(grid, (-sy, -sx), (1, 2)) followed by a plain partition.
+ * inverse = 0: x frame-major -> y tile-major.  Rows [Lt, tile_stride) of every tile are written as exact +0: the pad md_attention_fwd_f16
+ *              documents (the contract of md_token_pool_f16).  tile_stride = Lt for a Q operand; the caller rounds up to a multiple of 8 for
+ *              K / V where Lt is none.
+ * inverse = 1: x tile-major -> y frame-major, the exact inverse permutation.  The pad rows of x are never read.
+ * The wrap-around of a shifted tile is not masked (the paper's code does not mask it either): tokens of opposite frame edges may share a
+ * tile.  A copy: every bit pattern (-0, subnormals, NaN payloads) survives; 16-byte loads and stores, no atomics: two calls give the same
+ * bits.  Nothing outside the rows of y named above is written.
+ * t in 2..8, Hh % t == 0 and Ww % t == 0, 0 <= sy < Hh, 0 <= sx < Ww, tile_stride >= Lt, inverse 0 or 1, C % 8 == 0, x and y not NULL,
+ * 16-byte aligned and not overlapping; MD_ERR_ARG otherwise, with nothing launched and y untouched. */
+int md_token_tile_f16(const void* x, void* y, int B, int Hh, int Ww, int C, int t, int sy, int sx, int tile_stride, int inverse, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

@@ -266,11 +266,23 @@ class SelfAttnCall:
       keeps every token; the K / V source -- norm1(x), or norm1(x) + bank on the rows that read the bank, pooled AFTER the add -- goes through
       ops.token_pool (s per axis, mode "nearest" or "mean") in front of to_k / to_v, and the attention runs with Lk = (Hh // s) * (Ww // s)
       keys at kv_stride = roundup8(Lk).  The bank written is the full-resolution norm1(x).  An identity map has no attention to shorten: no
-      effect there."""
+      effect there.
+    tile: None, or {TransformerBlock: (t, (sy, sx))}: shifted-tile self-attention (MSW-MSA of HiDiffusion, Zhang et al., arXiv 2311.17528).
+      Every frame's token grid, rolled by (-sy, -sx), is cut into t x t tiles of th x tw = (Hh / t) x (Ww / t) tokens and attention runs inside
+      each tile at full key resolution: ops.token_tile reorders the q source norm1(x), and the K / V source after the bank add, into tile-major
+      order (ONE reorder feeding the fused q|k GEMM where no row reads the bank and th tw is a multiple of 8), the row-wise projections run on
+      the reordered rows, the attention runs with B t^2 batch items of Lq = Lk = th tw tokens (kv_stride = roundup8(th tw)), and
+      ops.token_untile puts its output back in frame order in front of to_out, whose residual and row term are in frame order.
+      Cross-attention, the feed-forward and everything outside the block see frame order.  BLUR THEN TILE: a blurred block's queries are
+      projected and blurred over the whole frame grid, then reordered.  TILE THEN POOL: with `pool` on the same block ops.token_pool runs per
+      tile on the th x tw grid, with B t^2 "frames".  The bank written is norm1(x) in frame order, never tiled.  The wrap-around of a shifted
+      tile is not masked (the paper's code does not mask it either): tokens of opposite frame edges may share a tile.  An identity map has no
+      attention to tile: no effect there."""
     half: int = None
     identity: tuple = None
     blur: tuple = None
     pool: dict = None
+    tile: dict = None
 
     def __post_init__(self):
         if self.identity is not None and self.blur is not None:
@@ -331,8 +343,33 @@ class TransformerBlock(_Packed):
             self._kv_cache = (cross.root, ops.gemm(cross.ctx, pk["k2"]), ops.gemm(cross.ctx, pk["v2"], transpose_out=True), {})
         return self._kv_cache[1:]
 
+    def _tiled_attention(self, pk, n, kv, B, grid, sigma, pool, tile):
+        """Steps 2 and 3 of forward for a block of SelfAttnCall.tile: projections on tile-major rows, attention per tile, output in frame order."""
+        C, H = self.dim, self.heads
+        (Hh, Ww), (t, shift) = grid, tile
+        Lt = (Hh // t) * (Ww // t)
+        Bt = B * t * t
+        stride = (Lt + 7) // 8 * 8                                       # K / V rows per tile; q has Lt
+        if n is kv and pool is None and sigma is None and stride == Lt:
+            src = ops.token_tile(n, B, Hh, Ww, t, shift)[0]              # one reorder feeds the fused q|k GEMM
+            qk = ops.gemm(src, pk["qk1"])
+            q, k, Lk, stride = qk[:, :C], qk[:, C:], Lt, None
+        else:
+            if sigma is not None:                                        # blur then tile: the queries are blurred over the whole frame grid
+                q = ops.token_tile(ops.token_blur(ops.gemm(n, pk["q1"]), B, Hh, Ww, sigma), B, Hh, Ww, t, shift)[0]
+            else:
+                q = ops.gemm(ops.token_tile(n, B, Hh, Ww, t, shift)[0], pk["q1"])
+            if pool is None:
+                src, Lk = ops.token_tile(kv, B, Hh, Ww, t, shift, tile_stride=stride)[0], Lt
+            else:                                                        # tile then pool: every tile is one "frame" of th x tw tokens
+                src, Lk, stride = ops.token_pool(ops.token_tile(kv, B, Hh, Ww, t, shift)[0], Bt, Hh // t, Ww // t, pool[0], pool[1])
+            k = ops.gemm(src, pk["k1"])                                  # (pad rows are zeros, to_k / to_v have no bias: zero K rows, zero V^T columns)
+        vt = ops.gemm(src, pk["v1"], transpose_out=True)
+        a = ops.attention(q, k, vt, Bt, H, C // H, Lt, Lk, kv_stride=stride)
+        return ops.token_untile(a, B, Hh, Ww, t, shift)
+
     def forward(self, h, B, L, cross, sa=PLAIN, grid=None):
-        """h: [B*L, C] tokens.  Returns tokens.  sa: the call's SelfAttnCall; grid: (Hh, Ww) of the L tokens, for a block that pools or blurs."""
+        """h: [B*L, C] tokens.  Returns tokens.  sa: the call's SelfAttnCall; grid: (Hh, Ww) of the L tokens, for a block that pools, blurs or tiles."""
         pk = self.packed()
         C, H = self.dim, self.heads
         D = C // H
@@ -341,7 +378,8 @@ class TransformerBlock(_Packed):
         identity = sa.identity is not None and any(self is b for b in sa.identity)
         sigma = sa.blur[1] if sa.blur is not None and any(self is b for b in sa.blur[0]) else None
         pool = None if sa.pool is None or identity else sa.pool.get(self)
-        if (sigma is not None or pool is not None) and (grid is None or grid[0] * grid[1] != L):
+        tile = None if sa.tile is None or identity else sa.tile.get(self)
+        if (sigma is not None or pool is not None or tile is not None) and (grid is None or grid[0] * grid[1] != L):
             raise ValueError(f"TransformerBlock: grid {grid} does not hold L = {L} tokens")
         # 1. source: n = norm1(x) feeds q, kv feeds k and v; rows [begin, M) read the bank (kv = n + bank there), None: no row does
         M = h.shape[0]
@@ -366,6 +404,8 @@ class TransformerBlock(_Packed):
         if identity:
             # 2. no q, no k;  3. identity attention map: every query row takes its own V row
             a = ops.gemm(kv, pk["v1"])
+        elif tile is not None:
+            a = self._tiled_attention(pk, n, kv, B, grid, sigma, pool, tile)
         else:
             # 2. projections: q from n (blurred where selected), k and v^T from kv or from its downsampled grid
             if n is kv and pool is None and sigma is None:

@@ -26,6 +26,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      (an addition: K / V token downsampling in the spatial self-attention, arXiv 2402.13573; default 1 = off)
     pipe(..., seg_scale=--seg_scale, seg_blur_sigma=--seg_blur_sigma, seg_applied_layers=--seg_layers)
                      (an addition: smoothed-energy guidance, arXiv 2408.00760; default 0.0 = off)
+    pipe(..., tile_attention=--tile_attention, tile_attention_shift=--tile_attention_shift)
+                     (an addition: shifted-tile spatial self-attention, arXiv 2311.17528; default 1 = off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -56,7 +58,7 @@ SAMPLERS = {"ddim": lambda kw: DDIMScheduler(**kw),
 
 
 def _factors(text):
-    """--kv_downsample: "2" or "4,2" -> a tuple of integers (their range is the pipeline's business)."""
+    """--kv_downsample / --tile_attention: "2" or "4,2" -> a tuple of integers (their range is the pipeline's business)."""
     import argparse
     try:
         return tuple(int(v) for v in text.split(","))
@@ -137,6 +139,12 @@ def parse_args(argv=None):
                              "the highest down, e.g. 2 or 4,2; 1 = off")
     parser.add_argument("--kv_downsample_mode", choices=("nearest", "mean"), default="nearest",
                         help="(addition) how the K / V token grid is reduced: nearest (the paper's) or the mean of each block")
+    parser.add_argument("--tile_attention", type=_factors, default=(1,), metavar="N[,N...]",
+                        help="(addition) shifted-tile spatial self-attention in the denoising UNet (MSW-MSA of HiDiffusion, arXiv 2311.17528), "
+                             "an approximation that saves attention time at high resolution: one integer 1..8 per resolution level from the "
+                             "highest down, the number of tiles per axis, e.g. 2 or 2,2; it must divide the level's token grid; 1 = off")
+    parser.add_argument("--tile_attention_shift", choices=("cycle", "none"), default="cycle",
+                        help="(addition) how the tiling moves from step to step: cycle (a quarter tile further every step, period 4) or none")
     parser.add_argument("--seg_scale", type=float, default=0.0,
                         help="(addition) smoothed-energy guidance scale (SEG, arXiv 2408.00760): steer away from a second conditional "
                              "prediction made with the self-attention queries of --seg_layers Gaussian-blurred over the token grid, >= 0; "
@@ -244,7 +252,8 @@ def main(argv=None):
                apg=args.apg, apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum,
                pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale, pag_applied_layers=_layer_names(args.pag_layers),
                kv_downsample=args.kv_downsample, kv_downsample_mode=args.kv_downsample_mode,
-               seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma, seg_applied_layers=_layer_names(args.seg_layers))
+               seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma, seg_applied_layers=_layer_names(args.seg_layers),
+               tile_attention=args.tile_attention, tile_attention_shift=args.tile_attention_shift)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

@@ -550,6 +550,44 @@ def token_pool(x, B, Hh, Ww, s, mode="nearest", out=None):
     return out, Lk, stride
 
 
+def _tile_call(who, x, B, Hh, Ww, t, shift, tile_stride, out, inverse):
+    """The argument checks the two wrappers share and the one launch of md_token_tile_f16 -> (out, Lt, tile_stride)."""
+    _chk(x, "x"); _chk(out, "out")
+    sy, sx = shift
+    if t < 1 or Hh % t or Ww % t:
+        raise _lib.MdanceHipError(f"{who}: t = {t} does not divide the {Hh} x {Ww} grid")
+    Lt = (Hh // t) * (Ww // t)
+    tile_stride = Lt if tile_stride is None else tile_stride
+    rows_tile, rows_frame = B * t * t * tile_stride, B * Hh * Ww
+    rows_in, rows_out = (rows_tile, rows_frame) if inverse else (rows_frame, rows_tile)
+    if x.dim() != 2 or not x.is_contiguous() or x.shape[0] != rows_in:
+        raise _lib.MdanceHipError(f"{who}: x must be a contiguous [{rows_in}, C] matrix, got {tuple(x.shape)} for B={B} Hh={Hh} Ww={Ww} t={t} "
+                                  f"tile_stride={tile_stride}")
+    C = x.shape[1]
+    if out is None:
+        out = torch.empty((rows_out, C), device=x.device, dtype=F16)
+    assert out.is_contiguous() and tuple(out.shape) == (rows_out, C), (tuple(out.shape), (rows_out, C))
+    rows_read = B * t * t * Lt                                     # either direction reads the B*Hh*Ww tokens (the inverse skips the pad rows) and writes rows_out
+    _lib.call("md_token_tile_f16", x.data_ptr(), out.data_ptr(), B, Hh, Ww, C, t, sy, sx, tile_stride, int(inverse), _st(),
+              meta=(f"{who} B={B} {Hh}x{Ww} C={C} t={t}", 0.0, 2.0 * C * (rows_read + rows_out)))
+    return out, Lt, tile_stride
+
+
+def token_tile(x, B, Hh, Ww, t, shift=(0, 0), tile_stride=None, out=None):
+    """Frame order -> tile-major order for tiled self-attention (md_token_tile_f16; MSW-MSA of HiDiffusion, arXiv 2311.17528): x [B*Hh*Ww, C]
+    contiguous, the tokens of B frames -> (y, Lt, tile_stride): y [B*t*t*tile_stride, C], tile (b, j, i) = batch item (b*t + j)*t + i holding the
+    th x tw = (Hh // t) x (Ww // t) tokens of torch.roll(grid, (-sy, -sx), (1, 2)) at (j*th.., i*tw..), Lt = th*tw, the rows behind Lt exact
+    zeros.  shift = (sy, sx), 0 <= sy < Hh, 0 <= sx < Ww; tile_stride: rows per tile, default Lt (a Q operand; pass roundup8(Lt) for K / V and
+    kv_stride=tile_stride to `attention`).  `out`: a contiguous [B*t*t*tile_stride, C] destination."""
+    return _tile_call("token_tile", x, B, Hh, Ww, t, shift, tile_stride, out, False)
+
+
+def token_untile(x, B, Hh, Ww, t, shift=(0, 0), tile_stride=None, out=None):
+    """The inverse of token_tile with the same arguments: x [B*t*t*tile_stride, C] tile-major -> y [B*Hh*Ww, C] in frame order.  The pad rows
+    of x are not read."""
+    return _tile_call("token_untile", x, B, Hh, Ww, t, shift, tile_stride, out, True)[0]
+
+
 def blur_kernel_size(sigma, n):
     """Taps of SEG's Gaussian along a grid axis of n tokens: the official gaussian_blur_2d's ceil(6 sigma) + 1 - ceil(6 sigma) % 2, clamped to
     the largest odd number a reflect-padded axis of n allows (n if n is odd, else n + 1); 1 for n = 1."""

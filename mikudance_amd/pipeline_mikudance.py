@@ -83,6 +83,7 @@ class SamplingPlan:
     strength: float
     kv: Union[None, tuple, dict]   # None: no K / V downsampling; (factors, mode), resolved: UNet3DConditionModel.kv_downsample_plan
     guide: Union[None, Rescale, APG, Perturb]      # None: plain (u + g (c - u), or c without CFG)
+    tile: Union[None, tuple] = None                # None: no tiled self-attention; (factors, shift), resolved: (UNet3DConditionModel.tile_attention_plan, shift)
 
 
 # the step forms v in ONE way: (asked for, beside, why not), in the order the refusals are made
@@ -164,7 +165,7 @@ class MikuDanceVideoPipeline:
                 free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25, free_init_temporal_stop=0.25,
                 free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
                 pag_applied_layers=("mid",), kv_downsample=1, kv_downsample_mode="nearest", seg_scale=0.0, seg_blur_sigma=100.0,
-                seg_applied_layers=("mid",)):
+                seg_applied_layers=("mid",), tile_attention=1, tile_attention_shift="cycle"):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -283,6 +284,28 @@ class MikuDanceVideoPipeline:
                             padding: the official implementation's gaussian_blur_2d, per axis) or math.inf (every query becomes its frame's mean
                             query: the official inf_blur).  100.0, the paper's default, spans every grid of a 768 x 768 clip
         seg_applied_layers  as pag_applied_layers
+        tile_attention      shifted-tile self-attention in the spatial self-attention of the denoising UNet (MSW-MSA of HiDiffusion, Zhang et al.,
+                            arXiv 2311.17528), an opt-in APPROXIMATION that trades accuracy for time at high resolution: an integer factor 1..8
+                            per resolution level from the highest down (levels as kv_downsample; missing levels and 1 = untouched).  At a level
+                            with factor t every frame's token grid is cut into t x t tiles and attention runs inside each tile at full key
+                            resolution (ops.token_tile / ops.token_untile round the existing attention entry, B t^2 batch items of L / t^2
+                            tokens), so that level's attention FLOPs fall by t^2; the price is three reorder passes per block that reads the
+                            bank, two otherwise.  The reference UNet, its banks, cross-attention and the motion modules are untouched; the main
+                            evaluation and PAG's / SEG's perturbed evaluation of a step use the same plan and shift (SEG blurs over the whole
+                            frame, then tiles; an identity-map block of PAG has no attention to tile).  With kv_downsample on the same level
+                            the pooling runs inside each tile.  The wrap-around of a shifted tile is not masked (the paper's code does not
+                            mask it either): on shifted steps tokens of opposite frame edges may share a tile.  Sits inside the UNet: works
+                            with both samplers, eta, init_latents, every window schedule and fuse mode, FreeInit, every guide, kv_downsample,
+                            window_parallel and two_queues.  ValueError, before anything runs, for other values, more factors than levels, a
+                            level without attention, a factor that does not divide both sides of its level's grid for THIS latent size
+                            (levels halve with ceil), or tiles smaller than that level's kv_downsample factor.  Image quality on real
+                            weights has not been assessed.  1 (the default) and all ones: bitwise the loop without the keyword, no new
+                            operator call, no buffer, no new keyword to forward_nhwc
+        tile_attention_shift  "cycle" (default): at step index k = t_start + step_i (video-to-video keeps the shifts of the steps it keeps; every
+                            FreeInit pass starts over), q = k mod 4 and a level whose tiles hold th x tw tokens shifts its tiling by
+                            (q th // 4, q tw // 4), so no tile border stays put; "none": no shift.  The paper's code draws the shift at random
+                            per call; here it is a pure function of the step, so that runs are reproducible and the ranks of window_parallel
+                            agree without talking
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         plan = self.sampling_plan(
@@ -291,7 +314,8 @@ class MikuDanceVideoPipeline:
             free_init_temporal_stop=free_init_temporal_stop, free_init_fast=free_init_fast, apg=apg, apg_eta=apg_eta,
             apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
             pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode, seg_scale=seg_scale,
-            seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers)
+            seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
+            tile_attention_shift=tile_attention_shift)
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         ops.require_gpu(latents, "MikuDanceVideoPipeline.denoise")
@@ -344,6 +368,9 @@ class MikuDanceVideoPipeline:
             ns_main, ns_pert, pert_counter = noise_sum[:nb], noise_sum[nb:], torch.zeros((F_,), device=dev, dtype=torch.float32)
             pert_kw = dict(pag=pert.blocks) if pert.kind == "identity" else dict(seg=(pert.blocks, pert.sigma))
         kv_kw = {} if plan.kv is None else dict(kv_downsample=plan.kv)             # no plan: no keyword
+        tile_plan, tile_shift = plan.tile or (None, None)                          # no plan: no keyword either
+        if tile_plan is not None:
+            from .unet_3d_mix import tile_shift_at
         windows = [list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
                                                                             context_stride, context_overlap)]
         mm_len = getattr(den, "temporal_position_encoding_max_len", None)
@@ -416,6 +443,8 @@ class MikuDanceVideoPipeline:
                     noise_sum.zero_()
                     counter.zero_()
                     s_t = self._pag_scale_at(pert.scale, pert.adaptive, t) if pert else 0.0     # a pure function of t: no sync
+                    # tiled self-attention: the main and the perturbed evaluation of a step share the plan and the step's shift
+                    sa_kw = kv_kw if tile_plan is None else dict(kv_kw, tile_attention=tile_plan, tile_shift=tile_shift_at(tile_shift, t_start + step_i))
                     for wi, win in enumerate(windows):
                         if window_parallel is not None and not window_parallel.mine(wi):
                             continue                                         # another rank's window (its share arrives in the all_reduce)
@@ -436,13 +465,13 @@ class MikuDanceVideoPipeline:
                         # both clip-halves are packed from the SAME latents (batch stride 0 above): the layers in front of the first attention
                         # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
                         pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
-                                                two_queues=self.two_queues, **kv_kw)
+                                                two_queues=self.two_queues, **sa_kw)
                         accumulate(pred, ns_main, counter, wi, nb)
                         if s_t > 0.0:
                             # ---- PAG / SEG: the conditional frames once more (the banks are still in place), the selected self-attention maps
                             # = identity / from blurred queries
                             pred = den.forward_nhwc(x[(nb - 1) * f:], 1, f, torch.full((1,), float(t)), cross.rows(f, 2 * f) if do_cfg else cross,
-                                                    **pert_kw, **kv_kw)
+                                                    **pert_kw, **sa_kw)
                             accumulate(pred, ns_pert, pert_counter, wi, 1)
                         reader.clear()
                         writer.clear()
@@ -463,12 +492,13 @@ class MikuDanceVideoPipeline:
     def sampling_plan(num_inference_steps, guidance_scale, has_init, shape, *, guidance_rescale, strength, context_fuse,
                       free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop, free_init_fast, apg, apg_eta,
                       apg_norm_threshold, apg_momentum, pag_scale, pag_adaptive_scale, pag_applied_layers, kv_downsample, kv_downsample_mode,
-                      seg_scale, seg_blur_sigma, seg_applied_layers):
+                      seg_scale, seg_blur_sigma, seg_applied_layers, tile_attention=1, tile_attention_shift="cycle"):
         """Every refusal of denoise()'s sampling keywords (see its docstring) that needs no model -- every value is checked whether or not its
         feature is on, and neither UNet is called -- then what they resolve to -> SamplingPlan, still holding the layer names and the
         (factors, mode) that _resolve_plan hands to the denoising UNet.  has_init: there is a clip to start from (init_latents / video);
         shape: the latents' shape behind (batch, channels), (F, h, w)."""
-        from .unet_3d_mix import check_kv_downsample, check_kv_downsample_grid, check_pag_layer_names
+        from .unet_3d_mix import (check_kv_downsample, check_kv_downsample_grid, check_pag_layer_names, check_tile_attention,
+                                  check_tile_attention_grid)
         asked = []
 
         def ask(guide):                                                  # one more of the ways to form v is asked for
@@ -515,6 +545,8 @@ class MikuDanceVideoPipeline:
             ask("pag_scale > 0")
         kv_factors, kv_mode = check_kv_downsample(kv_downsample, kv_downsample_mode)
         check_kv_downsample_grid(kv_factors, int(shape[-2]), int(shape[-1]))      # every selected level keeps at least one s x s block
+        tile_factors, tile_shift = check_tile_attention(tile_attention, tile_attention_shift)
+        check_tile_attention_grid(tile_factors, int(shape[-2]), int(shape[-1]), kv_factors)      # t divides the level's grid; a tile holds an s x s block
         try:
             seg_s, sigma = float(seg_scale), float(seg_blur_sigma)
         except (TypeError, ValueError):
@@ -538,7 +570,8 @@ class MikuDanceVideoPipeline:
         elif phi > 0.0 and guidance_scale > 1.0:
             guide = Rescale(phi)
         return SamplingPlan(context_fuse, (free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
-                                           free_init_fast), strength, (kv_factors, kv_mode) if any(f > 1 for f in kv_factors) else None, guide)
+                                           free_init_fast), strength, (kv_factors, kv_mode) if any(f > 1 for f in kv_factors) else None, guide,
+                            (tile_factors, tile_shift) if any(f > 1 for f in tile_factors) else None)
 
     def _resolve_plan(self, plan):
         """The refusals only the denoising UNet can make (a layer name that selects no block, more factors than levels, a level without
@@ -547,7 +580,8 @@ class MikuDanceVideoPipeline:
         if isinstance(guide, Perturb):
             what = () if guide.kind == "identity" else ("seg_applied_layers", "smoothed-energy guidance")
             guide = guide._replace(blocks=den.pag_blocks(guide.blocks, *what))
-        return replace(plan, guide=guide, kv=None if plan.kv is None else den.kv_downsample_plan(*plan.kv))
+        return replace(plan, guide=guide, kv=None if plan.kv is None else den.kv_downsample_plan(*plan.kv),
+                       tile=None if plan.tile is None else (den.tile_attention_plan(plan.tile[0]), plan.tile[1]))
 
     @staticmethod
     def _pag_scale_at(pag_scale, pag_adaptive_scale, t):
@@ -721,7 +755,8 @@ class MikuDanceVideoPipeline:
                  context_fuse="flat", free_init_iters=1, free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25,
                  free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0,
                  pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), kv_downsample=1,
-                 kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), **kwargs):
+                 kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), tile_attention=1,
+                 tile_attention_shift="cycle", **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -738,7 +773,8 @@ class MikuDanceVideoPipeline:
                        free_init_temporal_stop=free_init_temporal_stop, free_init_fast=free_init_fast, apg=apg, apg_eta=apg_eta,
                        apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
                        pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode,
-                       seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers)
+                       seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
+                       tile_attention_shift=tile_attention_shift)
         self._resolve_plan(self.sampling_plan(num_inference_steps, guidance_scale, video is not None,
                                               (video_length, (height or 768) // 8, (width or 768) // 8), **loop_kw))
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):

@@ -307,6 +307,46 @@ class _UNetBase(_Packed):
                 plan[a] = (s, mode)
         return plan or None
 
+    def tile_attention_plan(self, factors):
+        """The per-block plan of shifted-tile self-attention (MSW-MSA of HiDiffusion, arXiv 2311.17528) that forward_nhwc(tile_attention=)
+        takes: {SpatialTransformer: t} for every spatial transformer of a level whose factor is > 1, or None when no factor is.  factors and
+        levels as kv_downsample_plan.  ValueError for anything else, for more factors than levels and for a factor > 1 on a level without an
+        attention block.  (That t divides the level's grid depends on the latent: check_tile_attention_grid.)"""
+        factors, _ = check_tile_attention(factors, "none")
+        n = len(self.down_blocks)
+        if len(factors) > n:
+            raise ValueError(f"tile_attention: {len(factors)} factors for a UNet of {n} resolution levels")
+        plan = {}
+        for i, t in enumerate(factors):
+            if t == 1:
+                continue
+            names = [(f"down_blocks.{i}", self.down_blocks[i]), (f"up_blocks.{n - 1 - i}", self.up_blocks[n - 1 - i])]
+            if i == n - 1:
+                names.append(("mid_block", self.mid_block))
+            hit = [a for _, blk in names if blk.has_cross_attention for a in blk.attentions]
+            if not hit:
+                raise ValueError(f"tile_attention: factor {t} on level {i}, which has no attention block ({', '.join(nm for nm, _ in names)})")
+            for a in hit:
+                plan[a] = t
+        return plan or None
+
+    def _tile_pairs(self, plan, hh, ww, q):
+        """{TransformerBlock: (t, (sy, sx))} of a tile_attention_plan for an hh x ww latent at shift index q: a transformer of level i works on
+        the grid halved i times with ceil, and (sy, sx) = (q th // 4, q tw // 4) with th x tw its tile."""
+        n = len(self.down_blocks)
+        level = {}
+        for i in range(n):
+            for blk in [self.down_blocks[i], self.up_blocks[n - 1 - i]] + ([self.mid_block] if i == n - 1 else []):
+                if blk.has_cross_attention:
+                    level.update({a: i for a in blk.attentions})
+        pairs = {}
+        for st, t in plan.items():
+            h, w = hh, ww
+            for _ in range(level[st]):
+                h, w = (h + 1) // 2, (w + 1) // 2
+            pairs[st.transformer_blocks[0]] = (t, (q * (h // t) // 4, q * (w // t) // 4))
+        return pairs
+
     @property
     def dtype(self):
         return self.conv_in.weight.dtype
@@ -372,6 +412,46 @@ def check_kv_downsample_grid(factors, h, w):
         h, w = (h + 1) // 2, (w + 1) // 2
 
 
+TILE_SHIFTS = ("cycle", "none")
+
+
+def check_tile_attention(factors, shift):
+    """tile_attention / tile_attention_shift as (tuple of integer factors 1..8, shift); an int n stands for (n,), a missing level or 1 means
+    untouched; shift is one of TILE_SHIFTS.  ValueError otherwise.  Needs no model: the pipeline calls it before anything runs."""
+    import numbers
+    if isinstance(factors, numbers.Integral) and not isinstance(factors, bool):
+        factors = (factors,)
+    try:
+        factors = tuple(factors)
+    except TypeError:
+        raise ValueError(f"tile_attention must be an integer or a sequence of integers, got {factors!r}") from None
+    for v in factors:
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not 1 <= v <= 8:
+            raise ValueError(f"tile_attention: every factor must be an integer in 1..8, got {v!r}")
+    if shift not in TILE_SHIFTS:
+        raise ValueError(f"tile_attention_shift must be one of {TILE_SHIFTS}, got {shift!r}")
+    return tuple(int(v) for v in factors), shift
+
+
+def check_tile_attention_grid(factors, h, w, kv_factors=()):
+    """Refuses a factor t that does not divide both sides of its level's token grid of an h x w latent (the levels halve with ceil, as the
+    stride-2 conv does), and one whose th x tw tile has no s x s block for that level's kv_downsample factor s (tile then pool)."""
+    for i, t in enumerate(factors):
+        if t > 1:
+            if h % t or w % t:
+                raise ValueError(f"tile_attention: factor {t} on level {i}, whose token grid is {h} x {w} for this latent size: {t} must divide both sides")
+            s = kv_factors[i] if i < len(kv_factors) else 1
+            if s > 1 and (h // t < s or w // t < s):
+                raise ValueError(f"tile_attention: factor {t} on level {i} leaves tiles of {h // t} x {w // t} tokens, smaller than that level's "
+                                 f"kv_downsample factor {s}")
+        h, w = (h + 1) // 2, (w + 1) // 2
+
+
+def tile_shift_at(shift, k):
+    """The shift index of step k: k mod 4 under "cycle", 0 under "none".  forward_nhwc(tile_shift=) turns it into (sy, sx) per level."""
+    return int(k) % 4 if shift == "cycle" else 0
+
+
 class UNet3DConditionModel(_UNetBase):
     kind = "3d"
 
@@ -424,14 +504,19 @@ class UNet3DConditionModel(_UNetBase):
         self._build(in_channels, tuple(block_out_channels), cross_attention_dim, norm_eps, flags, mm_kwargs, with_out=True)
 
     # ------------------------------------------------------------------------------------------ internal NHWC forward
-    def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None, kv_downsample=None, seg=None):
+    def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None, kv_downsample=None, seg=None,
+                     tile_attention=None, tile_shift=0):
         """x: (nb*f, h, w, 64) fp16 (4 latent channels, zero padded); returns pred tokens [(nb*f*h*w), 4].
         pag: None, or the blocks of pag_blocks(): this call is then the PERTURBED evaluation of perturbed-attention guidance, a call of its own
         beside the main one: nb must be 1, x the conditional frames, cross their context (the main call's context or its rows(f, 2f): the
         cached K / V projections are shared, nothing of the main call is touched).  Not with two_queues: one clip-half has nothing to run beside.
         seg: None, or (blocks, sigma) with the blocks of pag_blocks(): the perturbed evaluation of smoothed-energy guidance, under pag's conditions.
         kv_downsample: None, or the plan of kv_downsample_plan(): K / V token downsampling in the spatial transformers it names.
-        What each does in the blocks: blocks.SelfAttnCall, which carries the three through this call.
+        tile_attention: None, or the plan of tile_attention_plan(): shifted-tile self-attention in the spatial transformers it names;
+        tile_shift: the step's shift index, an int (tile_shift_at): with q = tile_shift mod 4 a transformer whose tiles hold th x tw tokens
+        shifts its tiling by (sy, sx) = (q th // 4, q tw // 4).  The paper's code draws the shift at random per call; here it is a pure
+        function of the step, so that runs are reproducible and the ranks of window_parallel agree without talking.
+        What each does in the blocks: blocks.SelfAttnCall, which carries the four through this call.
         halves_identical: the caller GUARANTEES that the two clip-halves of x hold the same latents (classifier-free guidance: the loop of
         src/pipelines/pipeline_mikudance.py:626-633 feeds `torch.cat([latents] * 2)`) -- with equal timesteps, conv_in and the first resnet
         (no attention in front of them: nothing has seen the context or the bank yet) then produce the same tensor for both halves, so
@@ -439,7 +524,8 @@ class UNet3DConditionModel(_UNetBase):
         two_queues (with halves_identical): behind those shared layers the unconditional and the conditional half are independent all the way
         to the output (per-image GroupNorm, per-row attention and LayerNorm, per-clip-half temporal attention: src/models/unet_3d_mix.py:
         418-598, src/models/mutual_mix_attention.py:173-201), and they are evaluated as TWO KERNEL QUEUES (_forward_two_queues)."""
-        sa = SelfAttnCall(identity=pag, blur=seg, pool=kv_downsample and {st.transformer_blocks[0]: sm for st, sm in kv_downsample.items()})
+        sa = SelfAttnCall(identity=pag, blur=seg, pool=kv_downsample and {st.transformer_blocks[0]: sm for st, sm in kv_downsample.items()},
+                          tile=tile_attention and self._tile_pairs(tile_attention, x.shape[1], x.shape[2], int(tile_shift) % 4))
         if sa.perturbed and (nb != 1 or two_queues or halves_identical):
             raise ValueError(f"forward_nhwc: the perturbed evaluation ({'pag' if seg is None else 'seg'}=) is one clip-half on one queue: "
                              "nb == 1, no two_queues, no halves_identical")
