@@ -343,30 +343,38 @@ class TransformerBlock(_Packed):
             self._kv_cache = (cross.root, ops.gemm(cross.ctx, pk["k2"]), ops.gemm(cross.ctx, pk["v2"], transpose_out=True), {})
         return self._kv_cache[1:]
 
-    def _tiled_attention(self, pk, n, kv, B, grid, sigma, pool, tile):
-        """Steps 2 and 3 of forward for a block of SelfAttnCall.tile: projections on tile-major rows, attention per tile, output in frame order."""
+    def _self_attention(self, pk, n, kv, B, L, grid, sigma, pool, tile):
+        """Steps 2 and 3 of forward, as SelfAttnCall states them: the projections -- q from n (blurred where sigma is given), k and v^T from kv or
+        from its downsampled grid -- and the attention launch.  With `tile` the rows are in tile-major order from the projections to the
+        attention (B t^2 batch items of Lt tokens) and the output goes back to frame order; without, the one "tile" is the frame (Bt = B,
+        Lt = L) and nothing is reordered."""
         C, H = self.dim, self.heads
-        (Hh, Ww), (t, shift) = grid, tile
-        Lt = (Hh // t) * (Ww // t)
-        Bt = B * t * t
-        stride = (Lt + 7) // 8 * 8                                       # K / V rows per tile; q has Lt
-        if n is kv and pool is None and sigma is None and stride == Lt:
-            src = ops.token_tile(n, B, Hh, Ww, t, shift)[0]              # one reorder feeds the fused q|k GEMM
+        t, shift = tile or (1, None)
+        th, tw = (grid[0] // t, grid[1] // t) if grid is not None else (None, None)
+        Bt, Lt = (B, L) if tile is None else (B * t * t, th * tw)
+        pad = None if tile is None else (Lt + 7) // 8 * 8                # K / V rows per tile; q has Lt
+
+        def order(x, stride=None):
+            """Frame order -> tile-major order."""
+            return x if tile is None else ops.token_tile(x, B, grid[0], grid[1], t, shift, tile_stride=stride)[0]
+
+        if n is kv and pool is None and sigma is None and pad in (None, Lt):    # (tiled: only where the K / V rows of a tile need no pad)
+            src = order(n)                                               # one reorder feeds the fused q|k GEMM
             qk = ops.gemm(src, pk["qk1"])
             q, k, Lk, stride = qk[:, :C], qk[:, C:], Lt, None
-        else:
+        else:                                                            # q alone and contiguous: k is not made from n, or q goes through the blur
             if sigma is not None:                                        # blur then tile: the queries are blurred over the whole frame grid
-                q = ops.token_tile(ops.token_blur(ops.gemm(n, pk["q1"]), B, Hh, Ww, sigma), B, Hh, Ww, t, shift)[0]
+                q = order(ops.token_blur(ops.gemm(n, pk["q1"]), B, grid[0], grid[1], sigma))
             else:
-                q = ops.gemm(ops.token_tile(n, B, Hh, Ww, t, shift)[0], pk["q1"])
+                q = ops.gemm(order(n), pk["q1"])
             if pool is None:
-                src, Lk = ops.token_tile(kv, B, Hh, Ww, t, shift, tile_stride=stride)[0], Lt
+                src, Lk, stride = order(kv, pad), Lt, pad
             else:                                                        # tile then pool: every tile is one "frame" of th x tw tokens
-                src, Lk, stride = ops.token_pool(ops.token_tile(kv, B, Hh, Ww, t, shift)[0], Bt, Hh // t, Ww // t, pool[0], pool[1])
+                src, Lk, stride = ops.token_pool(order(kv), Bt, th, tw, pool[0], pool[1])
             k = ops.gemm(src, pk["k1"])                                  # (pad rows are zeros, to_k / to_v have no bias: zero K rows, zero V^T columns)
         vt = ops.gemm(src, pk["v1"], transpose_out=True)
         a = ops.attention(q, k, vt, Bt, H, C // H, Lt, Lk, kv_stride=stride)
-        return ops.token_untile(a, B, Hh, Ww, t, shift)
+        return a if tile is None else ops.token_untile(a, B, grid[0], grid[1], t, shift)
 
     def forward(self, h, B, L, cross, sa=PLAIN, grid=None):
         """h: [B*L, C] tokens.  Returns tokens.  sa: the call's SelfAttnCall; grid: (Hh, Ww) of the L tokens, for a block that pools, blurs or tiles."""
@@ -404,23 +412,8 @@ class TransformerBlock(_Packed):
         if identity:
             # 2. no q, no k;  3. identity attention map: every query row takes its own V row
             a = ops.gemm(kv, pk["v1"])
-        elif tile is not None:
-            a = self._tiled_attention(pk, n, kv, B, grid, sigma, pool, tile)
         else:
-            # 2. projections: q from n (blurred where selected), k and v^T from kv or from its downsampled grid
-            if n is kv and pool is None and sigma is None:
-                qk = ops.gemm(n, pk["qk1"])
-                q, k, src, Lk, stride = qk[:, :C], qk[:, C:], kv, L, None
-            else:
-                q = ops.gemm(n, pk["q1"])                                # q alone and contiguous: k is not made from n, or q goes through the blur
-                if sigma is not None:
-                    q = ops.token_blur(q, B, grid[0], grid[1], sigma)
-                # (the pooled grid's pad rows are zeros and to_k / to_v have no bias: zero K rows, zero V^T columns)
-                src, Lk, stride = (kv, L, None) if pool is None else ops.token_pool(kv, B, grid[0], grid[1], pool[0], pool[1])
-                k = ops.gemm(src, pk["k1"])
-            vt = ops.gemm(src, pk["v1"], transpose_out=True)
-            # 3. attention
-            a = ops.attention(q, k, vt, B, H, D, L, Lk, kv_stride=stride)
+            a = self._self_attention(pk, n, kv, B, L, grid, sigma, pool, tile)
         kv2 = self.context_kv(cross)
         zf = min(cross.zero_frames, B) if ZERO_CONTEXT_SKIP else 0
         if zf:

@@ -175,17 +175,22 @@ def gemm_ln(a, wf, sc, eps=1e-5, rowadd=None, rows_per_group=0, act=ACT_NONE, ou
     return out
 
 
-_gn_ws = {}
+_workspaces = {}
+
+
+def _workspace(who, device, need, dtype=torch.float32, floor=0):
+    """The workspace of entry point `who` on this (device, current stream): one cache per entry point, so that no two ever share a buffer;
+    kept until it is too small for `need` bytes, then replaced by one of max(need, floor) bytes rounded up to whole elements of `dtype`."""
+    cache = _workspaces.setdefault(who, {})
+    key = (device, torch.cuda.current_stream().cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() * dtype.itemsize < need:
+        ws = cache[key] = torch.empty((max(need, floor) + dtype.itemsize - 1) // dtype.itemsize, device=device, dtype=dtype)
+    return ws
 
 
 def _gn_workspace(x, B, HW, C, groups):
-    need = _lib.load().md_groupnorm_workspace_bytes(B, HW, C, groups)
-    key = (x.device, torch.cuda.current_stream().cuda_stream)
-    ws = _gn_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((max(need, 1 << 20) + 3) // 4, device=x.device, dtype=torch.float32)
-        _gn_ws[key] = ws
-    return ws
+    return _workspace("groupnorm", x.device, _lib.load().md_groupnorm_workspace_bytes(B, HW, C, groups), floor=1 << 20)
 
 
 def gemm_affine_plan(M, N, K, rows_per_image, x=None):
@@ -348,21 +353,13 @@ def window_accumulate_weighted(pred, noise_sum, counter, window, weights, f, fto
               weights.data_ptr(), f, ftot, hw, halves, _st())
 
 
-_rs_ws = {}
-
-
 def cfg_guidance_rescale(noise_sum, counter, ftot, hw, guidance, phi, out=None):
     """Guidance rescale factor (md_cfg_guidance_rescale): fp32 (1,) device tensor 1 - phi + phi std(c) / std(v) of the guided output
     v = u + guidance (c - u) of a CFG noise_sum (2, ftot, hw, 4); 1 when std(v) == 0.  Stays on the device: pass it as `vscale=` to
     cfg_ddim_step / cfg_multistep_step.  The workspace is kept per (device, stream) and reused."""
     _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
     assert noise_sum.is_contiguous() and noise_sum.numel() == 2 * ftot * hw * 4 and counter.numel() >= ftot
-    need = _lib.load().md_cfg_rescale_workspace_bytes(ftot, hw)
-    key = (noise_sum.device, torch.cuda.current_stream().cuda_stream)
-    ws = _rs_ws.get(key)
-    if ws is None or ws.numel() * 8 < need:
-        ws = torch.empty((max(need, 1 << 14) + 7) // 8, device=noise_sum.device, dtype=torch.float64)
-        _rs_ws[key] = ws
+    ws = _workspace("cfg_guidance_rescale", noise_sum.device, _lib.load().md_cfg_rescale_workspace_bytes(ftot, hw), torch.float64, 1 << 14)
     if out is None:
         out = torch.empty((1,), device=noise_sum.device, dtype=torch.float32)
     _chk(out, "out", torch.float32)
@@ -420,9 +417,6 @@ def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance,
               float(c_m0), float(c_m1), float(c_z), _st())
 
 
-_apg_ws = {}
-
-
 def _apg_buffers(momentum_buf, coef, ftot, hw):
     _chk(momentum_buf, "momentum_buf", torch.float32); _chk(coef, "coef", torch.float32)
     assert momentum_buf.is_contiguous() and momentum_buf.numel() == ftot * hw * 4 and coef.is_contiguous() and coef.numel() == ftot * 2
@@ -436,12 +430,7 @@ def cfg_apg_prepare(latents, noise_sum, counter, momentum_buf, coef, ftot, hw, a
     cfg_multistep_step_apg with the same alpha / sigma.  The workspace is kept per (device, stream) and reused."""
     bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, 0.0, None, None)
     mp, cp = _apg_buffers(momentum_buf, coef, ftot, hw)
-    need = _lib.load().md_cfg_apg_workspace_bytes(ftot, hw)
-    key = (noise_sum.device, torch.cuda.current_stream().cuda_stream)
-    ws = _apg_ws.get(key)
-    if ws is None or ws.numel() * 8 < need:
-        ws = torch.empty((max(need, 1 << 14) + 7) // 8, device=noise_sum.device, dtype=torch.float64)
-        _apg_ws[key] = ws
+    ws = _workspace("cfg_apg_prepare", noise_sum.device, _lib.load().md_cfg_apg_workspace_bytes(ftot, hw), torch.float64, 1 << 14)
     n = ftot * hw * 4
     _lib.call("md_cfg_apg_prepare", *bufs, mp, ftot, hw, 2, float(alpha_s), float(sigma_s), float(momentum), float(eta), float(norm_threshold),
               ws.data_ptr(), ws.numel() * 8, cp, _st(), meta=(f"cfg_apg_prepare F={ftot} HW={hw}", 0.0, (2.0 + 8.0 + 8.0) * n))
@@ -494,9 +483,6 @@ def cfg_multistep_step_pag(latents, noise_sum, counter, history, perturbed_sum, 
               float(pag_scale), float(alpha_s), float(sigma_s), float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
 
 
-_fi_ws = {}
-
-
 def free_init_mix(out, x0, noise0, z, lpf, a, b):
     """FreeInit's frequency mix (md_free_init_mix_f16): out = fp16(z + IDFT3(lpf * DFT3(a x0 + b noise0 - z))) per channel over (F, H, W).
     out / x0 / noise0 / z: contiguous (F, H, W, 4) fp16, out may be x0; lpf: contiguous (F, H, W) fp32, unshifted order
@@ -511,12 +497,7 @@ def free_init_mix(out, x0, noise0, z, lpf, a, b):
         raise _lib.MdanceHipError(f"free_init_mix: no kernel for a clip of F={F} H={H} W={W} (every axis must be 1..256)")
     assert all(t.is_contiguous() and t.shape == out.shape for t in (out, x0, noise0, z)), [tuple(t.shape) for t in (out, x0, noise0, z)]
     assert lpf.is_contiguous() and tuple(lpf.shape) == (F, H, W), (tuple(lpf.shape), (F, H, W))
-    need = _lib.load().md_free_init_workspace_bytes(F, H, W)
-    key = (out.device, torch.cuda.current_stream().cuda_stream)
-    ws = _fi_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((need + 3) // 4, device=out.device, dtype=torch.float32)
-        _fi_ws[key] = ws
+    ws = _workspace("free_init_mix", out.device, _lib.load().md_free_init_workspace_bytes(F, H, W))
     n = F * H * W * 4
     _lib.call("md_free_init_mix_f16", out.data_ptr(), x0.data_ptr(), noise0.data_ptr(), z.data_ptr(), lpf.data_ptr(), F, H, W, float(a), float(b),
               ws.data_ptr(), ws.numel() * 4, _st(),
@@ -606,7 +587,6 @@ def blur_taps(sigma, n):
 
 
 _blur_tables = {}
-_blur_ws = {}
 
 
 def token_blur(x, B, Hh, Ww, sigma, out=None):
@@ -625,12 +605,7 @@ def token_blur(x, B, Hh, Ww, sigma, out=None):
     if out is None:
         out = torch.empty_like(x)
     assert out.is_contiguous() and out.shape == x.shape, (tuple(out.shape), tuple(x.shape))
-    need = _lib.load().md_token_blur_workspace_bytes(B, Hh, Ww, C)
-    key = (x.device, torch.cuda.current_stream().cuda_stream)
-    ws = _blur_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
-        _blur_ws[key] = ws
+    ws = _workspace("token_blur", x.device, _lib.load().md_token_blur_workspace_bytes(B, Hh, Ww, C))
     n = B * Hh * Ww * C
     if math.isinf(sigma):
         _lib.call("md_token_mean_f16", x.data_ptr(), out.data_ptr(), B, Hh * Ww, C, ws.data_ptr(), _st(),

@@ -149,6 +149,10 @@ class _UNetBase(_Packed):
             self.conv_out = Conv(c0, 4, 3)
         self.norm_eps = norm_eps
         self._cross_cache = {}
+        # the resolution levels, highest first: level i is down_blocks.i and the up block at the same resolution, up_blocks.(n - 1 - i), and the
+        # last level also mid_block; its token grid is the latent halved i times with ceil (level_grids)
+        self._levels = tuple(((f"down_blocks.{i}", self.down_blocks[i]), (f"up_blocks.{n - 1 - i}", self.up_blocks[n - 1 - i]))
+                             + ((("mid_block", self.mid_block),) if i == n - 1 else ()) for i in range(n))
 
     def _register_extra(self):
         pass
@@ -283,6 +287,25 @@ class _UNetBase(_Packed):
             picked += [b for b in hit if not any(b is q for q in picked)]
         return tuple(picked)
 
+    def _level_transformers(self, i):
+        """The SpatialTransformers of level i of self._levels (has_cross_attention is read at every use, as the forward reads it)."""
+        return [a for _, blk in self._levels[i] if blk.has_cross_attention for a in blk.attentions]
+
+    def _level_plan(self, what, factors, values):
+        """{SpatialTransformer: values[i]} for every spatial transformer of a level i whose factor is > 1, or None when no factor is; `what`:
+        the keyword the error messages name."""
+        if len(factors) > len(self._levels):
+            raise ValueError(f"{what}: {len(factors)} factors for a UNet of {len(self._levels)} resolution levels")
+        plan = {}
+        for i, s in enumerate(factors):
+            if s == 1:
+                continue
+            hit = self._level_transformers(i)
+            if not hit:
+                raise ValueError(f"{what}: factor {s} on level {i}, which has no attention block ({', '.join(nm for nm, _ in self._levels[i])})")
+            plan.update({a: values[i] for a in hit})
+        return plan or None
+
     def kv_downsample_plan(self, factors, mode="nearest"):
         """The per-block plan of K / V token downsampling (ToDo, arXiv 2402.13573) that forward_nhwc(kv_downsample=) takes:
         {SpatialTransformer: (s, mode)} for every spatial transformer of a level whose factor is > 1, or None when no factor is.
@@ -290,22 +313,7 @@ class _UNetBase(_Packed):
         the up block at the same resolution, up_blocks.(levels - 1 - i), and the last level also mid_block; missing levels mean 1 = untouched.
         ValueError for anything else, for more factors than levels and for a factor > 1 on a level without an attention block."""
         factors, mode = check_kv_downsample(factors, mode)
-        n = len(self.down_blocks)
-        if len(factors) > n:
-            raise ValueError(f"kv_downsample: {len(factors)} factors for a UNet of {n} resolution levels")
-        plan = {}
-        for i, s in enumerate(factors):
-            if s == 1:
-                continue
-            names = [(f"down_blocks.{i}", self.down_blocks[i]), (f"up_blocks.{n - 1 - i}", self.up_blocks[n - 1 - i])]
-            if i == n - 1:
-                names.append(("mid_block", self.mid_block))
-            hit = [a for _, blk in names if blk.has_cross_attention for a in blk.attentions]
-            if not hit:
-                raise ValueError(f"kv_downsample: factor {s} on level {i}, which has no attention block ({', '.join(nm for nm, _ in names)})")
-            for a in hit:
-                plan[a] = (s, mode)
-        return plan or None
+        return self._level_plan("kv_downsample", factors, [(s, mode) for s in factors])
 
     def tile_attention_plan(self, factors):
         """The per-block plan of shifted-tile self-attention (MSW-MSA of HiDiffusion, arXiv 2311.17528) that forward_nhwc(tile_attention=)
@@ -313,39 +321,20 @@ class _UNetBase(_Packed):
         levels as kv_downsample_plan.  ValueError for anything else, for more factors than levels and for a factor > 1 on a level without an
         attention block.  (That t divides the level's grid depends on the latent: check_tile_attention_grid.)"""
         factors, _ = check_tile_attention(factors, "none")
-        n = len(self.down_blocks)
-        if len(factors) > n:
-            raise ValueError(f"tile_attention: {len(factors)} factors for a UNet of {n} resolution levels")
-        plan = {}
-        for i, t in enumerate(factors):
-            if t == 1:
-                continue
-            names = [(f"down_blocks.{i}", self.down_blocks[i]), (f"up_blocks.{n - 1 - i}", self.up_blocks[n - 1 - i])]
-            if i == n - 1:
-                names.append(("mid_block", self.mid_block))
-            hit = [a for _, blk in names if blk.has_cross_attention for a in blk.attentions]
-            if not hit:
-                raise ValueError(f"tile_attention: factor {t} on level {i}, which has no attention block ({', '.join(nm for nm, _ in names)})")
-            for a in hit:
-                plan[a] = t
-        return plan or None
+        return self._level_plan("tile_attention", factors, factors)
+
+    def _per_block(self, plan, hh, ww, value=lambda v, h, w: v):
+        """{TransformerBlock: value(plan[its SpatialTransformer], h, w)} of a per-level plan for an hh x ww latent, h x w the token grid of the
+        transformer's level: what forward_nhwc puts into the call's SelfAttnCall."""
+        out = {}
+        for i, (h, w) in enumerate(level_grids(hh, ww, len(self._levels))):
+            out.update({st.transformer_blocks[0]: value(plan[st], h, w) for st in self._level_transformers(i) if st in plan})
+        return out
 
     def _tile_pairs(self, plan, hh, ww, q):
-        """{TransformerBlock: (t, (sy, sx))} of a tile_attention_plan for an hh x ww latent at shift index q: a transformer of level i works on
-        the grid halved i times with ceil, and (sy, sx) = (q th // 4, q tw // 4) with th x tw its tile."""
-        n = len(self.down_blocks)
-        level = {}
-        for i in range(n):
-            for blk in [self.down_blocks[i], self.up_blocks[n - 1 - i]] + ([self.mid_block] if i == n - 1 else []):
-                if blk.has_cross_attention:
-                    level.update({a: i for a in blk.attentions})
-        pairs = {}
-        for st, t in plan.items():
-            h, w = hh, ww
-            for _ in range(level[st]):
-                h, w = (h + 1) // 2, (w + 1) // 2
-            pairs[st.transformer_blocks[0]] = (t, (q * (h // t) // 4, q * (w // t) // 4))
-        return pairs
+        """{TransformerBlock: (t, (sy, sx))} of a tile_attention_plan for an hh x ww latent at shift index q: (sy, sx) = (q th // 4, q tw // 4)
+        with th x tw the tile of the transformer's level."""
+        return self._per_block(plan, hh, ww, lambda t, h, w: (t, (q * (h // t) // 4, q * (w // t) // 4)))
 
     @property
     def dtype(self):
@@ -386,30 +375,42 @@ def check_pag_layer_names(applied_layers, what="pag_applied_layers"):
 KV_POOL_MODES = ("nearest", "mean")
 
 
-def check_kv_downsample(factors, mode):
-    """kv_downsample / kv_downsample_mode as (tuple of integer factors 1..8, mode); an int n stands for (n,).  ValueError otherwise.  Needs no
-    model: the pipeline calls it before anything runs."""
+def _check_factors(what, factors):
+    """The per-level factors of the keyword `what` as a tuple of integers 1..8; an int n stands for (n,).  ValueError otherwise."""
     import numbers
     if isinstance(factors, numbers.Integral) and not isinstance(factors, bool):
         factors = (factors,)
     try:
         factors = tuple(factors)
     except TypeError:
-        raise ValueError(f"kv_downsample must be an integer or a sequence of integers, got {factors!r}") from None
+        raise ValueError(f"{what} must be an integer or a sequence of integers, got {factors!r}") from None
     for v in factors:
         if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not 1 <= v <= 8:
-            raise ValueError(f"kv_downsample: every factor must be an integer in 1..8, got {v!r}")
+            raise ValueError(f"{what}: every factor must be an integer in 1..8, got {v!r}")
+    return tuple(int(v) for v in factors)
+
+
+def level_grids(h, w, levels):
+    """The token grid (h, w) of each of `levels` resolution levels of an h x w latent: the levels halve with ceil, as the stride-2 conv does."""
+    for _ in range(levels):
+        yield h, w
+        h, w = (h + 1) // 2, (w + 1) // 2
+
+
+def check_kv_downsample(factors, mode):
+    """kv_downsample / kv_downsample_mode as (tuple of integer factors 1..8, mode); an int n stands for (n,).  ValueError otherwise.  Needs no
+    model: the pipeline calls it before anything runs."""
+    factors = _check_factors("kv_downsample", factors)
     if mode not in KV_POOL_MODES:
         raise ValueError(f"kv_downsample_mode must be one of {KV_POOL_MODES}, got {mode!r}")
-    return tuple(int(v) for v in factors), mode
+    return factors, mode
 
 
 def check_kv_downsample_grid(factors, h, w):
-    """Refuses a factor whose level of an h x w latent has no s x s block to pool (the levels halve with ceil, as the stride-2 conv does)."""
-    for i, s in enumerate(factors):
+    """Refuses a factor whose level of an h x w latent has no s x s block to pool."""
+    for i, (s, (h, w)) in enumerate(zip(factors, level_grids(h, w, len(factors)))):
         if s > 1 and (h // s < 1 or w // s < 1):
             raise ValueError(f"kv_downsample: factor {s} on level {i}, whose token grid is {h} x {w} for this latent size: nothing left to attend to")
-        h, w = (h + 1) // 2, (w + 1) // 2
 
 
 TILE_SHIFTS = ("cycle", "none")
@@ -418,25 +419,16 @@ TILE_SHIFTS = ("cycle", "none")
 def check_tile_attention(factors, shift):
     """tile_attention / tile_attention_shift as (tuple of integer factors 1..8, shift); an int n stands for (n,), a missing level or 1 means
     untouched; shift is one of TILE_SHIFTS.  ValueError otherwise.  Needs no model: the pipeline calls it before anything runs."""
-    import numbers
-    if isinstance(factors, numbers.Integral) and not isinstance(factors, bool):
-        factors = (factors,)
-    try:
-        factors = tuple(factors)
-    except TypeError:
-        raise ValueError(f"tile_attention must be an integer or a sequence of integers, got {factors!r}") from None
-    for v in factors:
-        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not 1 <= v <= 8:
-            raise ValueError(f"tile_attention: every factor must be an integer in 1..8, got {v!r}")
+    factors = _check_factors("tile_attention", factors)
     if shift not in TILE_SHIFTS:
         raise ValueError(f"tile_attention_shift must be one of {TILE_SHIFTS}, got {shift!r}")
-    return tuple(int(v) for v in factors), shift
+    return factors, shift
 
 
 def check_tile_attention_grid(factors, h, w, kv_factors=()):
-    """Refuses a factor t that does not divide both sides of its level's token grid of an h x w latent (the levels halve with ceil, as the
-    stride-2 conv does), and one whose th x tw tile has no s x s block for that level's kv_downsample factor s (tile then pool)."""
-    for i, t in enumerate(factors):
+    """Refuses a factor t that does not divide both sides of its level's token grid of an h x w latent, and one whose th x tw tile has no
+    s x s block for that level's kv_downsample factor s (tile then pool)."""
+    for i, (t, (h, w)) in enumerate(zip(factors, level_grids(h, w, len(factors)))):
         if t > 1:
             if h % t or w % t:
                 raise ValueError(f"tile_attention: factor {t} on level {i}, whose token grid is {h} x {w} for this latent size: {t} must divide both sides")
@@ -444,7 +436,6 @@ def check_tile_attention_grid(factors, h, w, kv_factors=()):
             if s > 1 and (h // t < s or w // t < s):
                 raise ValueError(f"tile_attention: factor {t} on level {i} leaves tiles of {h // t} x {w // t} tokens, smaller than that level's "
                                  f"kv_downsample factor {s}")
-        h, w = (h + 1) // 2, (w + 1) // 2
 
 
 def tile_shift_at(shift, k):
@@ -524,7 +515,7 @@ class UNet3DConditionModel(_UNetBase):
         two_queues (with halves_identical): behind those shared layers the unconditional and the conditional half are independent all the way
         to the output (per-image GroupNorm, per-row attention and LayerNorm, per-clip-half temporal attention: src/models/unet_3d_mix.py:
         418-598, src/models/mutual_mix_attention.py:173-201), and they are evaluated as TWO KERNEL QUEUES (_forward_two_queues)."""
-        sa = SelfAttnCall(identity=pag, blur=seg, pool=kv_downsample and {st.transformer_blocks[0]: sm for st, sm in kv_downsample.items()},
+        sa = SelfAttnCall(identity=pag, blur=seg, pool=kv_downsample and self._per_block(kv_downsample, x.shape[1], x.shape[2]),
                           tile=tile_attention and self._tile_pairs(tile_attention, x.shape[1], x.shape[2], int(tile_shift) % 4))
         if sa.perturbed and (nb != 1 or two_queues or halves_identical):
             raise ValueError(f"forward_nhwc: the perturbed evaluation ({'pag' if seg is None else 'seg'}=) is one clip-half on one queue: "

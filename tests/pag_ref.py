@@ -8,19 +8,17 @@ which tests/fake_ops.py installs with its own.
     perturbed_forward(den_sd, x, t, ctx, banks, names)      oracle.cpu_ref.denoising_unet_forward as the perturbed conditional evaluation
     denoise_loop(..., pag_scale=, pag_adaptive_scale=, pag_layers=)   tests/fusion_ref.denoise_loop with PAG; pag_scale=0 is that loop op for op
     cfg_ddim_step_pag / cfg_multistep_step_pag              the operators' emulations (installed by fake_ops.install)
-The oracle is not edited: inside `perturbed(...)`, and in this process only, its transformer_block_read is swapped for one that takes the
-identity in place of the self-attention map for the selected prefixes.
+The oracle is not edited: the perturbed block and the patcher that swaps it in for the selected prefixes are tests/selfattn_ref.py's.
 """
-import contextlib
 import re
 
 import torch
-import torch.nn.functional as F
 
 from oracle import cpu_ref as O
 
 import fake_ops
 import fusion_ref as FR
+import selfattn_ref as SA
 
 
 # ---- the definition
@@ -69,34 +67,12 @@ def select(prefixes, names):
 # ---- the perturbed evaluation on the oracle
 def _read_identity(sd, p, x, ctx, bank):
     """oracle transformer_block_read(cfg=False) with the identity for softmax(q k^T d^-1/2): attn1 = to_out(to_v(norm1(x) + bank))."""
-    n = O.layer_norm(sd, p + "norm1.", x)
-    kv = n + bank if bank is not None else n
-    v = F.linear(kv, sd[p + "attn1.to_v.weight"])
-    x = F.linear(v, sd[p + "attn1.to_out.0.weight"], sd[p + "attn1.to_out.0.bias"]) + x
-    x = O.attention(sd, p + "attn2.", O.layer_norm(sd, p + "norm2.", x), ctx) + x
-    x = O.feed_forward(sd, p + "ff.", O.layer_norm(sd, p + "norm3.", x)) + x
-    return x
+    return SA.block_read(sd, p, x, ctx, bank, False, identity=True)
 
 
-@contextlib.contextmanager
 def perturbed(selected):
-    """Within the block, the oracle's read blocks whose key prefix is in `selected` use the identity attention map."""
-    orig = O.transformer_block_read
-    keys = {p + ".transformer_blocks.0." for p in selected}
-    seen = []
-
-    def read(sd, p, x, ctx, bank, cfg=True):
-        if p not in keys:
-            return orig(sd, p, x, ctx, bank, cfg)
-        assert not cfg, "the perturbed evaluation is conditional-only"
-        seen.append(p)
-        return _read_identity(sd, p, x, ctx, bank)
-
-    O.transformer_block_read = read
-    try:
-        yield seen
-    finally:
-        O.transformer_block_read = orig
+    """Within the block, the oracle's read blocks whose key prefix is in `selected` use the identity attention map (selfattn_ref.modified)."""
+    return SA.modified(identity=selected)
 
 
 def perturbed_forward(den_sd, x, t, ctx, banks, names):
@@ -104,7 +80,7 @@ def perturbed_forward(den_sd, x, t, ctx, banks, names):
     sel = select(block_prefixes(den_sd), names)
     with perturbed(sel) as seen:
         out = O.denoising_unet_forward(den_sd, x, t, ctx, banks, cfg=False)
-    assert sorted(seen) == sorted(p + ".transformer_blocks.0." for p in sel), (seen, sel)
+    assert sorted(s[0] for s in seen) == sorted(p + ".transformer_blocks.0." for p in sel), (seen, sel)
     return out
 
 

@@ -9,19 +9,17 @@ oracle/cpu_ref.py, and a CPU emulation of ops.token_blur, which tests/fake_ops.p
     block_read(sd, p, x, ctx, bank, Hh, Ww, sigma, kv_pool) the perturbed conditional read block with blurred queries
     perturbed_forward(...), denoise_loop(..., seg_scale=, seg_blur_sigma=, seg_layers=)   tests/pag_ref.denoise_loop with SEG's perturbation
     token_blur                                              the operator's emulation (installed by fake_ops.install)
-The oracle is not edited: inside `perturbed(...)`, and in this process only, its transformer_3d is wrapped to note the grid and its
-transformer_block_read is swapped for block_read on the selected prefixes.
+The oracle is not edited: the perturbed block and the patcher that swaps it in for the selected prefixes are tests/selfattn_ref.py's.
 """
-import contextlib
 import math
 
 import torch
-import torch.nn.functional as F
 
 from oracle import cpu_ref as O
 
 import fake_ops
 import pag_ref as P
+import selfattn_ref as SA
 import todo_ref as T
 
 
@@ -103,54 +101,15 @@ def bound(x, B, Hh, Ww, sigma):
 
 
 # ---- the perturbed block
-def block_read(sd, p, x, ctx, bank, Hh, Ww, sigma, kv_pool=None, heads=O.HEADS):
+def block_read(sd, p, x, ctx, bank, Hh, Ww, sigma, kv_pool=None):
     """oracle transformer_block_read(cfg=False) with the QUERIES blurred over the Hh x Ww grid: q = blur(to_q(norm1(x))), k / v from
     norm1(x) + bank (pooled by kv_pool = (s, mode) AFTER the add, when given)."""
-    B, L, C = x.shape
-    n = O.layer_norm(sd, p + "norm1.", x)
-    kv = n + bank if bank is not None else n
-    if kv_pool is not None:
-        kv = T.pool(kv, B, Hh, Ww, *kv_pool)
-    a = p + "attn1."
-    q = F.linear(n, sd[a + "to_q.weight"])
-    q = blur64(q.reshape(B * L, C), B, Hh, Ww, sigma).to(q.dtype).reshape(B, L, C)
-    k, v = F.linear(kv, sd[a + "to_k.weight"]), F.linear(kv, sd[a + "to_v.weight"])
-    d = C // heads
-    q, k, v = (t.view(B, -1, heads, d).transpose(1, 2) for t in (q, k, v))
-    o = O._sdpa(q, k, v).transpose(1, 2).reshape(B, L, C)
-    x = F.linear(o, sd[a + "to_out.0.weight"], sd[a + "to_out.0.bias"]) + x
-    x = O.attention(sd, p + "attn2.", O.layer_norm(sd, p + "norm2.", x), ctx) + x
-    x = O.feed_forward(sd, p + "ff.", O.layer_norm(sd, p + "norm3.", x)) + x
-    return x
+    return SA.block_read(sd, p, x, ctx, bank, False, (Hh, Ww), sigma=sigma, pool=kv_pool)
 
 
-@contextlib.contextmanager
 def perturbed(selected, sigma):
-    """Within the block, the oracle's read blocks whose key prefix is in `selected` blur their queries.  Yields [(prefix, Hh, Ww)]."""
-    orig_t3d, orig_read = O.transformer_3d, O.transformer_block_read
-    keys = {p + ".transformer_blocks.0." for p in selected}
-    grid, seen = [], []
-
-    def transformer_3d(sd, p, x, ctx_per_frame, bank, cfg):
-        grid.append(tuple(x.shape[2:]))
-        try:
-            return orig_t3d(sd, p, x, ctx_per_frame, bank, cfg)
-        finally:
-            grid.pop()
-
-    def read(sd, p, x, ctx, bank, cfg=True):
-        if p not in keys:
-            return orig_read(sd, p, x, ctx, bank, cfg)
-        assert not cfg, "the perturbed evaluation is conditional-only"
-        Hh, Ww = grid[-1]
-        seen.append((p, Hh, Ww))
-        return block_read(sd, p, x, ctx, bank, Hh, Ww, sigma)
-
-    O.transformer_3d, O.transformer_block_read = transformer_3d, read
-    try:
-        yield seen
-    finally:
-        O.transformer_3d, O.transformer_block_read = orig_t3d, orig_read
+    """Within the block, the oracle's read blocks whose key prefix is in `selected` blur their queries (selfattn_ref.modified)."""
+    return SA.modified(blur=selected, sigma=sigma)
 
 
 def perturbed_forward(den_sd, x, t, ctx, banks, names, sigma):

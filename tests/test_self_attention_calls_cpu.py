@@ -26,6 +26,17 @@ The recording was made at the parent commit with this module and the old spellin
         got = {kind: t.trace_all(mp, kind, old) for kind in ("2d", "3d")}
     assert got["2d"] == got["3d"]
     json.dump(t.pack(got["2d"]), open(t.GOLDEN, "w"), indent=0)
+
+tests/golden/self_attention_option_calls.json is a second recording, of what the block issued BEFORE its two projection paths (the plain one in
+TransformerBlock.forward and the tile-major one beside it) became one method: at the grids of GRIDS -- 8 x 8, where a t = 2 tile holds
+Lt = 16 tokens (the fused tiled path), and 4 x 6, where it holds Lt = 6, roundup8(Lt) != Lt (the unfused padded path; plain L = 24) -- every
+block state of STATES under every option set of OPTIONS (none, pool, tile, tile + pool), and the perturbed evaluation under every entry of
+PERTURBED.  Per call it holds what the first recording holds and, behind "alias=", the pairs of tensor arguments that share their storage
+(the q | k halves of the fused GEMM's output, an in-place `out=`).  The block must issue exactly those, in that order: nothing is permitted
+to differ.  It was made at the parent commit with this module as it is:
+
+    import test_self_attention_calls_cpu as t
+    t.dump_options()
 """
 import inspect
 import json
@@ -72,14 +83,20 @@ def _describe(v, names):
     return repr(v)
 
 
-def _recorded(name, fn, log, names):
-    """fn, logging "name(arg=..., ...)" of every call: the arguments by name, those left at or given their default omitted."""
+def _recorded(name, fn, log, names, aliases=False):
+    """fn, logging "name(arg=..., ...)" of every call: the arguments by name, those left at or given their default omitted.  aliases: followed
+    by " alias=a~b,..." where two tensor arguments share their storage."""
     params = inspect.signature(fn).parameters
 
     def wrapper(*a, **kw):
         given = inspect.signature(fn).bind(*a, **kw).arguments
-        log.append(name + "(" + ", ".join(f"{k}={_describe(v, names)}" for k, v in given.items()
-                                          if isinstance(v, torch.Tensor) or not (v is params[k].default or v == params[k].default)) + ")")
+        rec = name + "(" + ", ".join(f"{k}={_describe(v, names)}" for k, v in given.items()
+                                     if isinstance(v, torch.Tensor) or not (v is params[k].default or v == params[k].default)) + ")"
+        if aliases:
+            ts = [(k, v.untyped_storage().data_ptr()) for k, v in given.items() if isinstance(v, torch.Tensor)]
+            pairs = [f"{a_}~{b_}" for i, (a_, pa) in enumerate(ts) for b_, pb in ts[i + 1:] if pa == pb]
+            rec += " alias=" + ",".join(pairs) if pairs else ""
+        log.append(rec)
         return fn(*a, **kw)
     return wrapper
 
@@ -165,3 +182,97 @@ def test_refused_combinations(monkeypatch):
             with pytest.raises(ValueError, match=f"does not hold L = {L}"):
                 blk(h.clone(), F, L, cross, sa=sa, grid=grid)
     blk.ref_mode, blk.ref_cfg, blk.bank = None, False, []
+
+
+# ------------------------------------------------------------------ the second recording: every option set at two grids
+OPTION_GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "self_attention_option_calls.json")
+GRIDS = {"8x8": (8, 8), "4x6": (4, 6)}
+POOL, TILE, SIGMA = (2, "mean"), (2, (1, 1)), 1.5
+# state -> (ref_mode, ref_cfg, stop_after_bank, rows of the CFG batch, clip-half)
+STATES = {"plain": (None, False, False, "all", None),
+          "write": ("write", False, False, "all", None),
+          "write-stop": ("write", False, True, "all", None),
+          "read": ("read", False, False, "cond", None),
+          "read-cfg": ("read", True, False, "all", None),
+          "half0": ("read", True, False, "uncond", 0),
+          "half1": ("read", True, False, "cond", 1)}
+OPTIONS = {"none": (None, None), "pool": (POOL, None), "tile": (None, TILE), "tile+pool": (POOL, TILE)}     # (pool, tile)
+# the perturbed evaluation (read + ref_cfg, the conditional rows, every row reads the bank): (perturbation, pool, tile)
+PERTURBED = {"identity": ("identity", None, None), "blur": ("blur", None, None), "blur+pool": ("blur", POOL, None), "blur+tile": ("blur", None, TILE),
+             "blur+tile+pool": ("blur", POOL, TILE), "identity+pool+tile": ("identity", POOL, TILE)}
+
+
+def trace_options(monkeypatch):
+    """{"grid/state/options" and "grid/perturbed/entry": [call, ...]} of the block of todo_ref.block_setup under the emulated operators."""
+    import tile_ref
+    fake_ops.install(monkeypatch)
+    monkeypatch.setattr(ops, "token_tile", tile_ref.token_tile, raising=False)
+    monkeypatch.setattr(ops, "token_untile", tile_ref.token_untile, raising=False)
+    log, names = [], {}
+    for name in [n for n in fake_ops._NAMES if n != "require_gpu"] + ["token_pool", "token_blur", "token_tile", "token_untile"]:
+        monkeypatch.setattr(ops, name, _recorded(name, getattr(ops, name), log, names, aliases=True))
+    out = {}
+    with torch.no_grad():
+        for gname, grid in GRIDS.items():
+            st = T.block_setup(DIM, DIM, grid[0], grid[1], F, torch.device("cpu"))
+            blk, L = st.blk, st.L
+            names.clear()
+            names.update({id(v): k for k, v in blk.packed().items() if isinstance(v, torch.Tensor)})
+            h = st.x.reshape(2 * F * L, DIM)
+            rows = {"all": (0, 2 * F), "uncond": (0, F), "cond": (F, 2 * F)}
+
+            def run(case, ref_mode, cfg, stop, which, sa):
+                lo, hi = rows[which]
+                blk.ref_mode, blk.ref_cfg, blk.stop_after_bank, blk._kv_cache = ref_mode, cfg, stop, None
+                blk.bank = [st.bank] if ref_mode == "read" else []
+                del log[:]
+                blk(h[lo * L:hi * L].clone(), hi - lo, L, st.cross if which == "all" else st.cross.rows(lo, hi), sa=sa, grid=grid)
+                out[f"{gname}/{case}"] = list(log)
+
+            for state, (ref_mode, cfg, stop, which, half) in STATES.items():
+                for oname, (pool, tile) in OPTIONS.items():
+                    run(f"{state}/{oname}", ref_mode, cfg, stop, which,
+                        blocks.SelfAttnCall(half=half, pool=pool and {blk: pool}, tile=tile and {blk: tile}))
+            for pname, (pert, pool, tile) in PERTURBED.items():
+                run(f"perturbed/{pname}", "read", True, False, "cond",
+                    blocks.SelfAttnCall(identity=(blk,) if pert == "identity" else None, blur=((blk,), SIGMA) if pert == "blur" else None,
+                                        pool=pool and {blk: pool}, tile=tile and {blk: tile}))
+            blk.ref_mode, blk.ref_cfg, blk.stop_after_bank, blk.bank = None, False, False, []
+    return out
+
+
+def dump_options(path=OPTION_GOLDEN):
+    with pytest.MonkeyPatch.context() as mp:
+        got = trace_options(mp)
+    with open(path, "w") as fh:
+        json.dump(pack(got), fh, indent=0)
+
+
+@pytest.fixture(scope="module")
+def option_traces():
+    with pytest.MonkeyPatch.context() as mp:
+        got = trace_options(mp)
+    with open(OPTION_GOLDEN) as fh:
+        return got, unpack(json.load(fh))
+
+
+OPTION_CASES = [f"{g}/{s}/{o}" for g in GRIDS for s in STATES for o in OPTIONS] + [f"{g}/perturbed/{p}" for g in GRIDS for p in PERTURBED]
+
+
+def test_the_option_recording_holds_every_case_and_no_other(option_traces):
+    got, want = option_traces
+    assert sorted(want) == sorted(OPTION_CASES) == sorted(got)
+    for g in GRIDS:
+        assert want[f"{g}/perturbed/identity+pool+tile"] == want[f"{g}/perturbed/identity"]          # no attention to shorten or to tile
+        assert not any(c.startswith(("attention(q=float16[", "token_")) and "kv_index" not in c for c in want[f"{g}/perturbed/identity"])
+    # the two tiled paths: 8 x 8 fuses q | k behind ONE reorder, 4 x 6 (Lt = 6) reorders q and the padded K / V source on their own
+    fused, padded = want["8x8/plain/tile"], want["4x6/plain/tile"]
+    assert len([c for c in fused if c.startswith("token_tile(")]) == 1 and any("w=qk1:" in c for c in fused)
+    assert len([c for c in padded if c.startswith("token_tile(")]) == 2 and not any("w=qk1:" in c for c in padded)
+    assert any(c.startswith("token_tile(") and "tile_stride=8" in c for c in padded)
+
+
+@pytest.mark.parametrize("case", OPTION_CASES)
+def test_block_issues_the_recorded_option_calls(option_traces, case):
+    got, want = option_traces
+    assert got[case] == want[case], case

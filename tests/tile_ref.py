@@ -13,18 +13,15 @@ after loop_helpers.worker_setup in a spawned worker.
     install(monkeypatch), install_process()                the emulations over mikudance_amd.ops; every attention / token_tile / token_untile call is
                                                            also noted with the TransformerBlock that made it (BLOCK_CALLS)
     block_runs(st, tile, ...)                              todo_ref.block_runs with the tile field
-The oracle is not edited: inside `tiled(...)`, and in this process only, its denoising_unet_forward is wrapped to note the timestep, its
-transformer_3d to note the grid, and its transformer_block_read is swapped for block_read on the selected prefixes.
+The oracle is not edited: the tiled block and the patcher that swaps it in on the selected levels are tests/selfattn_ref.py's.
 """
-import contextlib
-
 import torch
-import torch.nn.functional as F
 
 from oracle import cpu_ref as O
 
 import fake_ops
 import fusion_ref as FR
+import selfattn_ref as SA
 import todo_ref as T
 
 
@@ -52,87 +49,18 @@ def shift_at(mode, k, th, tw):
 
 
 # ---- one block
-def block_read(sd, p, x, ctx, bank, cfg, Hh, Ww, t, shift, pool=None, sigma=None, heads=O.HEADS):
+def block_read(sd, p, x, ctx, bank, cfg, Hh, Ww, t, shift, pool=None, sigma=None):
     """oracle transformer_block_read with the self-attention run inside every shifted tile: q from tile(norm1(x)) -- with sigma, from
     tile(blur(to_q(norm1(x)))), blurred over the whole frame grid first -- k / v from tile(norm1(x) + bank), pooled per tile by
     pool = (s, mode) when given; the output goes back to frame order in front of to_out.  Under cfg the unconditional first half attends
     to tile(norm1(x)) alone."""
-    B, L, C = x.shape
-    th, tw = Hh // t, Ww // t
-    a = p + "attn1."
-    d = C // heads
-    n = O.layer_norm(sd, p + "norm1.", x)
-
-    def attend(nq, kv):
-        b = nq.shape[0]
-        q = F.linear(nq, sd[a + "to_q.weight"])
-        if sigma is not None:
-            import seg_ref
-            q = seg_ref.blur64(q.reshape(b * L, C), b, Hh, Ww, sigma).to(q.dtype).reshape(b, L, C)
-        q, kv = tile(q, b, Hh, Ww, t, shift), tile(kv, b, Hh, Ww, t, shift)
-        if pool is not None:
-            kv = T.pool(kv, b * t * t, th, tw, *pool)
-        k, v = F.linear(kv, sd[a + "to_k.weight"]), F.linear(kv, sd[a + "to_v.weight"])
-        q, k, v = (z.view(b * t * t, -1, heads, d).transpose(1, 2) for z in (q, k, v))
-        o = O._sdpa(q, k, v).transpose(1, 2).reshape(b * t * t, th * tw, C)
-        return F.linear(untile(o, b, Hh, Ww, t, shift), sd[a + "to_out.0.weight"], sd[a + "to_out.0.bias"])
-
-    h = attend(n, n + bank if bank is not None else n) + x
-    if cfg:
-        half = B // 2
-        h = h.clone()
-        h[:half] = attend(n[:half], n[:half]) + x[:half]
-    x = h
-    x = O.attention(sd, p + "attn2.", O.layer_norm(sd, p + "norm2.", x), ctx) + x
-    x = O.feed_forward(sd, p + "ff.", O.layer_norm(sd, p + "norm3.", x)) + x
-    return x
+    return SA.block_read(sd, p, x, ctx, bank, cfg, (Hh, Ww), sigma=sigma, pool=pool, tile=(t, shift))
 
 
-@contextlib.contextmanager
 def tiled(den_sd, factors, shift="cycle", first_step=0, kv=None, step=None):
-    """Within the block, the oracle's read blocks on a level with a factor > 1 attend per shifted tile.  The step index of an evaluation is
-    first_step + the position of its timestep among the distinct timesteps seen so far (a FreeInit pass sees the same ones again), or
-    `step` where given (one forward outside a loop).  kv = (factors, mode): those levels' K / V are pooled inside each tile.  Yields the list
-    of (prefix, Hh, Ww, t, (sy, sx)) of every block evaluated that way."""
-    factors = T.check_factors(factors)
-    levels = O._n_levels(den_sd)
-    assert len(factors) <= levels, (factors, levels)
-    kv_factors, kv_mode = (T.check_factors(kv[0]), kv[1]) if kv is not None else ((), "nearest")
-    orig_fwd, orig_t3d, orig_read = O.denoising_unet_forward, O.transformer_3d, O.transformer_block_read
-    grid, seen, order, now = [], [], {}, []
-
-    def forward(sd, sample, t, *a, **kw):
-        key = float(torch.as_tensor(t).reshape(-1)[0])
-        now.append(step if step is not None else first_step + order.setdefault(key, len(order)))
-        try:
-            return orig_fwd(sd, sample, t, *a, **kw)
-        finally:
-            now.pop()
-
-    def transformer_3d(sd, p, x, ctx_per_frame, bank, cfg):
-        grid.append(tuple(x.shape[2:]))
-        try:
-            return orig_t3d(sd, p, x, ctx_per_frame, bank, cfg)
-        finally:
-            grid.pop()
-
-    def read(sd, p, x, ctx, bank, cfg=True, sigma=None):
-        t = T.factor_of(p, factors, levels)
-        if t == 1:
-            assert sigma is None
-            return orig_read(sd, p, x, ctx, bank, cfg)
-        Hh, Ww = grid[-1]
-        s = T.factor_of(p, kv_factors, levels) if kv_factors else 1
-        sh = shift_at(shift, now[-1], Hh // t, Ww // t)
-        seen.append((p, Hh, Ww, t, sh))
-        return block_read(sd, p, x, ctx, bank, cfg, Hh, Ww, t, sh, pool=(s, kv_mode) if s > 1 else None, sigma=sigma)
-
-    read.grid = grid
-    O.denoising_unet_forward, O.transformer_3d, O.transformer_block_read = forward, transformer_3d, read
-    try:
-        yield seen
-    finally:
-        O.denoising_unet_forward, O.transformer_3d, O.transformer_block_read = orig_fwd, orig_t3d, orig_read
+    """Within the block, the oracle's read blocks on a level with a factor > 1 attend per shifted tile (selfattn_ref.modified, which states
+    the step index); kv = (factors, mode): those levels' K / V are pooled inside each tile."""
+    return SA.modified(den_sd, pool=kv, tile=factors, shift=shift, first_step=first_step, step=step)
 
 
 def unet_forward(den_sd, x, t, ctx, banks, factors, shift=("none", 0), cfg=True):
@@ -141,39 +69,14 @@ def unet_forward(den_sd, x, t, ctx, banks, factors, shift=("none", 0), cfg=True)
         return O.denoising_unet_forward(den_sd, x, t, ctx, banks, cfg=cfg)
 
 
-def _seg_forward(den_sd, x, t, ctx, banks, names, sigma, factors):
-    """seg_ref.perturbed_forward under tiled(): a selected block on a tiled level blurs over the whole frame, then tiles."""
-    import pag_ref as P
-    import seg_ref as S
-    sel = P.select(P.block_prefixes(den_sd), names)
-    keys = {p + ".transformer_blocks.0." for p in sel}
-    levels = O._n_levels(den_sd)
-    outer = O.transformer_block_read                                  # tiled()'s read
-
-    def read(sd, p, x_, ctx_, bank, cfg=True):
-        if p not in keys:
-            return outer(sd, p, x_, ctx_, bank, cfg)
-        assert not cfg, "the perturbed evaluation is conditional-only"
-        if T.factor_of(p, factors, levels) > 1:
-            return outer(sd, p, x_, ctx_, bank, cfg, sigma=sigma)
-        Hh, Ww = outer.grid[-1]
-        return S.block_read(sd, p, x_, ctx_, bank, Hh, Ww, sigma)
-
-    O.transformer_block_read = read
-    try:
-        return O.denoising_unet_forward(den_sd, x, t, ctx, banks, cfg=False)
-    finally:
-        O.transformer_block_read = outer
-
-
 def denoise_loop(ref_sd, den_sd, latents, ref_latents, embeds, num_steps, tile_attention=1, tile_attention_shift="cycle", kv_downsample=1,
                  kv_mode="nearest", pag_scale=0.0, pag_layers=("mid",), seg_scale=0.0, seg_blur_sigma=100.0, seg_layers=("mid",),
                  init_latents=None, strength=1.0, free_init_iters=1, **kw):
     """The restated loop of the feature the keywords ask for -- tests/fusion_ref.denoise_loop (reduced=True), tests/pag_ref.denoise_loop
     (pag_scale / seg_scale > 0; a PAG-selected block has no attention to tile, a SEG-selected one blurs then tiles, the unselected blocks
     of the perturbed evaluation tile like the main one), tests/v2v_ref.denoise_loop (init_latents; the step index starts at the first kept
-    step), tests/free_init_ref.denoise_loop (free_init_iters > 1; every pass starts over) -- with shifted-tile self-attention, and with
-    tests/todo_ref.pooled around it for kv_downsample.  Every tile factor 1: that loop op for op."""
+    step), tests/free_init_ref.denoise_loop (free_init_iters > 1; every pass starts over) -- with shifted-tile self-attention and kv_downsample's
+    pooling in one selfattn_ref.modified block around it.  Every tile factor 1: that loop op for op."""
     import pag_ref as P
     factors, kvf = T.check_factors(tile_attention), T.check_factors(kv_downsample)
     first = 0
@@ -193,20 +96,13 @@ def denoise_loop(ref_sd, den_sd, latents, ref_latents, embeds, num_steps, tile_a
     else:
         loop = lambda: FR.denoise_loop(ref_sd, den_sd, latents, ref_latents, embeds, num_steps, reduced=True, **kw)
     orig = P.perturbed_forward
-    if seg_scale > 0:
-        P.perturbed_forward = lambda sd, x, t, ctx, banks, names: _seg_forward(sd, x, t, ctx, banks, names, seg_blur_sigma, factors)
+    if seg_scale > 0:                                                 # a selected block blurs over the whole frame, then tiles
+        import seg_ref as S
+        P.perturbed_forward = lambda sd, x, t, ctx, banks, names: S.perturbed_forward(sd, x, t, ctx, banks, names, seg_blur_sigma)
     try:
-        with contextlib.ExitStack() as stack:
-            if any(v > 1 for v in kvf):
-                stack.enter_context(T.pooled(den_sd, kvf, kv_mode))
-            if all(v == 1 for v in factors):
-                if seg_scale > 0:                                     # no tiled() to note the grid: seg_ref's own restatement
-                    import seg_ref as S
-                    P.perturbed_forward = lambda sd, x, t, ctx, banks, names: S.perturbed_forward(sd, x, t, ctx, banks, names, seg_blur_sigma)
-                return loop()
-            seen = stack.enter_context(tiled(den_sd, factors, tile_attention_shift, first, kv=(kvf, kv_mode)))
+        with SA.modified(den_sd, pool=(kvf, kv_mode), tile=factors, shift=tile_attention_shift, first_step=first) as seen:
             out = loop()
-        assert seen, "no block was tiled"
+        assert all(v == 1 for v in factors) or any("tile" in s[3] for s in seen), "no block was tiled"
         return out
     finally:
         P.perturbed_forward = orig
@@ -323,49 +219,5 @@ def clear():
 
 # ------------------------------------------------------------------ one TransformerBlock in every reference mode (CPU-emulated and GPU tests)
 def block_runs(st, tile_spec, kv_pool=None, sigma=None):
-    """todo_ref.block_runs with the tile field: the block of todo_ref.block_setup in every reference mode with tile_spec = (t, (sy, sx)) or
-    None, kv_pool = (s, mode) or None on the same block -> {case: (got, want)} on the host, fp32: plain, write (with the bank it wrote), read
-    + ref_cfg on the whole batch, and its two clip-halves as SelfAttnCall(half=0 / 1).  sigma: the block blurs its queries (a perturbed
-    evaluation: only the conditional frames, every row reads the bank) -> {"seg": (got, want)}."""
-    from mikudance_amd import blocks
-    blk, f, L, dim, dev, Hh, Ww = st.blk, st.f, st.L, st.dim, st.device, st.Hh, st.Ww
-    h = st.x.reshape(2 * f * L, dim).to(dev)
-    xf, bankf = st.x.float(), st.bank.float()
-    grid = (Hh, Ww)
-    tile_f = None if tile_spec is None else {blk: tile_spec}
-    pool_f = None if kv_pool is None else {blk: kv_pool}
-
-    def ref(x, ctx, bank, cfg, sg=None):
-        if tile_spec is not None:
-            return block_read(st.sd, "", x, ctx, bank, cfg, Hh, Ww, tile_spec[0], tile_spec[1], pool=kv_pool, sigma=sg)
-        if sg is not None:
-            import seg_ref
-            return seg_ref.block_read(st.sd, "", x, ctx, bank, Hh, Ww, sg, kv_pool=kv_pool)
-        if kv_pool is not None:
-            return T.block_read(st.sd, "", x, ctx, bank, cfg, Hh, Ww, *kv_pool)
-        return O.transformer_block_read(st.sd, "", x, ctx, bank, cfg=cfg)
-
-    out = {}
-    with torch.no_grad():
-        if sigma is not None:
-            blk.ref_mode, blk.ref_cfg, blk.bank = "read", True, [st.bank.to(dev)]
-            got = blk(h[f * L:].clone(), f, L, st.cross.rows(f, 2 * f), sa=blocks.SelfAttnCall(blur=((blk,), sigma), pool=pool_f, tile=tile_f), grid=grid)
-            out["seg"] = (got, ref(xf[f:], st.ctx_f[f:], bankf, False, sigma))
-            blk.ref_mode, blk.ref_cfg, blk.bank = None, False, []
-            return {k: (g.float().cpu().reshape(w.shape), w) for k, (g, w) in out.items()}
-        kw = dict(sa=blocks.SelfAttnCall(pool=pool_f, tile=tile_f), grid=grid)
-        want_plain = ref(xf, st.ctx_f, None, False)
-        want_read = ref(xf, st.ctx_f, torch.cat([torch.zeros_like(bankf), bankf]), True)
-        blk.ref_mode, blk.ref_cfg, blk.bank = None, False, []
-        out["plain"] = (blk(h.clone(), 2 * f, L, st.cross, **kw), want_plain)
-        blk.ref_mode = "write"
-        out["write"] = (blk(h.clone(), 2 * f, L, st.cross, **kw), want_plain)
-        out["write-bank"] = (blk.bank[0].reshape(2 * f, L, dim), O.layer_norm(st.sd, "norm1.", xf))
-        blk.ref_mode, blk.ref_cfg, blk.bank = "read", True, [st.bank.to(dev)]
-        out["read-cfg"] = (blk(h.clone(), 2 * f, L, st.cross, **kw), want_read)
-        for c in (0, 1):
-            got = blk(h[c * f * L:(c + 1) * f * L].clone(), f, L, st.cross.rows(c * f, (c + 1) * f),
-                      sa=blocks.SelfAttnCall(half=c, pool=pool_f, tile=tile_f), grid=grid)
-            out[f"read-cfg-chain{c}"] = (got, want_read[c * f:(c + 1) * f])
-        blk.ref_mode, blk.ref_cfg, blk.bank = None, False, []
-    return {k: (g.float().cpu().reshape(w.shape), w) for k, (g, w) in out.items()}
+    """selfattn_ref.block_runs of the block of todo_ref.block_setup with tile_spec = (t, (sy, sx)) or None and kv_pool = (s, mode) or None."""
+    return SA.block_runs(st, (st.Hh, st.Ww), pool=kv_pool, tile=tile_spec, sigma=sigma)

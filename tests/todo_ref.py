@@ -11,10 +11,8 @@ to mikudance_amd.ops, which tests/fake_ops.py installs with its own.
                                                            with every factor 1 it is that loop op for op
     token_pool                                             the operator's emulation (installed by fake_ops.install)
     block_setup(...), block_runs(st, kv_pool)              one product TransformerBlock in every reference mode beside its restatement
-The oracle is not edited: inside `pooled(...)`, and in this process only, its transformer_3d is wrapped to note the grid and its
-transformer_block_read is swapped for block_read on the selected prefixes.
+The oracle is not edited: the pooled block and the patcher that swaps it in on the selected levels are tests/selfattn_ref.py's.
 """
-import contextlib
 import re
 
 import torch
@@ -24,6 +22,7 @@ from oracle import cpu_ref as O
 
 import fake_ops
 import fusion_ref as FR
+import selfattn_ref as SA
 
 
 # ---- the definition
@@ -65,50 +64,12 @@ def factor_of(prefix, factors, levels):
 def block_read(sd, p, x, ctx, bank, cfg, Hh, Ww, s, mode):
     """oracle transformer_block_read with the self-attention K / V source pooled: q from every token of norm1(x), k / v from
     pool(norm1(x) + bank) -- pooled AFTER the add -- and, under cfg, from pool(norm1(x)) on the unconditional first half."""
-    B = x.shape[0]
-    n = O.layer_norm(sd, p + "norm1.", x)
-    kv = n + bank if bank is not None else n
-    h = O.attention(sd, p + "attn1.", n, pool(kv, B, Hh, Ww, s, mode)) + x
-    if cfg:
-        half = B // 2
-        h = h.clone()
-        h[:half] = O.attention(sd, p + "attn1.", n[:half], pool(n[:half], half, Hh, Ww, s, mode)) + x[:half]
-    x = h
-    x = O.attention(sd, p + "attn2.", O.layer_norm(sd, p + "norm2.", x), ctx) + x
-    x = O.feed_forward(sd, p + "ff.", O.layer_norm(sd, p + "norm3.", x)) + x
-    return x
+    return SA.block_read(sd, p, x, ctx, bank, cfg, (Hh, Ww), pool=(s, mode))
 
 
-@contextlib.contextmanager
 def pooled(den_sd, factors, mode="nearest"):
-    """Within the block, the oracle's read blocks on a level with a factor > 1 take K / V from the pooled source.  Yields the list of
-    (prefix, Hh, Ww, s) of every block evaluated that way."""
-    factors = check_factors(factors)
-    levels = O._n_levels(den_sd)
-    assert len(factors) <= levels, (factors, levels)
-    orig_t3d, orig_read = O.transformer_3d, O.transformer_block_read
-    grid, seen = [], []
-
-    def transformer_3d(sd, p, x, ctx_per_frame, bank, cfg):
-        grid.append(tuple(x.shape[2:]))
-        try:
-            return orig_t3d(sd, p, x, ctx_per_frame, bank, cfg)
-        finally:
-            grid.pop()
-
-    def read(sd, p, x, ctx, bank, cfg=True):
-        s = factor_of(p, factors, levels)                          # (read blocks exist in the denoising UNet only)
-        if s == 1:
-            return orig_read(sd, p, x, ctx, bank, cfg)
-        Hh, Ww = grid[-1]
-        seen.append((p, Hh, Ww, s))
-        return block_read(sd, p, x, ctx, bank, cfg, Hh, Ww, s, mode)
-
-    O.transformer_3d, O.transformer_block_read = transformer_3d, read
-    try:
-        yield seen
-    finally:
-        O.transformer_3d, O.transformer_block_read = orig_t3d, orig_read
+    """Within the block, the oracle's read blocks on a level with a factor > 1 take K / V from the pooled source (selfattn_ref.modified)."""
+    return SA.modified(den_sd, pool=(factors, mode))
 
 
 def unet_forward(den_sd, x, t, ctx, banks, factors, mode="nearest", cfg=True):
@@ -191,31 +152,5 @@ def block_setup(dim, dctx, Hh, Ww, f, device, seed=21):
 
 
 def block_runs(st, kv_pool):
-    """The block of block_setup in every reference mode with `kv_pool` ((Hh, Ww, s, mode) or None) -> {case: (got, want)} on the host, fp32:
-    plain, write (with the bank it wrote), read + ref_cfg on the whole batch, and its two clip-halves as SelfAttnCall(half=0 / 1)."""
-    from mikudance_amd import blocks
-    blk, f, L, dim, dev = st.blk, st.f, st.L, st.dim, st.device
-    h = st.x.reshape(2 * f * L, dim).to(dev)
-    xf, bankf = st.x.float(), st.bank.float()
-    if kv_pool is None:
-        ref = lambda bank, cfg: O.transformer_block_read(st.sd, "", xf, st.ctx_f, bank, cfg=cfg)
-    else:
-        ref = lambda bank, cfg: block_read(st.sd, "", xf, st.ctx_f, bank, cfg, *kv_pool)
-    pool, grid = (None, None) if kv_pool is None else ({blk: tuple(kv_pool[2:])}, tuple(kv_pool[:2]))
-    kw = dict(sa=blocks.SelfAttnCall(pool=pool), grid=grid)
-    out = {}
-    with torch.no_grad():
-        want_plain = ref(None, False)
-        want_read = ref(torch.cat([torch.zeros_like(bankf), bankf]), True)
-        blk.ref_mode, blk.ref_cfg, blk.bank = None, False, []
-        out["plain"] = (blk(h.clone(), 2 * f, L, st.cross, **kw), want_plain)
-        blk.ref_mode = "write"
-        out["write"] = (blk(h.clone(), 2 * f, L, st.cross, **kw), want_plain)
-        out["write-bank"] = (blk.bank[0].reshape(2 * f, L, dim), O.layer_norm(st.sd, "norm1.", xf))
-        blk.ref_mode, blk.ref_cfg, blk.bank = "read", True, [st.bank.to(dev)]
-        out["read-cfg"] = (blk(h.clone(), 2 * f, L, st.cross, **kw), want_read)
-        for c in (0, 1):
-            got = blk(h[c * f * L:(c + 1) * f * L].clone(), f, L, st.cross.rows(c * f, (c + 1) * f), sa=blocks.SelfAttnCall(half=c, pool=pool), grid=grid)
-            out[f"read-cfg-chain{c}"] = (got, want_read[c * f:(c + 1) * f])
-        blk.ref_mode, blk.ref_cfg, blk.bank = None, False, []
-    return {k: (g.float().cpu().reshape(w.shape), w) for k, (g, w) in out.items()}
+    """selfattn_ref.block_runs of the block of block_setup with `kv_pool` ((Hh, Ww, s, mode) or None)."""
+    return SA.block_runs(st) if kv_pool is None else SA.block_runs(st, tuple(kv_pool[:2]), pool=tuple(kv_pool[2:]))
