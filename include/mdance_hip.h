@@ -75,7 +75,9 @@ int md_conv_nhwc_f16(const void* X, int ldx, const void* W, void* Y, int ldy, in
 
 /* In-place softmax(scale * x) over the rows of a row-major fp16 matrix [rows][ldx] (cols valid, cols % 8 == 0).
  * The score matrix of the single 512-channel head of the AutoencoderKL mid-block attention (QK^T and PV run on
- * md_gemm_f16): src/pipelines/pipeline_mikudance.py:115-130 (decode_latents), :456-549 (vae.encode). */
+ * md_gemm_f16): src/pipelines/pipeline_mikudance.py:115-130 (decode_latents), :456-549 (vae.encode).
+ * scale must be positive and finite (the kernel scales the row maximum of x, which is the maximum of scale * x only for scale > 0):
+ * MD_ERR_ARG otherwise, with nothing launched. */
 int md_softmax_rows_f16(void* x, int ldx, int rows, int cols, float scale, void* stream);
 
 /* GroupNorm(G, eps) [+SiLU] over (B, HW, C) NHWC.  src/models/resnet.py:20-28,220-221,231,237;
@@ -97,6 +99,22 @@ int md_groupnorm_ld_nhwc_f16(const void* x, int ldx, void* y, const void* gamma,
  * query input only, src/models/motion_module.py:404-417).  src/models/attention.py:105-107,331-365. */
 int md_layernorm_f16(const void* x, void* y, void* y2, const void* gamma, const void* beta, const void* add, int M,
                      int C, float eps, int add_mode, int add_row_begin, int rows_per_frame, int frames, void* stream);
+
+/* Which kernels md_groupnorm_ld_nhwc_f16 (table = 0) / md_groupnorm_table_f16 (table = 1) run, and their launch geometry; no device
+ * access, nothing launched; the launchers run the same function.  x_align16: whether x is 16-byte aligned.  Returns
+ *   600  two launches: the statistics sweep, then the apply sweep (or the table kernel);
+ *   601  three launches: more than 128 slabs per image, one small launch reduces the partial sums in between;
+ *   61k / 62k  the one-sweep kernel that keeps an (image, group) in the registers of 256 / 512 threads, k = 1, 2, 4 for its 6 / 12 / 24
+ *        sweeps-per-thread instances (611 612 614 622 624; never with table = 1): (C / G) % 4 == 0, C / G <= 256, B * G >= 256, HW <= 1024;
+ * or MD_ERR_ARG for what the entries refuse from these arguments (C % 8, G outside 1..64, C % G, ldx < C, ldx % 8, x not 16-byte
+ * aligned, C > 8192).  *threads: threads per workgroup; *R: pixel lanes per workgroup; *slab: pixels per workgroup; *nslab: workgroups
+ * per image (600 / 601) -- HW and 1 for the one-sweep kernel, whose workgroup owns a whole (image, group).  Any of them may be NULL; all
+ * stay untouched on error.  md_groupnorm_workspace_bytes is (B * nslab * G * 2 + B * G * 3) floats of the table = 1 plan. */
+int md_groupnorm_plan(int B, int HW, int C, int G, int ldx, int x_align16, int table, int* threads, int* R, int* slab, int* nslab);
+
+/* Which kernel md_layernorm_f16 runs: 700 + MAXC for the kernel instance that holds rows of up to 512 * MAXC channels (701 .. 704), 720
+ * the C = 320 kernel, or MD_ERR_ARG as the entry (C % 8, C > 2048).  No device access; the launcher runs the same function. */
+int md_layernorm_plan(int M, int C);
 
 /* LayerNorm FOLDED into the Linear that consumes it: C = LayerNorm(A; gamma, beta, eps) . W^T + bias [+ rowadd] computed from the RAW rows
  * of A, the normalised tensor never touching HBM.  The caller folds once per layer (mikudance_amd/packing.py ln_fold):

@@ -34,6 +34,8 @@ SIGNATURES = {
     "md_groupnorm_ld_nhwc_f16": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, c_size_t, P]),
     "md_instnorm_spade_ld_f16": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_float, P]),
     "md_layernorm_f16": (c_int, [P, P, P, P, P, P, c_int, c_int, c_float, c_int, c_int, c_int, c_int, P]),
+    "md_groupnorm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int] + [ctypes.POINTER(c_int)] * 4),
+    "md_layernorm_plan": (c_int, [c_int, c_int]),
     "md_gemm_ln_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "md_gemm_ln_f16": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_float, P, c_int, c_int, c_int, P]),
     "md_groupnorm_table_f16": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_float, P, P, c_size_t, P]),

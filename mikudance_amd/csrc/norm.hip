@@ -20,12 +20,19 @@ __device__ __forceinline__ void norm_store(T* p, const T& v) { *p = v; }
 #endif
 
 // ------------------------------------------------------------------------------------------------ GroupNorm
-// Statistics are the one-sweep sums of (x - k) and (x - k)^2 in fp32, k = the value of the group's FIRST channel at PIXEL 0 of
-// the image: a pilot of the group mean (a sample of the very distribution being normalised), so the sums stay O(n * sigma) and
-// var = E[(x-k)^2] - E[x-k]^2 does not cancel when |mean| >> sigma (the plain E[x^2] - mean^2 loses the variance at
-// |mean| / sigma ~ 100 in fp32).  The statistics sweep reads k from x (two 2-byte loads per thread, 8 when a thread's 8 channels can
+// Statistics are the one-sweep sums of (x - k) and (x - k)^2 in fp32 around a pilot k of the group mean (a sample of the very distribution
+// being normalised), so the sums stay O(n * sigma) and var = E[(x-k)^2] - E[x-k]^2 does not cancel when |mean| >> sigma (the plain
+// E[x^2] - mean^2 loses the variance at |mean| / sigma ~ 100 in fp32).  k = the MEDIAN of three samples of the group -- its first channel at
+// pixel 0, its middle channel at pixel HW / 2, its last channel at pixel HW - 1 -- so that no single value decides it: with k = one sample,
+// a hot pixel (or a hot channel) at that very position, r sigma out, puts the cancellation back at r ~ 100 (rstd off by 2.4e-3 at r = 300,
+// tests/test_norm_scheme_cpu.py).  The statistics sweep reads k from x (six 2-byte loads per thread, 24 when a thread's 8 channels can
 // span more than two groups) and its slab-0 workgroups hand it to the apply sweep through the workspace (bit-identical on both sides,
 // and safe when the apply sweep runs in place).
+__device__ __forceinline__ float med3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
+__device__ __forceinline__ float gn_pilot(const half_t* __restrict__ ximg, int HW, int ldx, int g, int cpg) {
+  const half_t* p = ximg + g * cpg;
+  return med3((float)p[0], (float)p[(size_t)(HW >> 1) * ldx + (cpg >> 1)], (float)p[(size_t)(HW - 1) * ldx + cpg - 1]);
+}
 // Thread (cc, r): channel chunk cc (8 channels), row lane r.  A block owns `slab` consecutive pixels of one image.
 __global__ void gn_stats_kernel(const half_t* __restrict__ x, float* __restrict__ part, float* __restrict__ pilot, int HW, int C, int ldx, int G, int R,
                                 int slab, int nslab) {
@@ -39,12 +46,12 @@ __global__ void gn_stats_kernel(const half_t* __restrict__ x, float* __restrict_
   float s[8], q[8], k[8];
   if (cpg >= 8) {                // the 8 channels of a thread lie in at most two groups
     const int g0 = (cc * 8) / cpg, g1 = (cc * 8 + 7) / cpg;
-    const float k0 = (float)ximg[g0 * cpg], k1 = (float)ximg[g1 * cpg];
+    const float k0 = gn_pilot(ximg, HW, ldx, g0, cpg), k1 = gn_pilot(ximg, HW, ldx, g1, cpg);
 #pragma unroll
     for (int e = 0; e < 8; ++e) k[e] = (cc * 8 + e) / cpg == g0 ? k0 : k1;
   } else {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) k[e] = (float)ximg[((cc * 8 + e) / cpg) * cpg];
+    for (int e = 0; e < 8; ++e) k[e] = gn_pilot(ximg, HW, ldx, (cc * 8 + e) / cpg, cpg);
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
@@ -100,7 +107,7 @@ __global__ void gn_stats_kernel(const half_t* __restrict__ x, float* __restrict_
     o[1] = c2;
     // the pilot travels through the workspace: the apply sweep may run IN PLACE (y == x) and overwrite pixel 0 before the other
     // workgroups of the image have read it
-    if (sl == 0) pilot[(size_t)b * G + g] = (float)ximg[g * cpg];
+    if (sl == 0) pilot[(size_t)b * G + g] = gn_pilot(ximg, HW, ldx, g, cpg);
   }
 }
 
@@ -322,35 +329,68 @@ extern "C" size_t md_groupnorm_workspace_bytes(int B, int HW, int C, int G) {
   return ((size_t)B * nslab * G * 2 + (size_t)B * G * 3) * sizeof(float);   // partial sums + one pilot + (mean, rstd) per (image, group)
 }
 
+// Plan codes (md_groupnorm_plan exposes them so that the dispatch is testable without a GPU): 600 gn_stats_kernel + gn_apply_kernel (or
+// gn_table_kernel), 601 the same with gn_finalize_kernel in between, 610 + N / 6 and 620 + N / 6 gn_small_kernel<N, 256> / <N, 512>.
+struct GnPlan {
+  int code, threads, R, slab, nslab;
+};
+
+// THE dispatch rule of md_groupnorm_ld_nhwc_f16 and md_groupnorm_table_f16 (`table`: never the one-sweep kernel): the launchers and
+// md_groupnorm_plan all call it; no device access.  `who` prefixes the error text.  For the one-sweep kernel R is its pixel lanes, one
+// workgroup owns a whole (image, group): slab = HW, nslab = 1.
+static int gn_plan(const char* who, int B, int HW, int C, int G, int ldx, bool x16, bool table, GnPlan* pl) {
+  MD_CHECK_ARG(C % 8 == 0 && G > 0 && G <= 64 && C % G == 0, "%s: need C %% 8 == 0, G <= 64, C %% G == 0 (C=%d G=%d)", who, C, G);
+  MD_CHECK_ARG(ldx >= C && ldx % 8 == 0 && x16, "%s: ldx=%d must be a multiple of 8 and >= C=%d, x 16-byte aligned", who, ldx, C);
+  MD_CHECK_ARG(C / 8 <= 1024, "%s: C=%d too large", who, C);
+  int Rs, NTs;
+  const int it = table ? 0 : gn_small_iters(B, HW, C, G, &Rs, &NTs);
+  if (it) {
+    const int N = it <= 6 && NTs == 256 ? 6 : it <= 12 ? 12 : 24;
+    pl->code = (NTs == 512 ? 620 : 610) + N / 6;
+    pl->threads = NTs; pl->R = Rs; pl->slab = HW; pl->nslab = 1;
+    return MD_OK;
+  }
+  gn_geometry(B, HW, C, pl->R, pl->slab, pl->nslab);
+  pl->threads = C / 8 * pl->R;
+  pl->code = pl->nslab > GN_FIN_SLABS ? 601 : 600;
+  return MD_OK;
+}
+
+extern "C" int md_groupnorm_plan(int B, int HW, int C, int G, int ldx, int x_align16, int table, int* threads, int* R, int* slab, int* nslab) {
+  GnPlan pl;
+  if (const int rc = gn_plan(table ? "md_groupnorm_table" : "md_groupnorm", B, HW, C, G, ldx, x_align16 != 0, table != 0, &pl)) return rc;
+  if (threads) *threads = pl.threads;
+  if (R) *R = pl.R;
+  if (slab) *slab = pl.slab;
+  if (nslab) *nslab = pl.nslab;
+  return pl.code;
+}
+
 extern "C" int md_groupnorm_ld_nhwc_f16(const void* x, int ldx, void* y, const void* gamma, const void* beta, int B, int HW, int C, int G, float eps,
                                         int silu, void* workspace, size_t ws_bytes, void* stream) {
-  MD_CHECK_ARG(C % 8 == 0 && G > 0 && G <= 64 && C % G == 0, "md_groupnorm: need C %% 8 == 0, G <= 64, C %% G == 0 (C=%d G=%d)", C, G);
-  MD_CHECK_ARG(ldx >= C && ldx % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (ldx == C || x != y),
-               "md_groupnorm: ldx=%d must be a multiple of 8 and >= C=%d, x 16-byte aligned; in place only with ldx == C", ldx, C);
-  MD_CHECK_ARG(C / 8 <= 1024, "md_groupnorm: C=%d too large", C);
+  GnPlan pl;
+  if (const int rc = gn_plan("md_groupnorm", B, HW, C, G, ldx, (reinterpret_cast<uintptr_t>(x) & 15) == 0, false, &pl)) return rc;
+  MD_CHECK_ARG(ldx == C || x != y, "md_groupnorm: in place only with ldx == C (ldx=%d C=%d)", ldx, C);
   MD_CHECK_ARG(((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15) == 0, "md_groupnorm: gamma / beta must be 16-byte aligned");
   MD_CHECK_ARG(ws_bytes >= md_groupnorm_workspace_bytes(B, HW, C, G), "md_groupnorm: workspace too small");
-  {
-    int Rs, NTs;
-    const int it = (ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0) ? gn_small_iters(B, HW, C, G, &Rs, &NTs) : 0;
-    if (it) {
+  if (pl.code >= 610) {
+    const int Rs = pl.R;
 #define GN_SMALL(N, T)                                                                                                                       \
   hipLaunchKernelGGL((gn_small_kernel<N, T>), dim3(B * G), dim3(T), 0, (hipStream_t)stream, (const half_t*)x, (half_t*)y, (const half_t*)gamma, \
                      (const half_t*)beta, HW, C, ldx, C / G, Rs, eps, silu, B)
-      if (NTs == 512) {
-        if (it <= 12) GN_SMALL(12, 512);
-        else GN_SMALL(24, 512);
-      } else if (it <= 6) GN_SMALL(6, 256);
-      else if (it <= 12) GN_SMALL(12, 256);
-      else GN_SMALL(24, 256);
-#undef GN_SMALL
-      MD_CHECK_LAUNCH("md_groupnorm");
-      return MD_OK;
+    switch (pl.code) {
+      case 611: GN_SMALL(6, 256); break;
+      case 612: GN_SMALL(12, 256); break;
+      case 614: GN_SMALL(24, 256); break;
+      case 622: GN_SMALL(12, 512); break;
+      default: GN_SMALL(24, 512); break;     // 624
     }
+#undef GN_SMALL
+    MD_CHECK_LAUNCH("md_groupnorm");
+    return MD_OK;
   }
   const int cch = C / 8;
-  int R, slab, nslab;
-  gn_geometry(B, HW, C, R, slab, nslab);
+  const int R = pl.R, slab = pl.slab, nslab = pl.nslab;
   // The apply sweep re-reads what the statistics sweep has just read, in reverse order (most recently read slabs first): +3 % at
   // C = 640, +-0 elsewhere.  Splitting the batch into chunks so that the re-read would be served from the 256-MB memory-side cache
   // was measured and is a loss at every chunk size (24 MB: 2.7x slower, 96 MB: -12 %): launch gaps and tails, no visible hit-rate gain.
@@ -399,13 +439,12 @@ __global__ void gn_table_kernel(const float* __restrict__ part, const float* __r
 
 extern "C" int md_groupnorm_table_f16(const void* x, int ldx, const void* gamma, const void* beta, int B, int HW, int C, int G, float eps, float* table,
                                       void* workspace, size_t ws_bytes, void* stream) {
-  MD_CHECK_ARG(C % 8 == 0 && G > 0 && G <= 64 && C % G == 0, "md_groupnorm_table: need C %% 8 == 0, G <= 64, C %% G == 0 (C=%d G=%d)", C, G);
-  MD_CHECK_ARG(ldx >= C && ldx % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "md_groupnorm_table: ldx=%d must be a multiple of 8 and >= C=%d, x 16-byte aligned", ldx, C);
-  MD_CHECK_ARG(C / 8 <= 1024 && (reinterpret_cast<uintptr_t>(table) & 15) == 0, "md_groupnorm_table: C=%d too large or table not 16-byte aligned", C);
+  GnPlan pl;
+  if (const int rc = gn_plan("md_groupnorm_table", B, HW, C, G, ldx, (reinterpret_cast<uintptr_t>(x) & 15) == 0, true, &pl)) return rc;
+  MD_CHECK_ARG((reinterpret_cast<uintptr_t>(table) & 15) == 0, "md_groupnorm_table: table not 16-byte aligned");
   MD_CHECK_ARG(ws_bytes >= md_groupnorm_workspace_bytes(B, HW, C, G), "md_groupnorm_table: workspace too small");
   const int cch = C / 8;
-  int R, slab, nslab;
-  gn_geometry(B, HW, C, R, slab, nslab);
+  const int R = pl.R, slab = pl.slab, nslab = pl.nslab;
   const dim3 grid(nslab, B), block(cch * R);
   const size_t sh = (size_t)2 * R * C * sizeof(float);
   float* pilot = (float*)workspace + (size_t)B * nslab * G * 2;
@@ -623,27 +662,38 @@ __global__ __launch_bounds__(256) void layernorm320_kernel(const half_t* __restr
   }
 }
 
+// THE dispatch rule of md_layernorm_f16 (md_layernorm_plan exposes it): 700 + MAXC layernorm_kernel<MAXC>, 720 layernorm320_kernel.
+static int ln_plan(int M, int C) {
+  (void)M;                                               // the choice does not depend on the number of rows
+  MD_CHECK_ARG(C % 8 == 0 && C <= 8 * 64 * LN_MAXC, "md_layernorm: C=%d must be a multiple of 8 and <= %d", C, 8 * 64 * LN_MAXC);
+#ifndef LN_NO_320
+  if (C == 320) return 720;
+#endif
+  return 700 + (C <= 512 ? 1 : C <= 1024 ? 2 : C <= 1536 ? 3 : 4);
+}
+
+extern "C" int md_layernorm_plan(int M, int C) { return ln_plan(M, C); }
+
 extern "C" int md_layernorm_f16(const void* x, void* y, void* y2, const void* gamma, const void* beta, const void* add, int M, int C, float eps,
                                 int add_mode, int add_row_begin, int rows_per_frame, int frames, void* stream) {
-  MD_CHECK_ARG(C % 8 == 0 && C <= 8 * 64 * LN_MAXC, "md_layernorm: C=%d must be a multiple of 8 and <= %d", C, 8 * 64 * LN_MAXC);
+  const int code = ln_plan(M, C);
+  if (code < 0) return code;
   MD_CHECK_ARG(add_mode == 0 || (add != nullptr && y2 != nullptr), "md_layernorm: add_mode needs add and y2");
   MD_CHECK_ARG(add_mode != 2 || (rows_per_frame > 0 && frames > 0), "md_layernorm: add_mode 2 needs rows_per_frame and frames");
   const dim3 grid(cdiv(M, 4 * LN_R)), block(256);
   hipStream_t st = (hipStream_t)stream;
-#ifndef LN_NO_320
-  if (C == 320) {
+  if (code == 720) {
     hipLaunchKernelGGL(layernorm320_kernel, dim3(cdiv(M, 32)), block, 0, st, (const half_t*)x, (half_t*)y, (half_t*)y2, (const half_t*)gamma,
                        (const half_t*)beta, (const half_t*)add, M, eps, add_mode, add_row_begin, rows_per_frame, frames);
     MD_CHECK_LAUNCH("md_layernorm");
     return MD_OK;
   }
-#endif
-#define LN_LAUNCH(MC)                                                                                                                           \
+#define LN_LAUNCH(MC)                                                                                                                          \
   hipLaunchKernelGGL(layernorm_kernel<MC>, grid, block, 0, st, (const half_t*)x, (half_t*)y, (half_t*)y2, (const half_t*)gamma, (const half_t*)beta, \
                      (const half_t*)add, M, C, eps, add_mode, add_row_begin, rows_per_frame, frames)
-  if (C <= 512) LN_LAUNCH(1);
-  else if (C <= 1024) LN_LAUNCH(2);
-  else if (C <= 1536) LN_LAUNCH(3);
+  if (code == 701) LN_LAUNCH(1);
+  else if (code == 702) LN_LAUNCH(2);
+  else if (code == 703) LN_LAUNCH(3);
   else LN_LAUNCH(4);
 #undef LN_LAUNCH
   MD_CHECK_LAUNCH("md_layernorm");
@@ -658,8 +708,13 @@ __global__ __launch_bounds__(256) void instnorm_spade_kernel(const half_t* __res
   const int cc = threadIdx.x & 7, r = threadIdx.x >> 3;
   const int b = blockIdx.y, c0 = blockIdx.x * 64 + cc * 8;
   const half_t* xb = x + (size_t)b * HW * ldx + c0;
-  // sums of (x - k), (x - k)^2 with k = the channel's value at pixel 0 (a pilot of its mean: no cancellation when |mean| >> sigma)
-  const half8_t k8 = *reinterpret_cast<const half8_t*>(xb);
+  // sums of (x - k), (x - k)^2 with k = the median of the channel's values at pixels 0, HW / 2 and HW - 1 (a pilot of its mean: no
+  // cancellation when |mean| >> sigma, and no single pixel decides it -- see GroupNorm)
+  const half8_t ka = *reinterpret_cast<const half8_t*>(xb), kb = *reinterpret_cast<const half8_t*>(xb + (size_t)(HW >> 1) * ldx),
+                kc = *reinterpret_cast<const half8_t*>(xb + (size_t)(HW - 1) * ldx);
+  float k8[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) k8[e] = med3((float)ka[e], (float)kb[e], (float)kc[e]);
   float s[8], q[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
@@ -667,7 +722,7 @@ __global__ __launch_bounds__(256) void instnorm_spade_kernel(const half_t* __res
     const half8_t v = *reinterpret_cast<const half8_t*>(xb + (size_t)p * ldx);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float f = (float)v[e] - (float)k8[e];
+      const float f = (float)v[e] - k8[e];
       s[e] += f;
       q[e] += f * f;
     }
@@ -685,7 +740,8 @@ __global__ __launch_bounds__(256) void instnorm_spade_kernel(const half_t* __res
       c2 += sq[rr][threadIdx.x];
     }
     const float mu = a / (float)HW;                     // mean of x - k
-    mean_s[threadIdx.x] = (float)x[(size_t)b * HW * ldx + blockIdx.x * 64 + threadIdx.x] + mu;
+    const half_t* xc = x + (size_t)b * HW * ldx + blockIdx.x * 64 + threadIdx.x;
+    mean_s[threadIdx.x] = med3((float)xc[0], (float)xc[(size_t)(HW >> 1) * ldx], (float)xc[(size_t)(HW - 1) * ldx]) + mu;   // the same k
     rstd_s[threadIdx.x] = rsqrtf(fmaxf(c2 / (float)HW - mu * mu, 0.f) + eps);
   }
   __syncthreads();
@@ -759,6 +815,8 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(half_t* x, long ldx, 
 }
 
 extern "C" int md_softmax_rows_f16(void* x, int ldx, int rows, int cols, float scale, void* stream) {
+  // the kernel takes the row maximum of x and multiplies it by scale: with scale < 0 that is the row MINIMUM of scale * x and exp2 overflows
+  MD_CHECK_ARG(scale > 0.f && scale <= 3.0e38f, "md_softmax_rows: scale=%g must be positive and finite", (double)scale);
   MD_CHECK_ARG(rows > 0 && cols > 0 && cols % 8 == 0 && ldx % 8 == 0 && ldx >= cols, "md_softmax_rows: rows=%d cols=%d ldx=%d (cols, ldx multiples of 8)", rows, cols, ldx);
   MD_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0, "md_softmax_rows: x must be 16-byte aligned");
   hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (half_t*)x, (long)ldx, cols, scale * 1.4426950408889634f);

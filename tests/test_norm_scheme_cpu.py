@@ -1,6 +1,6 @@
 """CPU emulation (fp32, same association as the kernels') of the statistics scheme of md_groupnorm_nhwc_f16 /
-md_instnorm_spade_f16 (mikudance_amd/csrc/norm.hip): one sweep of sum(x - k), sum((x - k)^2) around a pilot k -- the group's first
-channel at pixel 0 (GroupNorm) or the channel's own pixel-0 value (InstanceNorm) -- then mean = k + E[x - k],
+md_instnorm_spade_f16 (mikudance_amd/csrc/norm.hip): one sweep of sum(x - k), sum((x - k)^2) around a pilot k -- a sample of the group
+(the median of three: the last two tests; the first three run the scheme around one sample, which is the same arithmetic) -- then mean = k + E[x - k],
 var = E[(x - k)^2] - E[x - k]^2.  Checked against fp64 statistics where the plain E[x^2] - mean^2 form loses the variance."""
 import pytest
 import torch
@@ -49,3 +49,42 @@ def test_instancenorm_pilot_shift():
     mu, var = _stats_shifted(xc, k)
     ref_mu, ref_var = xc.double().mean(-1), xc.double().var(-1, unbiased=False)
     assert ((var.double() - ref_var).abs() / ref_var).max().item() < 1e-4 and (mu.double() - ref_mu).abs().max().item() < 1e-3
+
+
+def _median3(a, b, c):
+    return torch.maximum(torch.minimum(a, b), torch.minimum(torch.maximum(a, b), c))
+
+
+@pytest.mark.parametrize("r", [30.0, 300.0, 1000.0])
+def test_pilot_that_is_itself_an_outlier(r):
+    """One hot value exactly where a single-sample pilot looks (pixel 0, the group's first channel), r sigma out: around THAT k the sums are
+    O(n r sigma), E[(x-k)^2] ~ r^2 and its fp32 ulp eats the variance (rstd off by 1e-3 and more from r = 300).  The pilot the kernels use --
+    the median of (first channel, pixel 0), (middle channel, pixel HW / 2), (last channel, pixel HW - 1) -- does not see one value."""
+    B, HW, G, cpg = 2, 1104, 4, 80
+    gen = torch.Generator().manual_seed(7)
+    x = torch.randn(B, HW, G, cpg, generator=gen)
+    x[:, 0, :, 0] = r
+    x = x.half()
+    xg = x.permute(0, 2, 1, 3).reshape(B, G, HW * cpg)
+    ref_var = xg.double().var(-1, unbiased=False)
+    rstd_err = lambda var: ((var.double() + 1e-5).rsqrt() / (ref_var + 1e-5).rsqrt() - 1).abs().max().item()  # noqa: E731
+    single = x[:, 0, :, 0].float().unsqueeze(-1)
+    median = _median3(x[:, 0, :, 0].float(), x[:, HW // 2, :, cpg // 2].float(), x[:, HW - 1, :, cpg - 1].float()).unsqueeze(-1)
+    assert rstd_err(_stats_shifted(xg, median)[1]) < 2e-5
+    if r >= 300:
+        assert rstd_err(_stats_shifted(xg, single)[1]) > 5e-4
+
+
+def test_instancenorm_pilot_outlier():
+    B, HW, C = 1, 36864, 8
+    gen = torch.Generator().manual_seed(8)
+    x = torch.randn(B, HW, C, generator=gen)
+    x[:, 0, :] = 300.0
+    x = x.half()
+    xc = x.permute(0, 2, 1)
+    ref_var = xc.double().var(-1, unbiased=False)
+    median = _median3(x[:, 0].float(), x[:, HW // 2].float(), x[:, HW - 1].float()).unsqueeze(-1)
+    _, var = _stats_shifted(xc, median)
+    assert ((var.double() - ref_var).abs() / ref_var).max().item() < 1e-4
+    _, var1 = _stats_shifted(xc, x[:, 0].float().unsqueeze(-1))
+    assert ((var1.double() - ref_var).abs() / ref_var).max().item() > 1e-3
