@@ -15,7 +15,7 @@ from .pipeline_mikudance import MikuDanceVideoPipeline, MikuDanceVideoPipelineOu
 from .pipeline_stage2_vdo import Pose2VideoPipeline  # noqa: F401
 from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler  # noqa: F401
 from .unet_2d_mix import UNet2DConditionModel, UNet2DConditionModelPlain  # noqa: F401
-from .unet_3d_mix import UNet3DConditionModel  # noqa: F401
+from .unet_3d_mix import DeepCacheSlot, UNet3DConditionModel  # noqa: F401
 from .vae import AutoencoderKL  # noqa: F401
 from .vae_temporal import AutoencoderKLTemporalDecoder  # noqa: F401
 

@@ -28,6 +28,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      (an addition: smoothed-energy guidance, arXiv 2408.00760; default 0.0 = off)
     pipe(..., tile_attention=--tile_attention, tile_attention_shift=--tile_attention_shift)
                      (an addition: shifted-tile spatial self-attention, arXiv 2311.17528; default 1 = off)
+    pipe(..., deep_cache_interval=--deep_cache_interval, deep_cache_depth=--deep_cache_depth)
+                     (an addition: DeepCache, arXiv 2312.00858: the deep part of the denoising UNet every N-th step only; default 1 = off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -153,6 +155,13 @@ def parse_args(argv=None):
                         help="(addition) SEG: sigma of the query blur in tokens, > 0; inf = every query becomes its frame's mean query")
     parser.add_argument("--seg_layers", default="mid",
                         help="(addition) SEG: comma-separated attention blocks of the denoising UNet, as --pag_layers")
+    parser.add_argument("--deep_cache_interval", type=int, default=1, metavar="N",
+                        help="(addition) DeepCache (arXiv 2312.00858), an approximation that saves the deep levels of the denoising UNet: only "
+                             "every N-th step evaluates the whole UNet, the steps between run its outermost layers on the deep hidden state "
+                             "of the last full step; 1 = off")
+    parser.add_argument("--deep_cache_depth", type=int, default=3, metavar="D",
+                        help="(addition) DeepCache: how many skip connections, counted from conv_in, the steps between still evaluate "
+                             "(this project's own index); 3 = the whole highest-resolution level on both sides")
     args = parser.parse_args(argv)
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
@@ -253,7 +262,8 @@ def main(argv=None):
                pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale, pag_applied_layers=_layer_names(args.pag_layers),
                kv_downsample=args.kv_downsample, kv_downsample_mode=args.kv_downsample_mode,
                seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma, seg_applied_layers=_layer_names(args.seg_layers),
-               tile_attention=args.tile_attention, tile_attention_shift=args.tile_attention_shift)
+               tile_attention=args.tile_attention, tile_attention_shift=args.tile_attention_shift,
+               deep_cache_interval=args.deep_cache_interval, deep_cache_depth=args.deep_cache_depth)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

@@ -84,6 +84,7 @@ class SamplingPlan:
     kv: Union[None, tuple, dict]   # None: no K / V downsampling; (factors, mode), resolved: UNet3DConditionModel.kv_downsample_plan
     guide: Union[None, Rescale, APG, Perturb]      # None: plain (u + g (c - u), or c without CFG)
     tile: Union[None, tuple] = None                # None: no tiled self-attention; (factors, shift), resolved: (UNet3DConditionModel.tile_attention_plan, shift)
+    deep: Union[None, tuple] = None                # None: deep_cache_interval == 1, no DeepCache; (interval N, depth d), d checked against the UNet by _resolve_plan
 
 
 # the step forms v in ONE way: (asked for, beside, why not), in the order the refusals are made
@@ -165,7 +166,7 @@ class MikuDanceVideoPipeline:
                 free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25, free_init_temporal_stop=0.25,
                 free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
                 pag_applied_layers=("mid",), kv_downsample=1, kv_downsample_mode="nearest", seg_scale=0.0, seg_blur_sigma=100.0,
-                seg_applied_layers=("mid",), tile_attention=1, tile_attention_shift="cycle"):
+                seg_applied_layers=("mid",), tile_attention=1, tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -306,6 +307,34 @@ class MikuDanceVideoPipeline:
                             (q th // 4, q tw // 4), so no tile border stays put; "none": no shift.  The paper's code draws the shift at random
                             per call; here it is a pure function of the step, so that runs are reproducible and the ranks of window_parallel
                             agree without talking
+        deep_cache_interval DeepCache (Ma, Fang, Wang, arXiv 2312.00858: the idea only), an opt-in APPROXIMATION that trades accuracy for time: an integer
+                            N >= 1.  Executed step k of a pass (k counts from 0 at the first step the loop actually runs: the first KEPT step under
+                            strength < 1; every FreeInit pass starts at k = 0 with an empty cache) is a KEY step iff k % N == 0: the denoising UNet
+                            is evaluated in full and keeps the hidden state that meets skip deep_cache_depth - 1 on its up path.  Every other step
+                            is a SHALLOW step: the UNet runs its outermost layers only (unet_3d_mix.DeepCacheSlot says which) on the
+                            current latents, time rows, context and banks, and takes the deep hidden state of the last key step.  No new kernel
+                            and no copy: every launch of a shallow step is one the full step makes at the same shape, and the cache is the
+                            concat buffer of skip deep_cache_depth - 1, kept.  One slot per (window of the step, plane), the planes being the main
+                            evaluation and PAG's / SEG's perturbed one (its scale only falls with t, so a perturbed evaluation that finds no
+                            slot is at a key step and fills it; asserted).  The window list is the same at every step of the loop (the window
+                            scheduler is called once, with step index 0: see the note on context_schedule below), so a shallow
+                            step meets the frames its key step cached, and under window_parallel the window-to-rank assignment is fixed: slots
+                            stay rank-local, no new collective.  Slots are dropped at the end of denoise() and between FreeInit passes.
+                            Memory per slot: one (nb f, H, W, C1 + Cs) fp16 buffer of skip deep_cache_depth - 1, 566 MB per window at 768 x 768,
+                            16 frames, CFG, depth 3 (32 x 96 x 96 x 960 x 2 bytes), half of that for a perturbed plane.  kv_downsample,
+                            tile_attention (its shift stays a function of the step), every guide, sampler, eta, init_latents, fuse mode, two_queues
+                            and share_first_layers act on the layers that run.  Image quality on real weights has not been assessed.  1 (the
+                            default): bitwise the loop without the keyword, the same operator calls, no cache allocated, nothing kept
+        deep_cache_depth    d >= 1, this project's own index (the mapping to DeepCache's cache_branch_id is not asserted): skip tensors are counted
+                            in production order -- conv_in, down_blocks.0 layer 0, layer 1, its downsampler, down_blocks.1 layer 0, ... -- and a
+                            shallow step runs conv_in, the first d - 1 of those operators and the last d up-block layers; d must be smaller
+                            than the number of skips (12).  3 (the default): all of the highest-resolution level on both sides.  Checked even
+                            when deep_cache_interval is 1
+                            Long clips, A STATED DEVIATION: the "uniform" / "uniform_open" window list is a function of a step index, and a cache
+                            keyed by window would meet other frames if a shallow step used another index than its key step.  With N > 1 the
+                            list of a whole cache period is therefore the key step's.  This loop calls the window scheduler once, with index 0,
+                            for every step (as the oracle does), so that holds by construction; a loop that moved its windows per step
+                            would have to hold them still over each period
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         plan = self.sampling_plan(
@@ -315,7 +344,7 @@ class MikuDanceVideoPipeline:
             apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
             pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode, seg_scale=seg_scale,
             seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
-            tile_attention_shift=tile_attention_shift)
+            tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth)
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         ops.require_gpu(latents, "MikuDanceVideoPipeline.denoise")
@@ -371,6 +400,21 @@ class MikuDanceVideoPipeline:
         tile_plan, tile_shift = plan.tile or (None, None)                          # no plan: no keyword either
         if tile_plan is not None:
             from .unet_3d_mix import tile_shift_at
+        # DeepCache: one slot per (window, plane) of this rank, plane 0 the main evaluation, 1 the perturbed one; no plan: no dict, no keyword
+        dc_slots = None
+        if plan.deep is not None:
+            from .unet_3d_mix import DeepCacheSlot
+            dc_slots = {}
+
+        def deep_kw(wi, plane, key):
+            """forward_nhwc's deep_cache keyword for window wi: a key step fills the window's slot, a shallow step reuses it."""
+            if dc_slots is None:
+                return {}
+            slot = dc_slots.get((wi, plane))
+            if slot is None:
+                assert key, f"DeepCache: no slot for window {wi}, plane {plane} at a shallow step"
+                slot = dc_slots[(wi, plane)] = DeepCacheSlot(plan.deep[1])
+            return dict(deep_cache=slot.fill() if key else slot.reuse())
         windows = [list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
                                                                             context_stride, context_overlap)]
         mm_len = getattr(den, "temporal_position_encoding_max_len", None)
@@ -439,12 +483,15 @@ class MikuDanceVideoPipeline:
                     timesteps = [int(t) for t in sch.timesteps]
                 if projected:
                     apg_m.zero_()                                        # the running average starts over with every pass
+                if dc_slots is not None:
+                    dc_slots.clear()                                     # every pass starts at k = 0 with an empty cache
                 for step_i, t in enumerate(timesteps):
                     noise_sum.zero_()
                     counter.zero_()
                     s_t = self._pag_scale_at(pert.scale, pert.adaptive, t) if pert else 0.0     # a pure function of t: no sync
                     # tiled self-attention: the main and the perturbed evaluation of a step share the plan and the step's shift
                     sa_kw = kv_kw if tile_plan is None else dict(kv_kw, tile_attention=tile_plan, tile_shift=tile_shift_at(tile_shift, t_start + step_i))
+                    dc_key = plan.deep is None or step_i % plan.deep[0] == 0      # k counts the steps this pass actually runs
                     for wi, win in enumerate(windows):
                         if window_parallel is not None and not window_parallel.mine(wi):
                             continue                                         # another rank's window (its share arrives in the all_reduce)
@@ -465,13 +512,13 @@ class MikuDanceVideoPipeline:
                         # both clip-halves are packed from the SAME latents (batch stride 0 above): the layers in front of the first attention
                         # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
                         pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
-                                                two_queues=self.two_queues, **sa_kw)
+                                                two_queues=self.two_queues, **sa_kw, **deep_kw(wi, 0, dc_key))
                         accumulate(pred, ns_main, counter, wi, nb)
                         if s_t > 0.0:
                             # ---- PAG / SEG: the conditional frames once more (the banks are still in place), the selected self-attention maps
                             # = identity / from blurred queries
                             pred = den.forward_nhwc(x[(nb - 1) * f:], 1, f, torch.full((1,), float(t)), cross.rows(f, 2 * f) if do_cfg else cross,
-                                                    **pert_kw, **sa_kw)
+                                                    **pert_kw, **sa_kw, **deep_kw(wi, 1, dc_key))
                             accumulate(pred, ns_pert, pert_counter, wi, 1)
                         reader.clear()
                         writer.clear()
@@ -481,6 +528,8 @@ class MikuDanceVideoPipeline:
                     if callback is not None and step_i % callback_steps == 0:
                         callback(step_i, t, self._latents_out(lat, latents))
         finally:
+            if dc_slots is not None:
+                dc_slots.clear()                                         # nothing outlives the clip
             refu.skip_dead_tail = False
             reader.clear()
             writer.clear()
@@ -492,7 +541,8 @@ class MikuDanceVideoPipeline:
     def sampling_plan(num_inference_steps, guidance_scale, has_init, shape, *, guidance_rescale, strength, context_fuse,
                       free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop, free_init_fast, apg, apg_eta,
                       apg_norm_threshold, apg_momentum, pag_scale, pag_adaptive_scale, pag_applied_layers, kv_downsample, kv_downsample_mode,
-                      seg_scale, seg_blur_sigma, seg_applied_layers, tile_attention=1, tile_attention_shift="cycle"):
+                      seg_scale, seg_blur_sigma, seg_applied_layers, tile_attention=1, tile_attention_shift="cycle", deep_cache_interval=1,
+                      deep_cache_depth=3):
         """Every refusal of denoise()'s sampling keywords (see its docstring) that needs no model -- every value is checked whether or not its
         feature is on, and neither UNet is called -- then what they resolve to -> SamplingPlan, still holding the layer names and the
         (factors, mode) that _resolve_plan hands to the denoising UNet.  has_init: there is a clip to start from (init_latents / video);
@@ -560,6 +610,10 @@ class MikuDanceVideoPipeline:
             raise ValueError("seg_applied_layers is empty: smoothed-energy guidance needs at least one attention block")
         if seg_s > 0.0:
             ask("seg_scale > 0")
+        import numbers
+        for name, v in (("deep_cache_interval", deep_cache_interval), ("deep_cache_depth", deep_cache_depth)):
+            if not isinstance(v, numbers.Integral) or isinstance(v, bool) or v < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
         guide = None
         if pag_s > 0.0:
             guide = Perturb("identity", pag_s, pag_a, pag_names, None)
@@ -571,12 +625,15 @@ class MikuDanceVideoPipeline:
             guide = Rescale(phi)
         return SamplingPlan(context_fuse, (free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
                                            free_init_fast), strength, (kv_factors, kv_mode) if any(f > 1 for f in kv_factors) else None, guide,
-                            (tile_factors, tile_shift) if any(f > 1 for f in tile_factors) else None)
+                            (tile_factors, tile_shift) if any(f > 1 for f in tile_factors) else None,
+                            (int(deep_cache_interval), int(deep_cache_depth)) if deep_cache_interval > 1 else None)
 
     def _resolve_plan(self, plan):
         """The refusals only the denoising UNet can make (a layer name that selects no block, more factors than levels, a level without
         attention) -> the plan with the selected blocks for the names and the per-block K / V plan for (factors, mode)."""
         den, guide = self.denoising_unet, plan.guide
+        if plan.deep is not None:
+            den.check_deep_cache_depth(plan.deep[1])
         if isinstance(guide, Perturb):
             what = () if guide.kind == "identity" else ("seg_applied_layers", "smoothed-energy guidance")
             guide = guide._replace(blocks=den.pag_blocks(guide.blocks, *what))
@@ -756,7 +813,7 @@ class MikuDanceVideoPipeline:
                  free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0,
                  pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), kv_downsample=1,
                  kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), tile_attention=1,
-                 tile_attention_shift="cycle", **kwargs):
+                 tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3, **kwargs):
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -774,7 +831,7 @@ class MikuDanceVideoPipeline:
                        apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
                        pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode,
                        seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
-                       tile_attention_shift=tile_attention_shift)
+                       tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth)
         self._resolve_plan(self.sampling_plan(num_inference_steps, guidance_scale, video is not None,
                                               (video_length, (height or 768) // 8, (width or 768) // 8), **loop_kw))
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):

@@ -82,17 +82,71 @@ def _side_streams(dev):
     return _SIDE_STREAMS[key]
 
 
-class _Skips:
-    """Bookkeeping of the concat buffers during one forward (see _UNetBase._skip_plan)."""
+class DeepCacheSlot:
+    """The state of DeepCache (Ma, Fang, Wang, arXiv 2312.00858: the idea only) for ONE sequence of forward_nhwc calls on the same frames:
+    forward_nhwc(deep_cache=slot).  depth d, 1 <= d < len(_skip_plan()), is THIS PROJECT'S OWN index, counted in skip tensors in the order of
+    _UNetBase._skip_plan (conv_in, down_blocks.0 layer 0, layer 1, its downsampler, down_blocks.1 layer 0, ...); how it maps to DeepCache's
+    cache_branch_id is not asserted.
+    mode "fill": the call is a full evaluation (a KEY step) that additionally keeps the hidden state that meets skip d - 1 on the up path.
+    mode "reuse": a SHALLOW step: conv_in and the first d - 1 skip-producing operators of the down path (down layers = resnet + spatial
+      transformer + motion module, or a downsampler where the order reaches one), then the kept hidden state where the up path would have written
+      it, then the last d up-block resnets with their transformers and motion modules (and an upsampler where one lies between them), then
+      conv_norm_out and conv_out.  d = 3 on the SD-1.5 geometry: all of level 0 on both sides; the kept tensor is up_blocks.2's upsampler output.
+    Nothing is copied: the cache IS the concat buffer of skip d - 1 (_skip_plan).  A fill call keeps a reference to that buffer in `store` -- its
+    left-hand C1 channels hold the hidden state when the call returns -- and a reuse call hands the right-hand slice of the KEPT buffer to the
+    producer of skip d - 1 instead of a fresh allocation; the up path pops the buffer as it is.  0 bytes moved per shallow step.
+    Memory: one (nb f, H, W, C1 + Cs) fp16 buffer of skip d - 1 per slot (two of (f, ...) under two_queues), alive until the slot is dropped or
+    filled again.  A reuse call uses the CURRENT time rows, context and banks for the layers it runs and reads nothing of a layer it skips.
+    `store` is shared by the slots made with reuse() / fill(): {"sig": (nb, f, two_queues, halves_identical), "bufs": {half: buffer},
+    "written": halves whose hidden slice the fill call's up path has produced in place}."""
 
-    def __init__(self, plan):
+    MODES = ("fill", "reuse")
+
+    def __init__(self, depth, mode="fill", store=None):
+        import numbers
+        if not isinstance(depth, numbers.Integral) or isinstance(depth, bool) or depth < 1:
+            raise ValueError(f"deep_cache_depth must be an integer >= 1, got {depth!r}")
+        if mode not in self.MODES:
+            raise ValueError(f"DeepCacheSlot: mode must be one of {self.MODES}, got {mode!r}")
+        self.depth, self.mode, self.store = int(depth), mode, {} if store is None else store
+
+    def fill(self):
+        return DeepCacheSlot(self.depth, "fill", self.store)
+
+    def reuse(self):
+        return DeepCacheSlot(self.depth, "reuse", self.store)
+
+    @property
+    def filled(self):
+        return bool(self.store.get("bufs"))
+
+    def drop(self):
+        self.store.clear()
+
+
+class _Skips:
+    """Bookkeeping of the concat buffers during one forward (see _UNetBase._skip_plan).  deep / half: the call's DeepCacheSlot and which of its
+    kept buffers this bookkeeping owns (0: the whole batch or the unconditional queue, 1: the conditional queue)."""
+
+    def __init__(self, plan, deep=None, half=0):
         self.plan, self.k, self.stack = plan, 0, []
+        self.deep, self.half = deep, half
 
     def slot(self, B, H, W, cs, device):
-        """Destination of the next skip tensor to be produced: the right-hand channel slice of a fresh concat buffer."""
+        """Destination of the next skip tensor to be produced: the right-hand channel slice of a fresh concat buffer -- or, for skip depth - 1 of
+        a DeepCache reuse call, of the buffer the fill call kept (its left-hand slice holds the deep hidden state)."""
         c1 = self.plan[self.k]
+        kept = self.deep is not None and self.k == self.deep.depth - 1
         self.k += 1
-        buf = torch.empty((B, H, W, c1 + cs), device=device, dtype=torch.float16)
+        if kept and self.deep.mode == "reuse":
+            buf = self.deep.store["bufs"][self.half]
+            if tuple(buf.shape) != (B, H, W, c1 + cs) or buf.device != torch.device(device):
+                raise ValueError(f"deep_cache: the kept buffer {tuple(buf.shape)} on {buf.device} does not fit this call's skip {self.k - 1}, "
+                                 f"{(B, H, W, c1 + cs)} on {device}")
+        else:
+            buf = torch.empty((B, H, W, c1 + cs), device=device, dtype=torch.float16)
+            if kept:
+                self.deep.store["bufs"][self.half] = buf
         self.stack.append((buf, c1))
         return buf[..., c1:]
 
@@ -101,6 +155,14 @@ class _Skips:
         buf, c1 = self.stack[-1]
         return buf[..., :c1]
 
+    def kept_hidden(self):
+        """DeepCache reuse: the hidden state the fill call left in the top buffer -- the buffer of skip depth - 1, whose up-path producer ran
+        in place in the fill call (pop() recorded it)."""
+        buf, _ = self.stack[-1]
+        assert len(self.stack) == self.deep.depth and buf is self.deep.store["bufs"][self.half], "the down path did not stop at skip depth - 1"
+        assert self.half in self.deep.store["written"], "the fill call never produced the kept hidden state"
+        return self.hidden_slot()
+
     def top_hw(self):
         return self.stack[-1][0].shape[1:3]
 
@@ -108,6 +170,8 @@ class _Skips:
         """The concatenated [hidden | skip] tensor; `x` must be the hidden slice written through hidden_slot()."""
         buf, c1 = self.stack.pop()
         assert x.data_ptr() == buf.data_ptr() and x.shape[-1] == c1 and x.shape[:3] == buf.shape[:3], "hidden state was not produced in place"
+        if self.deep is not None and self.deep.mode == "fill" and buf is self.deep.store["bufs"].get(self.half):
+            self.deep.store["written"].add(self.half)                    # the kept buffer's hidden slice now holds what a reuse call starts from
         return buf
 
     def __len__(self):
@@ -173,6 +237,34 @@ class _UNetBase(_Packed):
                 cs.append(blk.downsamplers[0].c)
         assert len(cs) == len(ups), (len(cs), len(ups))
         return [ups[len(ups) - 1 - k].cin - c for k, c in enumerate(cs)]
+
+    def _down_ops(self):
+        """The skip-producing operators of the down path behind conv_in, in production order: (block index, block, layer j) for a down layer,
+        (block index, block, None) for the block's downsampler."""
+        for bi, blk in enumerate(self.down_blocks):
+            for j in range(len(blk.resnets)):
+                yield bi, blk, j
+            if blk.downsamplers is not None:
+                yield bi, blk, None
+
+    def check_deep_cache_depth(self, depth):
+        """deep_cache_depth against this UNet: 1 <= depth < len(_skip_plan()); ValueError otherwise."""
+        n = len(self._skip_plan())
+        if not 1 <= depth < n:
+            raise ValueError(f"deep_cache_depth must be in 1..{n - 1} for this UNet ({n} skip tensors), got {depth}")
+        return depth
+
+    def deep_cache_layers(self, depth):
+        """What a DeepCache reuse call of this depth runs: (down ops, up layers, transformer blocks).  down ops: the first depth - 1 entries of
+        _down_ops(); up layers: the last `depth` (up block, layer j); transformer blocks: the TransformerBlocks of those layers, in
+        transformer_blocks_in_order()'s order."""
+        self.check_deep_cache_depth(depth)
+        down = list(self._down_ops())[:depth - 1]
+        ups = [(blk, j) for blk in self.up_blocks for j in range(len(blk.resnets))]
+        ups = ups[len(ups) - depth:]
+        run = [blk.attentions[j].transformer_blocks[0] for _, blk, j in down if j is not None and blk.has_cross_attention]
+        run += [blk.attentions[j].transformer_blocks[0] for blk, j in ups if blk.has_cross_attention]
+        return down, ups, [tb for tb in self.transformer_blocks_in_order() if any(tb is r for r in run)]
 
 
     # -------- packed top-level weights: conv_in (Cin zero-padded to 64), time embedding, all time_emb_proj fused
@@ -496,7 +588,7 @@ class UNet3DConditionModel(_UNetBase):
 
     # ------------------------------------------------------------------------------------------ internal NHWC forward
     def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None, kv_downsample=None, seg=None,
-                     tile_attention=None, tile_shift=0):
+                     tile_attention=None, tile_shift=0, deep_cache=None):
         """x: (nb*f, h, w, 64) fp16 (4 latent channels, zero padded); returns pred tokens [(nb*f*h*w), 4].
         pag: None, or the blocks of pag_blocks(): this call is then the PERTURBED evaluation of perturbed-attention guidance, a call of its own
         beside the main one: nb must be 1, x the conditional frames, cross their context (the main call's context or its rows(f, 2f): the
@@ -508,6 +600,14 @@ class UNet3DConditionModel(_UNetBase):
         shifts its tiling by (sy, sx) = (q th // 4, q tw // 4).  The paper's code draws the shift at random per call; here it is a pure
         function of the step, so that runs are reproducible and the ranks of window_parallel agree without talking.
         What each does in the blocks: blocks.SelfAttnCall, which carries the four through this call.
+        deep_cache: None (the plain call: no cache is allocated, nothing is kept, the operator calls are those of a call without the keyword), or
+        a DeepCacheSlot: mode "fill" runs everything and keeps the concat buffer of skip depth - 1; mode "reuse" runs the outermost layers only
+        and starts the up path from the hidden state in the kept buffer (DeepCacheSlot says which layers).  pag / seg / kv_downsample /
+        tile_attention / tile_shift act on the layers that run, exactly as in a full call; halves_identical and the shared first resnet work on a
+        reuse call for depth >= 2 (depth 1 shares conv_in only).  A reuse call never reads the bank, the cross-attention K / V or the time rows
+        of a layer it skips, and projects a new context for the blocks it runs only.  ValueError, before any launch: a depth out of range; reuse
+        with an empty slot or with a kept buffer whose shape, dtype or device does not fit this call; a reuse call whose (nb, f, two_queues,
+        halves_identical) differs from the fill call's.
         halves_identical: the caller GUARANTEES that the two clip-halves of x hold the same latents (classifier-free guidance: the loop of
         src/pipelines/pipeline_mikudance.py:626-633 feeds `torch.cat([latents] * 2)`) -- with equal timesteps, conv_in and the first resnet
         (no attention in front of them: nothing has seen the context or the bank yet) then produce the same tensor for both halves, so
@@ -524,16 +624,20 @@ class UNet3DConditionModel(_UNetBase):
         dev = x.device
         _, hh, ww, _ = x.shape
         force_size = self._needs_upsample_size(hh, ww, len(self.down_blocks))
+        tt = torch.as_tensor(timesteps).reshape(-1)
+        share = bool(halves_identical and nb == 2 and float(tt[0]) == float(tt[-1]))
+        b0 = self.down_blocks[0]
+        queues = bool(share and two_queues and x.is_cuda and (b0.has_cross_attention or b0.motion_modules[0] is not None))
+        if deep_cache is not None:                                       # every refusal before the first launch
+            self._deep_cache_begin(deep_cache, x, nb, f, (nb, f, bool(two_queues), bool(halves_identical)), queues)
+        reuse = deep_cache is not None and deep_cache.mode == "reuse"
         trows = self._time_rows(pk, timesteps, dev)                         # [nb, sumC]
         gf = 1 if self.use_inflated_groupnorm else f                        # plain nn.GroupNorm on 5-D: stats across frames
         B = x.shape[0]
         c0 = self.conv_in.weight.shape[0]
-        tt = torch.as_tensor(timesteps).reshape(-1)
-        share = bool(halves_identical and nb == 2 and float(tt[0]) == float(tt[-1]))
-        b0 = self.down_blocks[0]
-        if share and two_queues and x.is_cuda and (b0.has_cross_attention or b0.motion_modules[0] is not None):
-            return self._forward_two_queues(x, f, trows, cross, pk, gf, force_size, sa)
-        skips = _Skips(self._skip_plan())
+        if queues:
+            return self._forward_two_queues(x, f, trows, cross, pk, gf, force_size, sa, deep_cache)
+        skips = _Skips(self._skip_plan(), deep_cache)
         first = None
         if share:
             slot = skips.slot(B, hh, ww, c0, dev)
@@ -542,7 +646,9 @@ class UNet3DConditionModel(_UNetBase):
             x = slot
             # the first resnet on one half (time rows of group 0 = those of group 1), then both halves from the copy
             r = b0.resnets[0]
-            if b0.has_cross_attention or b0.motion_modules[0] is not None:
+            if reuse and deep_cache.depth == 1:                          # DeepCache reuse at depth 1 runs no down layer: only conv_in is shared
+                pass
+            elif b0.has_cross_attention or b0.motion_modules[0] is not None:
                 first = r(x[:f], self._temb(pk, trows, r), f * hh * ww, gf).repeat(2, 1, 1, 1)
             else:                                                        # the resnet is its layer's last operator: it writes the skip in place
                 dst = skips.slot(B, hh, ww, r.cout, dev)
@@ -551,40 +657,82 @@ class UNet3DConditionModel(_UNetBase):
                 first = dst
         else:
             x = ops.conv3x3(x, pk["cin"], c0, bias=pk["cinb"], out=skips.slot(B, hh, ww, c0, dev))
-        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first))
+        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first, deep=deep_cache))
 
-    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first=None, out=None):
+    def _deep_cache_begin(self, deep, x, nb, f, sig, queues):
+        """The refusals of forward_nhwc(deep_cache=) and the start of a fill: a fill call empties the store and records its call signature; a
+        reuse call must find the fill call's signature and one kept buffer per clip-half queue that fits this call."""
+        d = self.check_deep_cache_depth(deep.depth)
+        if deep.mode == "fill":
+            deep.store.clear()
+            deep.store.update(sig=sig, bufs={}, written=set())
+            return
+        if not deep.filled:
+            raise ValueError(f"deep_cache: reuse with an empty slot (depth {d}): no fill call has kept a hidden state")
+        if deep.store["sig"] != sig:
+            raise ValueError(f"deep_cache: this reuse call has (nb, f, two_queues, halves_identical) = {sig}, the fill call had {deep.store['sig']}")
+        _, hh, ww, _ = x.shape
+        geo = [(hh, ww, self.conv_in.weight.shape[0])]
+        for _, blk, j in self._down_ops():
+            h, w, _ = geo[-1]
+            geo.append(((h + 1) // 2, (w + 1) // 2, blk.downsamplers[0].c) if j is None else (h, w, blk.resnets[j].cout))
+        h, w, cs = geo[d - 1]
+        want = (f if queues else nb * f, h, w, self._skip_plan()[d - 1] + cs)
+        halves = (0, 1) if queues else (0,)
+        bufs = deep.store["bufs"]
+        if sorted(bufs) != list(halves) or not all(k in deep.store["written"] for k in halves):
+            raise ValueError(f"deep_cache: the slot holds the buffers of clip-half queues {sorted(bufs)}, this call needs {list(halves)}")
+        for k in halves:
+            if tuple(bufs[k].shape) != want or bufs[k].dtype != torch.float16 or bufs[k].device != x.device:
+                raise ValueError(f"deep_cache: the kept buffer {tuple(bufs[k].shape)} {bufs[k].dtype} on {bufs[k].device} does not fit this call, "
+                                 f"which needs {want} torch.float16 on {x.device}")
+
+    def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first=None, out=None, deep=None):
         """Everything behind conv_in.  x: conv_in's output (nb*f, h, w, C0), already in its skip slot; `sa`: the call's blocks.SelfAttnCall;
         `first`: the first resnet's output when the caller has evaluated it (shared between the clip-halves); `out`: where conv_out writes,
-        (nb*f, h, w, 4)."""
+        (nb*f, h, w, 4); `deep`: the call's DeepCacheSlot (the one `skips` was made with).  In mode "reuse" the down path stops behind its first
+        depth - 1 operators, the mid block and the first len(_skip_plan()) - depth up layers do not run, and the up path starts from the hidden
+        state in the kept buffer; otherwise everything runs, operator for operator as without the slot."""
         dev = x.device
         B = x.shape[0]
-        for bi, blk in enumerate(self.down_blocks):
-            for j, r in enumerate(blk.resnets):
-                H_, W_ = x.shape[1:3]
-                mm = blk.motion_modules[j]
-                last_op = not (blk.has_cross_attention or mm is not None)
-                if first is not None and bi == 0 and j == 0:
-                    x = first                                            # (written into its skip slot by the caller if it is the layer's last operator)
-                else:
-                    dst = skips.slot(B, H_, W_, r.cout, dev)             # the layer's LAST operator writes the skip in place
-                    x = r(x, self._temb(pk, trows, r), f * H_ * W_, gf, out=None if not last_op else dst)
-                if not last_op and first is not None and bi == 0 and j == 0:
-                    dst = skips.slot(B, H_, W_, r.cout, dev)
-                if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=None if mm is not None else dst, sa=sa)
-                if mm is not None:
-                    x = mm(x, nb, f, out=dst)
-            if blk.downsamplers is not None:
+        reuse = deep is not None and deep.mode == "reuse"
+        n_up = sum(len(blk.resnets) for blk in self.up_blocks)
+        down_ops = list(self._down_ops())
+        for bi, blk, j in down_ops[:deep.depth - 1] if reuse else down_ops:
+            if j is None:
                 x = blk.downsamplers[0](x, out=skips.slot(B, (x.shape[1] + 1) // 2, (x.shape[2] + 1) // 2, blk.downsamplers[0].c, dev))
-        mb = self.mid_block
-        x = mb.resnets[0](x, self._temb(pk, trows, mb.resnets[0]), f * x.shape[1] * x.shape[2], gf)
-        x = mb.attentions[0](x, cross, sa=sa)
-        if mb.motion_modules[0] is not None:
-            x = mb.motion_modules[0](x, nb, f)
-        x = mb.resnets[1](x, self._temb(pk, trows, mb.resnets[1]), f * x.shape[1] * x.shape[2], gf, out=skips.hidden_slot())
+                continue
+            r = blk.resnets[j]
+            H_, W_ = x.shape[1:3]
+            mm = blk.motion_modules[j]
+            last_op = not (blk.has_cross_attention or mm is not None)
+            if first is not None and bi == 0 and j == 0:
+                x = first                                                # (written into its skip slot by the caller if it is the layer's last operator)
+            else:
+                dst = skips.slot(B, H_, W_, r.cout, dev)                 # the layer's LAST operator writes the skip in place
+                x = r(x, self._temb(pk, trows, r), f * H_ * W_, gf, out=None if not last_op else dst)
+            if not last_op and first is not None and bi == 0 and j == 0:
+                dst = skips.slot(B, H_, W_, r.cout, dev)
+            if blk.has_cross_attention:
+                x = blk.attentions[j](x, cross, out=None if mm is not None else dst, sa=sa)
+            if mm is not None:
+                x = mm(x, nb, f, out=dst)
+        if reuse:
+            x = skips.kept_hidden()                                      # what the fill call's up path wrote in front of skip depth - 1
+        else:
+            mb = self.mid_block
+            x = mb.resnets[0](x, self._temb(pk, trows, mb.resnets[0]), f * x.shape[1] * x.shape[2], gf)
+            x = mb.attentions[0](x, cross, sa=sa)
+            if mb.motion_modules[0] is not None:
+                x = mb.motion_modules[0](x, nb, f)
+            x = mb.resnets[1](x, self._temb(pk, trows, mb.resnets[1]), f * x.shape[1] * x.shape[2], gf, out=skips.hidden_slot())
+        skipped = n_up - deep.depth if reuse else 0                      # up layers that a reuse call leaves out, from the deepest
+        ui = 0
         for blk in self.up_blocks:
             for j, r in enumerate(blk.resnets):
+                ui += 1
+                if ui <= skipped:
+                    continue
                 x = skips.pop(x)                                         # [hidden | skip]: nothing is copied
                 H_, W_ = x.shape[1:3]
                 mm = blk.motion_modules[j]
@@ -596,12 +744,12 @@ class UNet3DConditionModel(_UNetBase):
                     x = blk.attentions[j](x, cross, out=None if mm is not None else dst, sa=sa)
                 if mm is not None:
                     x = mm(x, nb, f, out=dst)
-            if blk.upsamplers is not None:
+            if blk.upsamplers is not None and ui > skipped:              # (behind a block whose last layer ran)
                 x = blk.upsamplers[0](x, skips.top_hw() if force_size else None, out=skips.hidden_slot())
         x = groupnorm_frames(x, pk["ow"], pk["ob"], self.norm_eps, True, gf)
         return ops.conv3x3(x, pk["co"], 4, bias=pk["cob"], out=out)
 
-    def _forward_two_queues(self, x, f, trows, cross, pk, gf, force_size, sa):
+    def _forward_two_queues(self, x, f, trows, cross, pk, gf, force_size, sa, deep=None):
         """The two clip-halves of a classifier-free-guidance batch as two kernel queues (stage B, without CU masks).
 
         One queue of B = 2f kernels leaves the chip idle wherever a launch cannot fill it -- partial last rounds of the persistent GEMM / conv
@@ -621,20 +769,30 @@ class UNet3DConditionModel(_UNetBase):
         runs its queues one after the other (queue 1 waits for queue 0's end), every later one side by side.
         Results: each half goes through the same kernels with B = f instead of B = 2f; where the tile dispatch picks another flavour for the
         smaller problem the fp32 summation order differs (bits may differ from the one-queue evaluation, error against fp32 is the same:
-        tests/test_two_queues_gpu.py); run to run the two-queue evaluation is bitwise reproducible (no atomics, no order dependence)."""
+        tests/test_two_queues_gpu.py); run to run the two-queue evaluation is bitwise reproducible (no atomics, no order dependence).
+        DeepCache (`deep`, a DeepCacheSlot): each clip-half has its own _Skips and so its own kept buffer, store["bufs"][0 / 1].  A kept buffer
+        outlives the call, against the rule above, and is safe for this reason: it is allocated inside its queue's stream context, so it belongs to
+        THAT side stream's pool, and the side streams are created once per device (_side_streams), so the reuse call of half c touches it on the
+        same stream that filled it -- stream order alone separates the fill call's writes from the reuse call's reads and writes, and no other
+        stream ever reads it (the calling stream reads `pred` only).  While the slot holds its reference the allocator cannot hand the block out;
+        when the slot is dropped the block returns to its own stream's pool, whose next user is ordered behind everything queued on that stream.
+        At depth 1 the kept buffer of half 0 is conv_in's skip, allocated on the calling stream like today: it is written on the calling stream
+        and read on queue 0 behind the fork event, and the calling stream has waited for queue 0's end before the next call writes it again.
+        forward_nhwc refuses a reuse call that would take the other path than its fill call (two_queues is part of the call signature)."""
         dev = x.device
         _, hh, ww, _ = x.shape
         c0 = self.conv_in.weight.shape[0]
         main = torch.cuda.current_stream(dev)
         qs = _side_streams(dev)
         plan = self._skip_plan()
-        sk = [_Skips(plan), _Skips(plan)]
+        reuse = deep is not None and deep.mode == "reuse"
+        sk = [_Skips(plan, deep, 0), _Skips(plan, deep, 1)]
         slot0 = sk[0].slot(f, hh, ww, c0, dev)
         ops.conv3x3(x[:f], pk["cin"], c0, bias=pk["cinb"], out=slot0)
         r = self.down_blocks[0].resnets[0]
-        first = r(slot0, self._temb(pk, trows[0:1], r), f * hh * ww, gf)
-        for tb in self.transformer_blocks_in_order():
-            tb.context_kv(cross)
+        first = None if reuse and deep.depth == 1 else r(slot0, self._temb(pk, trows[0:1], r), f * hh * ww, gf)
+        for tb in self.deep_cache_layers(deep.depth)[2] if reuse else self.transformer_blocks_in_order():
+            tb.context_kv(cross)                                          # (a reuse call: of the blocks it runs only)
         pred = torch.empty((2 * f, hh, ww, 4), device=dev, dtype=torch.float16)
         primed = pk.setdefault("_two_queue_shapes", set())
         serial = (f, hh, ww) not in primed or getattr(self, "serialize_queues", False)     # serialize_queues: bench.py's per-launch timing pass
@@ -650,7 +808,7 @@ class UNet3DConditionModel(_UNetBase):
                     slot1 = sk[1].slot(f, hh, ww, c0, dev)
                     slot1.copy_(slot0)
                 self._body(slot0 if c == 0 else slot1, sk[c], 1, f, trows[c:c + 1], cross.rows(c * f, (c + 1) * f), pk, gf, force_size,
-                           replace(sa, half=c), first=first, out=pred[c * f:(c + 1) * f])
+                           replace(sa, half=c), first=first, out=pred[c * f:(c + 1) * f], deep=deep)
                 ev = torch.cuda.Event()
                 ev.record(qs[c])
                 done.append(ev)
