@@ -390,6 +390,24 @@ int md_token_mean_f16(const void* x, void* y, int B, int L, int C, void* workspa
  * 16-byte aligned and not overlapping; MD_ERR_ARG otherwise, with nothing launched and y untouched. */
 int md_token_tile_f16(const void* x, void* y, int B, int Hh, int Ww, int C, int t, int sy, int sx, int tile_stride, int inverse, void* stream);
 
+/* Resampling of the packed latents for two-pass high-resolution sampling (the pipeline's hires_scale=): the clip sampled at the low size is
+ * enlarged to the target size, re-noised by md_add_noise_f16, and the tail of the schedule runs on it.
+ * x: (F, Hi, Wi, 4) fp16, the loop's packed latent layout (md_pack_nhwc_f16 with cpad = 4: 8 bytes per pixel); y: (F, Ho, Wo, 4) fp16; both
+ * contiguous.  mode 0 nearest-exact, 1 bilinear, 2 bicubic (A = -0.75), each as torch.nn.functional.interpolate(x, size=(Ho, Wo), mode=...,
+ * align_corners=False, antialias=False) per frame and channel: output o of an axis with ni inputs and no outputs sits at the source coordinate
+ * (o + 0.5) ni / no - 0.5; nearest-exact reads index floor((o + 0.5) ni / no), clamped to ni - 1; bilinear clamps the coordinate at 0 and
+ * blends floor and floor + 1 (clamped) by the fraction; bicubic blends the four taps floor - 1 .. floor + 2, their indices clamped to the border.
+ * Any ratio, up or down, the two axes independent.  NO antialiasing on the way down: a ratio below 1 skips input pixels (aliasing), exactly
+ * like antialias=False.
+ * fp32 operations, ONE rounding to fp16 at the store.  Floor and fraction come from the integer division ((2 o + 1) ni - no) / (2 no), and the
+ * fraction, the weights and the sums are carried as pairs of floats, so a value that cancels to little is still within an fp16 ulp of the
+ * float64 result.  nearest-exact is a copy; a size-preserving call returns x (weights exactly 0 and 1; the sign of a zero may change).
+ * Non-finite inputs give non-finite outputs (0 * Inf, as in torch).  One thread per output pixel, 8-byte loads and stores, no atomics: two
+ * calls give the same bits.  Nothing outside the F*Ho*Wo pixels of y is written.
+ * All sizes positive, F*Hi*Wi and F*Ho*Wo within int, mode 0..2, x and y not NULL, 8-byte aligned and not overlapping; MD_ERR_ARG otherwise,
+ * with nothing launched and y untouched. */
+int md_latent_resize_f16(const void* x, void* y, int F, int Hi, int Wi, int Ho, int Wo, int mode, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

@@ -30,6 +30,10 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      (an addition: shifted-tile spatial self-attention, arXiv 2311.17528; default 1 = off)
     pipe(..., deep_cache_interval=--deep_cache_interval, deep_cache_depth=--deep_cache_depth)
                      (an addition: DeepCache, arXiv 2312.00858: the deep part of the denoising UNet every N-th step only; default 1 = off)
+    pipe(..., hires_scale=--hires_scale, hires_strength=--hires_strength, hires_mode=--hires_mode, hires_steps=--hires_steps,
+         scene_motion_lowres_npy=camera_to_scene_motion at the first pass's grid)
+                     (an addition: two-pass high-resolution sampling, the whole schedule at -W / S x -H / S, the latents enlarged on the GPU,
+                     the tail of the schedule at -W x -H; default 1 = off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -162,9 +166,21 @@ def parse_args(argv=None):
     parser.add_argument("--deep_cache_depth", type=int, default=3, metavar="D",
                         help="(addition) DeepCache: how many skip connections, counted from conv_in, the steps between still evaluate "
                              "(this project's own index); 3 = the whole highest-resolution level on both sides")
+    parser.add_argument("--hires_scale", type=float, default=1.0, metavar="S",
+                        help="(addition) two-pass high-resolution sampling, an approximation that saves most full-resolution steps: the whole "
+                             "schedule runs at -W / S x -H / S (rounded to multiples of 8), the latents are enlarged on the GPU and re-noised, and "
+                             "only the last --hires_strength of the schedule runs at -W x -H; 1 = off.  Not with --init_video")
+    parser.add_argument("--hires_strength", type=float, default=0.5,
+                        help="(addition) with --hires_scale: the share of the second pass's schedule that is run, in (0, 1)")
+    parser.add_argument("--hires_mode", choices=("nearest", "bilinear", "bicubic"), default="bicubic",
+                        help="(addition) with --hires_scale: how the latents are enlarged")
+    parser.add_argument("--hires_steps", type=int, default=None,
+                        help="(addition) with --hires_scale: steps of the second pass's schedule before --hires_strength cuts it; default --steps")
     args = parser.parse_args(argv)
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
+    if args.hires_scale != 1.0 and args.init_video is not None:
+        parser.error("--hires_scale cannot be combined with --init_video: the second pass is itself the video-to-video pass")
     return args
 
 
@@ -235,9 +251,15 @@ def main(argv=None):
     else:
         w2c_npy, c2w_npy = np.load(config.tgt_w2c_path), np.load(config.tgt_c2w_path)
     depth_map = np.zeros((1, height, width)) if _none(config.get("ref_depth_path")) else np.load(config.ref_depth_path)
-    depth_map = resize_depth(depth_map, (1, height // 8, width // 8))
-    scene_motion_npy = camera_to_scene_motion([w2c_npy[k] for k in range(w2c_npy.shape[0])], [c2w_npy[k] for k in range(c2w_npy.shape[0])],
-                                              [3.2, 3.2, 1.6, 1.6], depth_map, width // 8, height // 8, False)
+    w2cs, c2ws = [w2c_npy[k] for k in range(w2c_npy.shape[0])], [c2w_npy[k] for k in range(c2w_npy.shape[0])]
+    scene_motion_npy = camera_to_scene_motion(w2cs, c2ws, [3.2, 3.2, 1.6, 1.6], resize_depth(depth_map, (1, height // 8, width // 8)), width // 8,
+                                              height // 8, False)
+    # --hires_scale: the first pass gets the EXACT flow of its own grid (the depth map resized to it), not the pipeline's resampled one
+    scene_motion_lowres_npy = None
+    hires = pipe.hires_plan(height, width, args.steps, args.hires_scale, args.hires_strength, args.hires_mode, args.hires_steps)
+    if hires is not None:
+        h_lo, w_lo = hires[0] // 8, hires[1] // 8
+        scene_motion_lowres_npy = camera_to_scene_motion(w2cs, c2ws, [3.2, 3.2, 1.6, 1.6], resize_depth(depth_map, (1, h_lo, w_lo)), w_lo, h_lo, False)
     print("Total frames: {}".format(num_frames))
     init_pils = None
     if args.init_video is not None:
@@ -263,7 +285,9 @@ def main(argv=None):
                kv_downsample=args.kv_downsample, kv_downsample_mode=args.kv_downsample_mode,
                seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma, seg_applied_layers=_layer_names(args.seg_layers),
                tile_attention=args.tile_attention, tile_attention_shift=args.tile_attention_shift,
-               deep_cache_interval=args.deep_cache_interval, deep_cache_depth=args.deep_cache_depth)
+               deep_cache_interval=args.deep_cache_interval, deep_cache_depth=args.deep_cache_depth,
+               hires_scale=args.hires_scale, hires_strength=args.hires_strength, hires_mode=args.hires_mode, hires_steps=args.hires_steps,
+               scene_motion_lowres_npy=scene_motion_lowres_npy)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

@@ -569,6 +569,34 @@ def token_untile(x, B, Hh, Ww, t, shift=(0, 0), tile_stride=None, out=None):
     return _tile_call("token_untile", x, B, Hh, Ww, t, shift, tile_stride, out, True)[0]
 
 
+RESIZE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+RESIZE_TAPS = {"nearest": 1, "bilinear": 4, "bicubic": 16}
+
+
+def latent_resize(x, F, hi, wi, ho, wo, mode="bicubic", out=None):
+    """Resampling of packed latents (md_latent_resize_f16; two-pass high-resolution sampling): x contiguous fp16 of F*hi*wi*4 elements, the
+    loop's (F, hi, wi, 4) layout -> y (F, ho, wo, 4).  mode "nearest" (nearest-exact), "bilinear" or "bicubic", each as F.interpolate(size=(ho, wo),
+    align_corners=False, antialias=False); any ratio, no antialiasing on the way down.  `out`: a contiguous destination of F*ho*wo*4 elements
+    that does not overlap x."""
+    _chk(x, "x"); _chk(out, "out")
+    if mode not in RESIZE_MODES:
+        raise _lib.MdanceHipError(f"latent_resize: mode must be one of {sorted(RESIZE_MODES)}, got {mode!r}")
+    if min(F, hi, wi, ho, wo) < 1:
+        raise _lib.MdanceHipError(f"latent_resize: F, hi, wi, ho, wo must be positive, got {(F, hi, wi, ho, wo)}")
+    if not x.is_contiguous() or x.numel() != F * hi * wi * 4:
+        raise _lib.MdanceHipError(f"latent_resize: x must be contiguous with F*hi*wi*4 = {F * hi * wi * 4} elements, got shape {tuple(x.shape)} "
+                                  f"strides {tuple(x.stride())}")
+    if out is None:
+        out = torch.empty((F, ho, wo, 4), device=x.device, dtype=F16)
+    if not out.is_contiguous() or out.numel() != F * ho * wo * 4:
+        raise _lib.MdanceHipError(f"latent_resize: out must be contiguous with F*ho*wo*4 = {F * ho * wo * 4} elements, got shape {tuple(out.shape)}")
+    n_out = F * ho * wo
+    taps = RESIZE_TAPS[mode]
+    _lib.call("md_latent_resize_f16", x.data_ptr(), out.data_ptr(), F, hi, wi, ho, wo, RESIZE_MODES[mode], _st(),
+              meta=(f"latent_resize F={F} {hi}x{wi}->{ho}x{wo} {mode}", 8.0 * n_out * taps if taps > 1 else 0.0, 8.0 * (F * hi * wi + n_out)))
+    return out
+
+
 def blur_kernel_size(sigma, n):
     """Taps of SEG's Gaussian along a grid axis of n tokens: the official gaussian_blur_2d's ceil(6 sigma) + 1 - ceil(6 sigma) % 2, clamped to
     the largest odd number a reflect-padded axis of n allows (n if n is odd, else n + 1); 1 for n = 1."""

@@ -801,6 +801,84 @@ class MikuDanceVideoPipeline:
         emb = enc(px).last_hidden_state
         return enc.visual_projection(enc.vision_model.post_layernorm(emb))
 
+    def _condition_latents(self, ref_image, ref_skel_image, groups, video, scene_motion, height, width, f):
+        """The VAE latents of every condition image at height x width and the flow -> (ref_latents (1, F, 22, h, w), init_latents (1, 4, F, h, w) or
+        None).  All 3F + 2 condition images in ONE pass through the VAE (reference :456-549 encodes them one by one, same arithmetic per image),
+        and the video-to-video frames after them, in the same pass."""
+        rep = lambda z: z.unsqueeze(1).repeat(1, f, 1, 1, 1).reshape((-1,) + tuple(z.shape[1:]))
+        lat_all = self._encode_many([_pil_to_tensor(ref_image, height, width, True), _pil_to_tensor(ref_skel_image, height, width, False)]
+                                    + [_pil_to_tensor(im, height, width, False) for grp in groups for im in grp]
+                                    + [_pil_to_tensor(im, height, width, True) for im in ([] if video is None else video)])
+        ref_image_latents, pose_ref_latents = rep(lat_all[0:1]), rep(lat_all[1:2])
+        o = [2]
+        for grp in groups:
+            o.append(o[-1] + len(grp))
+        pose_tgt, face_tgt, hand_tgt = (lat_all[a:b] for a, b in zip(o[:-1], o[1:]))
+        init_latents = None if video is None else lat_all[o[-1]:o[-1] + f].permute(1, 0, 2, 3)[None]     # (1, 4, F, h, w)
+        tracker = torch.from_numpy(np.asarray(scene_motion)).to(dtype=ref_image_latents.dtype, device=ref_image_latents.device)
+        return torch.cat([ref_image_latents, pose_ref_latents, pose_tgt, face_tgt, hand_tgt, tracker], dim=1)[None], init_latents
+
+    # ------------------------------------------------------------------------------------------ two-pass high-resolution sampling
+    hires_min_side = 64        # px: the smallest side pass 1 may have (8 latent cells; the UNets halve three times)
+
+    def hires_plan(self, height, width, num_inference_steps, hires_scale=1, hires_strength=0.5, hires_mode="bicubic", hires_steps=None):
+        """Every refusal of __call__'s hires_* keywords that needs neither a model nor a sampling plan (each value is checked whether or not
+        hires_scale is > 1) -> None for hires_scale == 1, else (H_lo, W_lo, pass 2's num_inference_steps) with
+        H_lo = 8 round(height / hires_scale / 8), W_lo likewise (Python's round).  A low side below self.hires_min_side is refused."""
+        import numbers
+        try:
+            s, st = float(hires_scale), float(hires_strength)
+        except (TypeError, ValueError):
+            raise ValueError(f"hires_scale and hires_strength must be numbers, got {hires_scale!r} and {hires_strength!r}") from None
+        if not (math.isfinite(s) and s >= 1.0):
+            raise ValueError(f"hires_scale must be a finite number >= 1, got {hires_scale}")
+        if not (math.isfinite(st) and 0.0 < st < 1.0):
+            raise ValueError(f"hires_strength must be a finite number in (0, 1), got {hires_strength}")
+        if hires_mode not in ops.RESIZE_MODES:
+            raise ValueError(f"hires_mode must be one of {sorted(ops.RESIZE_MODES)}, got {hires_mode!r}")
+        if hires_steps is not None and (not isinstance(hires_steps, numbers.Integral) or isinstance(hires_steps, bool) or hires_steps < 1):
+            raise ValueError(f"hires_steps must be None or an integer >= 1, got {hires_steps!r}")
+        if s == 1.0:
+            return None
+        height_lo, width_lo = 8 * round(height / s / 8), 8 * round(width / s / 8)
+        if height_lo < self.hires_min_side or width_lo < self.hires_min_side:
+            raise ValueError(f"hires_scale={hires_scale}: the low size {width_lo} x {height_lo} of {width} x {height} has a side below "
+                             f"{self.hires_min_side}")
+        if height_lo == height or width_lo == width:
+            raise ValueError(f"hires_scale={hires_scale}: the low size {width_lo} x {height_lo} has a side of the full size {width} x {height}; "
+                             "use hires_scale=1 or a larger scale")
+        return height_lo, width_lo, int(num_inference_steps if hires_steps is None else hires_steps)
+
+    @staticmethod
+    def lowres_scene_motion(scene_motion, h_lo, w_lo):
+        """Pass 1's flow DERIVED from the full-size one, on the host: (F, 2, h, w) -> float64 numpy (F, 2, h_lo, w_lo) by
+        F.interpolate(mode="bilinear", align_corners=False), channel 0 (x) times w_lo / w and channel 1 (y) times h_lo / h, the flow being
+        in latent-grid units.  An approximation of camera_to_scene_motion at the low grid (its clip to mean +- 3 std and the depth resize do
+        not commute with the resampling)."""
+        import torch.nn.functional as F
+        flow = torch.from_numpy(np.asarray(scene_motion, dtype=np.float64))
+        if flow.dim() != 4 or flow.shape[1] != 2:
+            raise ValueError(f"scene motion must be (F, 2, h, w), got {tuple(flow.shape)}")
+        h, w = flow.shape[2:]
+        low = F.interpolate(flow, size=(h_lo, w_lo), mode="bilinear", align_corners=False)
+        return (low * torch.tensor([w_lo / w, h_lo / h], dtype=torch.float64).view(1, 2, 1, 1)).numpy()
+
+    def upscale_latents(self, latents, height, width, mode="bicubic"):
+        """latents (1, 4, F, h_lo, w_lo) on the GPU -> (1, 4, F, height / 8, width / 8) in the same dtype: packed to the loop's (F, h, w, 4) fp16
+        layout, resampled by ops.latent_resize (md_latent_resize_f16: mode "nearest", "bilinear" or "bicubic", F.interpolate's rules without
+        antialiasing, fp32 arithmetic, one rounding) and unpacked.  No host copy.  height, width: the target size in pixels."""
+        ops.require_gpu(latents, "MikuDanceVideoPipeline.upscale_latents")
+        if latents.dim() != 5 or latents.shape[0] != 1 or latents.shape[1] != 4:
+            raise ValueError(f"upscale_latents: latents must be (1, 4, F, h, w), got {tuple(latents.shape)}")
+        _, c, F_, hl, wl = latents.shape
+        hh, ww = height // self.vae_scale_factor, width // self.vae_scale_factor
+        st = latents.stride()
+        lat = ops.pack_nhwc(latents, F_, F_, (0, st[2], st[1], st[3], st[4]), 0, c, 4, hl, wl)
+        out = torch.empty((1, c, F_, hh, ww), device=latents.device, dtype=latents.dtype)
+        so = out.stride()
+        ops.unpack_nhwc(ops.latent_resize(lat, F_, hl, wl, hh, ww, mode), out, F_, F_, (0, so[2], so[1], so[3], so[4]), c, hh, ww)
+        return out
+
     # ------------------------------------------------------------------------------------------ reference-compatible call
     @torch.no_grad()
     def __call__(self, ref_image, ref_skel_image, tgt_pose_images, tgt_face_images, tgt_hand_images, scene_motion_npy, width,
@@ -813,7 +891,36 @@ class MikuDanceVideoPipeline:
                  free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0,
                  pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), kv_downsample=1,
                  kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), tile_attention=1,
-                 tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3, **kwargs):
+                 tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3, hires_scale=1, hires_strength=0.5,
+                 hires_mode="bicubic", hires_steps=None, scene_motion_lowres_npy=None, **kwargs):
+        """The reference call (src/pipelines/pipeline_mikudance.py:362-704) with denoise()'s sampling keywords (see its docstring), and:
+
+        hires_scale         two-pass high-resolution sampling (the "hires fix" of the SD-1.5 front ends), an opt-in APPROXIMATION of the
+                            one-pass clip: a finite number >= 1.  With s > 1 the WHOLE schedule is sampled at the low size
+                            H_lo = 8 round(height / s / 8), W_lo = 8 round(width / s / 8) (Python's round: halves to even), the latents
+                            are enlarged on the device (upscale_latents: md_latent_resize_f16, no host copy, no VAE round trip), re-noised to
+                            an intermediate timestep, and only the tail of the schedule runs at height x width: pass 2 is
+                            denoise(init_latents=the enlarged latents, strength=hires_strength).  ValueError, before the CLIP tower or the
+                            VAE runs, if a low side is below 64 (self.hires_min_side) or equals the full side, together with video= (pass 2 is itself the
+                            video-to-video pass), and for everything either pass's sampling plan refuses at ITS latent grid (a kv_downsample
+                            or tile_attention factor that fits one grid and not the other: the message names the pass).  Every sampling keyword
+                            goes to both passes unchanged (guides, kv_downsample, tile_attention, deep_cache_*, context_*, eta), except that
+                            FreeInit belongs to pass 1 only (it refuses init_latents) and `strength` is pass 1's (1.0).  Not with
+                            window_parallel / dp (denoise() keeps supporting both).  Image quality on real weights has not been assessed.
+                            NOISE ORDER: prepare_latents draws the low-size noise FIRST, then the full-size noise, both from `generator`;
+                            the per-step draws of eta / SDE follow in pass order.  1 (the default): bitwise the call without the keywords,
+                            the same operator calls and generator draws, nothing allocated
+        hires_strength      finite, in (0, 1): pass 2 runs int(hires_steps * hires_strength) steps, the tail of its schedule
+        hires_mode          "nearest" (nearest-exact), "bilinear" or "bicubic": F.interpolate's rules without antialiasing (ops.latent_resize)
+        hires_steps         pass 2's num_inference_steps before hires_strength cuts it, an integer >= 1; None: num_inference_steps
+        scene_motion_lowres_npy  pass 1's flow (F, 2, H_lo / 8, W_lo / 8).  None: DERIVED from scene_motion_npy (lowres_scene_motion: bilinear
+                            resampling of the full-size flow, x times W_lo / width and y times H_lo / height, the flow being in latent-grid
+                            units).  That is an approximation: the exact flow is camera_to_scene_motion at the low grid with the depth map
+                            resized to it, which mikudance_amd.inference_video computes and passes
+        callback            sees pass 1's steps, then pass 2's: pass 2's k-th kept step arrives as step_i = num_inference_steps + k (the
+                            count goes on across the passes), with latents of the full size; callback_steps thins each pass from its own
+                            first step
+        """
         # context_batch_size: the reference concatenates that many windows along the batch axis (:601-622).  With one window per
         # context batch (every clip of <= context_frames frames, whatever the value) that is the evaluation below; with two or
         # more windows in a batch the reference itself fails at `noise_pred[:, :, c] + pred` (:662, batch 2 vs 2k), so there is
@@ -832,8 +939,25 @@ class MikuDanceVideoPipeline:
                        pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode,
                        seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
                        tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth)
-        self._resolve_plan(self.sampling_plan(num_inference_steps, guidance_scale, video is not None,
-                                              (video_length, (height or 768) // 8, (width or 768) // 8), **loop_kw))
+        hires = self.hires_plan(height or 768, width or 768, num_inference_steps, hires_scale, hires_strength, hires_mode, hires_steps)
+        if hires is None:
+            self._resolve_plan(self.sampling_plan(num_inference_steps, guidance_scale, video is not None,
+                                                  (video_length, (height or 768) // 8, (width or 768) // 8), **loop_kw))
+        else:
+            # two passes, two plans: both are built and resolved here, before the CLIP tower or the VAE runs
+            if video is not None:
+                raise ValueError("video= cannot be combined with hires_scale > 1: pass 2 is itself the video-to-video pass, from pass 1's result")
+            height_lo, width_lo, steps_hi = hires
+            hi_kw = dict(loop_kw, strength=hires_strength, free_init_iters=1)     # FreeInit refuses init_latents: pass 1 only
+            for what, steps, has_init, (hp, wp), kw in ((f"hires pass 1 ({width_lo} x {height_lo})", num_inference_steps, False, (height_lo, width_lo), loop_kw),
+                                                        (f"hires pass 2 ({width or 768} x {height or 768})", steps_hi, True, (height or 768, width or 768), hi_kw)):
+                try:
+                    self._resolve_plan(self.sampling_plan(steps, guidance_scale, has_init, (video_length, hp // 8, wp // 8), **kw))
+                except ValueError as e:
+                    raise ValueError(f"{what}: {e}") from None
+            if scene_motion_lowres_npy is not None and tuple(np.shape(scene_motion_lowres_npy)) != (video_length, 2, height_lo // 8, width_lo // 8):
+                raise ValueError(f"scene_motion_lowres_npy has shape {tuple(np.shape(scene_motion_lowres_npy))}, pass 1 needs "
+                                 f"{(video_length, 2, height_lo // 8, width_lo // 8)}")
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -847,27 +971,31 @@ class MikuDanceVideoPipeline:
         image_prompt_embeds = self.clip_embeds(ref_image)
         if do_cfg:
             image_prompt_embeds = torch.cat([torch.zeros_like(image_prompt_embeds), image_prompt_embeds], dim=0)
-        latents = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width, height,
-                                       video_length, image_prompt_embeds.dtype, device, generator)
-        f = video_length
-        rep = lambda z: z.unsqueeze(1).repeat(1, f, 1, 1, 1).reshape((-1,) + tuple(z.shape[1:]))
-        # all 3F + 2 condition images in ONE pass through the VAE (reference :456-549 encodes them one by one, same arithmetic per image)
-        # (and the video-to-video frames after them, in the same pass; the noise above was drawn first, so the generator stream is unchanged)
-        groups = [list(tgt_pose_images), list(tgt_face_images), list(tgt_hand_images)]
-        lat_all = self._encode_many([_pil_to_tensor(ref_image, height, width, True), _pil_to_tensor(ref_skel_image, height, width, False)]
-                                    + [_pil_to_tensor(im, height, width, False) for grp in groups for im in grp]
-                                    + [_pil_to_tensor(im, height, width, True) for im in ([] if video is None else video)])
-        ref_image_latents, pose_ref_latents = rep(lat_all[0:1]), rep(lat_all[1:2])
-        o = [2]
-        for grp in groups:
-            o.append(o[-1] + len(grp))
-        pose_tgt, face_tgt, hand_tgt = (lat_all[a:b] for a, b in zip(o[:-1], o[1:]))
-        init_latents = None if video is None else lat_all[o[-1]:o[-1] + f].permute(1, 0, 2, 3)[None]     # (1, 4, F, h, w)
-        tracker = torch.from_numpy(np.asarray(scene_motion_npy)).to(dtype=ref_image_latents.dtype, device=ref_image_latents.device)
-        ref_latents = torch.cat([ref_image_latents, pose_ref_latents, pose_tgt, face_tgt, hand_tgt, tracker], dim=1)[None]
-        latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, context_schedule,
-                               context_frames, context_stride, context_overlap, callback, callback_steps, eta=eta, generator=generator,
-                               init_latents=init_latents, **loop_kw)
+        images = (ref_image, ref_skel_image, [list(tgt_pose_images), list(tgt_face_images), list(tgt_hand_images)])
+        noise_args = (video_length, image_prompt_embeds.dtype, device, generator)
+        window_args = (context_schedule, context_frames, context_stride, context_overlap)
+        if hires is None:
+            latents = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width, height, *noise_args)
+            # (the noise is drawn before the video-to-video frames are encoded, so the generator stream does not depend on video=)
+            ref_latents, init_latents = self._condition_latents(*images, video, scene_motion_npy, height, width, video_length)
+            latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, *window_args, callback,
+                                   callback_steps, eta=eta, generator=generator, init_latents=init_latents, **loop_kw)
+        else:
+            # the noise of the low size FIRST, then of the full size (the order the docstring states); the images of each size through the VAE
+            # in batches of their own; the CLIP embeddings above serve both passes
+            noise_lo = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width_lo, height_lo, *noise_args)
+            noise = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width, height, *noise_args)
+            motion_lo = scene_motion_lowres_npy
+            if motion_lo is None:
+                motion_lo = self.lowres_scene_motion(scene_motion_npy, height_lo // 8, width_lo // 8)
+            ref_latents_lo, _ = self._condition_latents(*images, None, motion_lo, height_lo, width_lo, video_length)
+            ref_latents, _ = self._condition_latents(*images, None, scene_motion_npy, height, width, video_length)
+            latents = self.denoise(noise_lo, ref_latents_lo, image_prompt_embeds, num_inference_steps, guidance_scale, *window_args, callback,
+                                   callback_steps, eta=eta, generator=generator, init_latents=None, **loop_kw)
+            latents = self.upscale_latents(latents, height, width, hires_mode)
+            callback_hi = None if callback is None else (lambda i, t, x: callback(num_inference_steps + i, t, x))
+            latents = self.denoise(noise, ref_latents, image_prompt_embeds, steps_hi, guidance_scale, *window_args, callback_hi,
+                                   callback_steps, eta=eta, generator=generator, init_latents=latents, **hi_kw)
         if interpolation_factor > 0:
             latents = self.interpolate_latents(latents, interpolation_factor, device)
         images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)
