@@ -14,6 +14,8 @@ from parity_budget import check_kernel  # noqa: E402
 from mikudance_amd import ops, packing  # noqa: E402
 from oracle import cpu_ref as O  # noqa: E402
 
+from elementwise_ref import G_PAG, U16, _ddim64, _v64  # noqa: E402  (the float64 step statements; _v64 at scale 0 is the guided v at G_PAG)
+
 
 @pytest.fixture(scope="module")
 def dev():
@@ -404,6 +406,11 @@ def test_window_accumulate_and_ddim(dev):
     latd = lat.to(dev).clone()
     ops.cfg_ddim_step(latd, noise, cnt, Ftot, HW, 3.5, a_t, a_prev)
     close(latd, ref, rtol=2e-3, atol=2e-3, what="ddim")
+    # ... and to the step error model against float64 (tests/elementwise_ref.py), from the sums the device accumulated
+    ns = noise.cpu()
+    assert G_PAG == 3.5                                                    # the guidance _v64 is written with
+    want, scale = _ddim64(lat, *_v64(ns, ns[1], ref_cnt, 2, 0.0), a_t, a_prev, 0.0, None)
+    assert ((latd.cpu().double() - want).abs() <= U16 * want.abs() + 2e-6 * scale + 2.0 ** -24).all()
 
 
 # --------------------------------------------------------------------------------------------- benchmark / configs[4] sizes
@@ -662,3 +669,6 @@ def test_eta_ddim_kernel(dev):
     l = lat.to(dev).clone()
     ops.cfg_ddim_step(l, ns.to(dev), cnt.to(dev), Ft, HW, gs, a_t, a_prev, eta=eta, variance_noise=z.to(dev))
     close(l, want, rtol=2e-3, what="ddim eta")
+    assert gs == G_PAG                                                     # the guidance _v64 is written with
+    want, scale = _ddim64(lat, *_v64(ns, ns[1], cnt, 2, 0.0), a_t, a_prev, eta, z)      # the step error model against float64
+    assert ((l.cpu().double() - want).abs() <= U16 * want.abs() + 2e-6 * scale + 2.0 ** -24).all()
