@@ -311,6 +311,23 @@ int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, const void* 
                               const void* perturbed_sum, int Ftot, int HW, int halves, float guidance, float pag_scale, float alpha_s,
                               float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
 
+/* The unconditional plane of a sampling step that evaluated the conditional half only (guidance_interval= after Kynkaanniemi et al.,
+ * "Applying Guidance in a Limited Interval", arXiv 2404.07724; uncond_cache_interval= after the CFG cache of FasterCache, arXiv 2410.19355,
+ * the idea only): an opt-in approximation, between src/pipelines/pipeline_mikudance.py:662-668 (the windows) and :670-678 (CFG + step).
+ * noise_sum: the fp32 accumulator [2][Ftot][HW][4] with planes [u, c] as the halves == 2 step entries read it; counter: fp32 [Ftot];
+ * delta: fp32 [Ftot][HW][4], kept by the caller between steps.
+ *   mode 0 (store):    delta = c_sum / cnt - u_sum / cnt per frame with that frame's counter; noise_sum is not written
+ *   mode 1 (restore):  u_sum = c_sum - scale delta cnt; writes the u plane only.  scale 1: the step kernels then see c - u = delta, so their
+ *                      u + g (c - u) is c + (g - 1) delta.  scale 0 (no guidance at this step): the product is not formed, delta is not
+ *                      read and may be NULL, u_sum = c_sum bit for bit, so the guided v is exactly the conditional mean
+ * fp32, each operation rounded on its own (no fma), in this order -- store: inv = 1 / cnt, u = u_sum inv, c = c_sum inv (the step kernels'
+ * own u and c), delta = c - u; restore: t = delta cnt, t = scale t, u_sum = c_sum - t.  Every rank of a window-parallel run, holding the
+ * same planes after the all-reduce, gets the same bits.  Deterministic, no atomics.  A frame whose counter is 0 is NaN to the step kernels
+ * (0 * (1 / 0)) and gets no special case here either: store writes NaN, restore with scale != 0 hands it on.
+ * NULL noise_sum / counter, NULL delta unless mode 1 with scale == 0, Ftot <= 0, HW <= 0, mode not 0 or 1, a non-finite scale, noise_sum or
+ * delta not 16-byte or counter not 4-byte aligned: MD_ERR_ARG, with nothing launched and every buffer untouched. */
+int md_cfg_uncond_cache(void* noise_sum, const void* counter, void* delta, int Ftot, int HW, int mode, float scale, void* stream);
+
 /* Forward noising of a clean latent, the start of video-to-video sampling (`strength` < 1): latents = fp16(a x0 + b latents), computed in
  * fp32, in place, over n fp16 elements.  latents holds the N(0, 1) noise on entry; x0 is the clean VAE latent (already scaled by 0.18215),
  * both packed to the (F, h*w, 4) layout of md_pack_nhwc_f16.  a = sqrt(abar_t), b = sqrt(1 - abar_t) of the first kept timestep, computed by

@@ -173,7 +173,15 @@ __device__ __forceinline__ T guided_v(const T* __restrict__ ns, const float* __r
   T v = ns[i] * inv;
   if (halves == 2) {
     const T c = ns[total + i] * inv;
-    v = v + guidance * (c - v);
+    T d;
+    {
+      // c is a finished (rounded) value when it is subtracted, as the order above says: contracted, c - v became fma(sum_c, inv, -v), which
+      // leaves the rounding error of one product where sum_c == sum_u bit for bit (md_cfg_uncond_cache, mode 1 with scale 0), and the
+      // guided v of a step without guidance would not be the conditional mean exactly
+#pragma clang fp contract(off)
+      d = c - v;
+    }
+    v = v + guidance * d;
     if (c_out) *c_out = c;
   }
   return v;
@@ -516,6 +524,65 @@ extern "C" int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, c
                                          float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream) {
   return cfg_multistep_launch(latents, noise_sum, counter, history, variance_noise, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
                               stream, step_pag(perturbed_sum, pag_scale), "md_cfg_multistep_step_pag");
+}
+
+// ---- the unconditional plane of a step that did not evaluate it (guidance_interval=, uncond_cache_interval=) ---------------------------
+// A step that runs the conditional evaluation only leaves plane 0 (u) of the accumulator empty.  This kernel fills it so that every
+// consumer of the planes (guided_v and with it both steps, the rescale, APG, PAG / SEG) works unchanged:
+//   mode 0 (store, after a full step's windows):  delta = c_sum / cnt - u_sum / cnt, the guidance direction c - u as guided_v forms it
+//   mode 1 (restore, after a conditional-only step's windows):  u_sum = c_sum - scale delta cnt, so that guided_v's c - u is scale delta
+// Rounding order (fp32, no fma: fp contraction is switched off in the kernel body, every line below is rounded once, in this order, so every
+// rank of a window-parallel run, which holds the same planes after the all-reduce, gets the same bits):
+//   store:    inv = 1 / cnt;  u = u_sum inv;  c = c_sum inv;  delta = c - u            (inv, u, c exactly as guided_v writes them)
+//   restore:  t = delta cnt;  t = scale t  (exact for scale == 1);  u_sum = c_sum - t
+// scale == 0 (a step outside the guidance interval): the product is not formed and delta is not read; u_sum = c_sum bit for bit, so c - u
+// is exactly 0 and the guided v is the conditional mean, whatever delta holds (it may be NULL).
+// A frame whose counter is 0 gets no special case, as in the step kernels: guided_v forms inv = 1 / 0 = Inf and 0 * Inf = NaN for such a
+// frame; here store writes the same NaN into delta, restore with scale != 0 hands it on (NaN * 0) and restore with scale == 0 copies the
+// (zero) c_sum, which the step then turns into NaN itself.  The loop never produces such a frame: every frame lies in a window.
+// Streaming, HBM-bound: one thread owns one pixel per round (16-byte loads and stores), grid-stride with the step kernels' grid cap.
+// Every element is written by exactly one thread: deterministic, no atomics.
+template <int MODE>
+__global__ __launch_bounds__(256) void cfg_uncond_cache_kernel(floatx4* __restrict__ ns, const float* __restrict__ counter,
+                                                               floatx4* __restrict__ delta, int Ftot, int HW, float scale) {
+#pragma clang fp contract(off)
+  const long total = (long)Ftot * HW;  // pixels
+  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const float cnt = counter[(int)(p / HW)];
+    if constexpr (MODE == 0) {
+      const float inv = 1.f / cnt;
+      const floatx4 u = ns[p] * inv;
+      const floatx4 c = ns[total + p] * inv;
+      delta[p] = c - u;
+    } else {
+      floatx4 c = ns[total + p];
+      if (scale != 0.f) {
+        floatx4 t = delta[p] * cnt;
+        t = scale * t;
+        c = c - t;
+      }
+      ns[p] = c;
+    }
+  }
+}
+
+extern "C" int md_cfg_uncond_cache(void* noise_sum, const void* counter, void* delta, int Ftot, int HW, int mode, float scale, void* stream) {
+  MD_CHECK_ARG(Ftot > 0 && HW > 0 && (mode == 0 || mode == 1), "md_cfg_uncond_cache: bad arguments (Ftot, HW > 0, mode 0 = store or 1 = restore)");
+  MD_CHECK_ARG(__builtin_isfinite(scale), "md_cfg_uncond_cache: non-finite scale");
+  MD_CHECK_ARG(noise_sum && counter && (delta || (mode == 1 && scale == 0.f)),
+               "md_cfg_uncond_cache: null pointer (delta may be NULL for mode 1 with scale == 0 only)");
+  MD_CHECK_ARG(((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)delta % 16) == 0 && ((uintptr_t)counter % 4) == 0,
+               "md_cfg_uncond_cache: noise_sum / delta need 16-byte, counter 4-byte alignment");
+  const long total = (long)Ftot * HW;
+  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  if (mode == 0)
+    hipLaunchKernelGGL(cfg_uncond_cache_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (floatx4*)noise_sum, (const float*)counter,
+                       (floatx4*)delta, Ftot, HW, scale);
+  else
+    hipLaunchKernelGGL(cfg_uncond_cache_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (floatx4*)noise_sum, (const float*)counter,
+                       (floatx4*)delta, Ftot, HW, scale);
+  MD_CHECK_LAUNCH("md_cfg_uncond_cache");
+  return MD_OK;
 }
 
 // ---- guidance rescale factor (Lin et al., arXiv 2305.08891 section 3.4; diffusers rescale_noise_cfg) ----------------------------------

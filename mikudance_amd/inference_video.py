@@ -30,6 +30,9 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      (an addition: shifted-tile spatial self-attention, arXiv 2311.17528; default 1 = off)
     pipe(..., deep_cache_interval=--deep_cache_interval, deep_cache_depth=--deep_cache_depth)
                      (an addition: DeepCache, arXiv 2312.00858: the deep part of the denoising UNet every N-th step only; default 1 = off)
+    pipe(..., guidance_interval=--guidance_interval, uncond_cache_interval=--uncond_cache_interval)
+                     (an addition: guidance on a stretch of the schedule only, arXiv 2404.07724, and the unconditional half on every N-th guided
+                     step only, after arXiv 2410.19355; opt-in approximations, image quality on real weights not assessed; defaults 0,1 and 1 = off)
     pipe(..., hires_scale=--hires_scale, hires_strength=--hires_strength, hires_mode=--hires_mode, hires_steps=--hires_steps,
          scene_motion_lowres_npy=camera_to_scene_motion at the first pass's grid)
                      (an addition: two-pass high-resolution sampling, the whole schedule at -W / S x -H / S, the latents enlarged on the GPU,
@@ -70,6 +73,16 @@ def _factors(text):
         return tuple(int(v) for v in text.split(","))
     except ValueError:
         raise argparse.ArgumentTypeError(f"expected comma-separated integers, got {text!r}") from None
+
+
+def _interval(text):
+    """--guidance_interval: "0.1,0.8" -> (0.1, 0.8) (the range is the pipeline's business)."""
+    import argparse
+    try:
+        lo, hi = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected two comma-separated numbers lo,hi, got {text!r}") from None
+    return lo, hi
 
 
 def _layer_names(text):
@@ -166,6 +179,16 @@ def parse_args(argv=None):
     parser.add_argument("--deep_cache_depth", type=int, default=3, metavar="D",
                         help="(addition) DeepCache: how many skip connections, counted from conv_in, the steps between still evaluate "
                              "(this project's own index); 3 = the whole highest-resolution level on both sides")
+    parser.add_argument("--guidance_interval", type=_interval, default=(0.0, 1.0), metavar="LO,HI",
+                        help="(addition) guidance in a limited interval (arXiv 2404.07724), an approximation that saves the unconditional half "
+                             "of the denoising UNet: classifier-free guidance is applied at step k of --steps N only where LO N <= k < HI N, the "
+                             "other steps run on the conditional prediction alone; 0 <= LO <= HI <= 1; 0,1 = off.  Image quality on real "
+                             "weights has not been assessed.  Not with --deep_cache_interval")
+    parser.add_argument("--uncond_cache_interval", type=int, default=1, metavar="N",
+                        help="(addition) reuse of the guidance direction (the CFG cache of FasterCache, arXiv 2410.19355), an approximation: the "
+                             "unconditional half is evaluated on every N-th guided step only, the steps between reuse the last difference "
+                             "between the conditional and the unconditional prediction; 1 = off.  Image quality on real weights has not been "
+                             "assessed.  Not with --deep_cache_interval")
     parser.add_argument("--hires_scale", type=float, default=1.0, metavar="S",
                         help="(addition) two-pass high-resolution sampling, an approximation that saves most full-resolution steps: the whole "
                              "schedule runs at -W / S x -H / S (rounded to multiples of 8), the latents are enlarged on the GPU and re-noised, and "
@@ -286,6 +309,7 @@ def main(argv=None):
                seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma, seg_applied_layers=_layer_names(args.seg_layers),
                tile_attention=args.tile_attention, tile_attention_shift=args.tile_attention_shift,
                deep_cache_interval=args.deep_cache_interval, deep_cache_depth=args.deep_cache_depth,
+               guidance_interval=args.guidance_interval, uncond_cache_interval=args.uncond_cache_interval,
                hires_scale=args.hires_scale, hires_strength=args.hires_strength, hires_mode=args.hires_mode, hires_steps=args.hires_steps,
                scene_motion_lowres_npy=scene_motion_lowres_npy)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)

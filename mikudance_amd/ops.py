@@ -483,6 +483,19 @@ def cfg_multistep_step_pag(latents, noise_sum, counter, history, perturbed_sum, 
               float(pag_scale), float(alpha_s), float(sigma_s), float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
 
 
+def cfg_uncond_cache(noise_sum, counter, delta, ftot, hw, mode, scale=1.0):
+    """The unconditional plane of a step that evaluated the conditional half only (md_cfg_uncond_cache).  noise_sum: fp32 (2, ftot, hw, 4),
+    planes [u, c]; counter: fp32 (ftot,); delta: fp32 (ftot, hw, 4).  mode 0 stores delta = c_sum / cnt - u_sum / cnt; mode 1 restores
+    u_sum = c_sum - scale * delta * cnt in place.  With mode 1 and scale == 0 (no guidance at this step) delta is not read and may be None:
+    u_sum = c_sum bit for bit."""
+    _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32); _chk(delta, "delta", torch.float32)
+    n = ftot * hw * 4
+    assert noise_sum.is_contiguous() and noise_sum.numel() == 2 * n and counter.numel() >= ftot
+    assert delta is None or (delta.is_contiguous() and delta.numel() == n)
+    _lib.call("md_cfg_uncond_cache", noise_sum.data_ptr(), counter.data_ptr(), _p(delta), ftot, hw, int(mode), float(scale), _st(),
+              meta=(f"cfg_uncond_cache F={ftot} HW={hw} mode={int(mode)}", 0.0, 4.0 * n * (2 if mode == 1 and not scale else 3)))
+
+
 def free_init_mix(out, x0, noise0, z, lpf, a, b):
     """FreeInit's frequency mix (md_free_init_mix_f16): out = fp16(z + IDFT3(lpf * DFT3(a x0 + b noise0 - z))) per channel over (F, H, W).
     out / x0 / noise0 / z: contiguous (F, H, W, 4) fp16, out may be x0; lpf: contiguous (F, H, W) fp32, unshifted order

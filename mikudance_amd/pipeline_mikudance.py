@@ -85,6 +85,7 @@ class SamplingPlan:
     guide: Union[None, Rescale, APG, Perturb]      # None: plain (u + g (c - u), or c without CFG)
     tile: Union[None, tuple] = None                # None: no tiled self-attention; (factors, shift), resolved: (UNet3DConditionModel.tile_attention_plan, shift)
     deep: Union[None, tuple] = None                # None: deep_cache_interval == 1, no DeepCache; (interval N, depth d), d checked against the UNet by _resolve_plan
+    uncond: Union[None, tuple] = None              # None: guidance on every step from a full evaluation (the defaults, or no CFG); (lo, hi, n) of guidance_interval / uncond_cache_interval
 
 
 # the step forms v in ONE way: (asked for, beside, why not), in the order the refusals are made
@@ -166,7 +167,8 @@ class MikuDanceVideoPipeline:
                 free_init_filter="butterworth", free_init_order=4, free_init_spatial_stop=0.25, free_init_temporal_stop=0.25,
                 free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
                 pag_applied_layers=("mid",), kv_downsample=1, kv_downsample_mode="nearest", seg_scale=0.0, seg_blur_sigma=100.0,
-                seg_applied_layers=("mid",), tile_attention=1, tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3):
+                seg_applied_layers=("mid",), tile_attention=1, tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3,
+                guidance_interval=(0.0, 1.0), uncond_cache_interval=1):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -335,6 +337,37 @@ class MikuDanceVideoPipeline:
                             list of a whole cache period is therefore the key step's.  This loop calls the window scheduler once, with index 0,
                             for every step (as the oracle does), so that holds by construction; a loop that moved its windows per step
                             would have to hold them still over each period
+        guidance_interval   (lo, hi), two finite numbers with 0 <= lo <= hi <= 1 (Kynkaanniemi et al., "Applying Guidance in a Limited Interval",
+                            arXiv 2404.07724; the start / stop of diffusers' ClassifierFreeGuidance guider), an opt-in APPROXIMATION that trades
+                            accuracy for time: classifier-free guidance is applied at schedule index k = t_start + step_i (video-to-video keeps the
+                            indices of the steps it keeps; every FreeInit pass counts from 0, against the number of steps of ITS schedule) of an
+                            N-step schedule iff lo N <= k < hi N.  At every other step ("off") the denoising UNet evaluates the conditional
+                            clip-half only -- forward_nhwc(conditional=True) on the window's conditional frames, the unperturbed twin of PAG's
+                            evaluation and the conditional queue of two_queues, launch for launch -- its prediction is accumulated into the c plane
+                            with the real counter, and after the all-reduce ops.cfg_uncond_cache(mode 1, scale 0) copies the c plane over the u
+                            plane, so that c - u is exactly 0 and every step entry, the rescale, APG and PAG / SEG work on the planes unchanged:
+                            the guided v is the conditional mean.  A STATED DEVIATION: outside the interval the loop stays in CFG form, so the
+                            step sees the window MEAN of c, where a guidance_scale <= 1 call under context_fuse="flat" hands the scheduler the
+                            window sum (see context_fuse).  The reference banks are written for both halves as always, i.e. with the
+                            reference's interleaved [u, c, u, c, ...] contexts over the frames: the conditional half of a CFG run is therefore
+                            not the prediction of a run without CFG, with or without this keyword.  Checked whether or not
+                            guidance is on; inert (no call, no buffer) with guidance_scale <= 1.  Image quality on real weights has not been
+                            assessed.  (0.0, 1.0) (the default): bitwise the loop without the keyword, the same operator calls, no buffer
+        uncond_cache_interval  an integer n >= 1 (the CFG cache of FasterCache, arXiv 2410.19355: the idea only), an opt-in APPROXIMATION: inside the
+                            guidance interval the unconditional half is evaluated on every n-th step only.  A step inside the interval is FULL
+                            when no guidance direction has been stored since the pass began (or since the interval was entered) or n steps
+                            have passed since the last full step: today's two-half evaluation, after which (and after the all-reduce)
+                            ops.cfg_uncond_cache(mode 0) stores d = c - u, one fp32 (F, h*w, 4) buffer per call, allocated only when n > 1.
+                            Every other step inside the interval is CACHED: the conditional-only evaluation, then
+                            ops.cfg_uncond_cache(mode 1, scale 1) writes u_sum = c_sum - d cnt, so that the step forms c + (g - 1) d_last in
+                            place of u + g (c - u).  The kind of a step is decided on the host from integers: no sync.  PAG's / SEG's
+                            evaluation is made on all three kinds.  Composes with both samplers, eta / SDE noise, init_latents / strength, every
+                            window schedule and fuse mode, FreeInit (every pass starts with an empty cache), guidance_rescale, APG, PAG / SEG
+                            (they read the restored planes), kv_downsample, tile_attention and window_parallel (the restore runs after the
+                            all-reduce, replicated: every rank holds an identical d, no new collective).  ValueError, before anything runs,
+                            together with deep_cache_interval > 1 (a DeepCache slot is shaped by the batch of the evaluation that filled it; a
+                            conditional-only step would meet a slot of the other shape), for this keyword and for guidance_interval alike.
+                            Image quality on real weights has not been assessed.  1 (the default): as for guidance_interval
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         plan = self.sampling_plan(
@@ -344,7 +377,8 @@ class MikuDanceVideoPipeline:
             apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
             pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode, seg_scale=seg_scale,
             seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
-            tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth)
+            tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth,
+            guidance_interval=guidance_interval, uncond_cache_interval=uncond_cache_interval)
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         ops.require_gpu(latents, "MikuDanceVideoPipeline.denoise")
@@ -415,7 +449,12 @@ class MikuDanceVideoPipeline:
                 assert key, f"DeepCache: no slot for window {wi}, plane {plane} at a shallow step"
                 slot = dc_slots[(wi, plane)] = DeepCacheSlot(plan.deep[1])
             return dict(deep_cache=slot.fill() if key else slot.reuse())
-        windows = [list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
+        # guidance interval / cached unconditional half: d = c - u of the last full step, kept only when some step reuses it; no plan: no buffer,
+        # no new call.  Under window_parallel every rank keeps its own identical copy (written after the all_reduce)
+        uc_delta = None
+        if plan.uncond is not None and plan.uncond[2] > 1:
+            uc_delta = torch.empty((F_, HW, 4), device=dev, dtype=torch.float32)
+        windows =[list(w) for w in get_context_scheduler(context_schedule)(0, num_inference_steps, F_, context_frames,
                                                                             context_stride, context_overlap)]
         mm_len = getattr(den, "temporal_position_encoding_max_len", None)
         if mm_len is not None and max(len(w) for w in windows) > mm_len:
@@ -485,6 +524,7 @@ class MikuDanceVideoPipeline:
                     apg_m.zero_()                                        # the running average starts over with every pass
                 if dc_slots is not None:
                     dc_slots.clear()                                     # every pass starts at k = 0 with an empty cache
+                uc_since = None                                          # steps since the last full step; None: no d stored (in this pass / interval)
                 for step_i, t in enumerate(timesteps):
                     noise_sum.zero_()
                     counter.zero_()
@@ -492,6 +532,17 @@ class MikuDanceVideoPipeline:
                     # tiled self-attention: the main and the perturbed evaluation of a step share the plan and the step's shift
                     sa_kw = kv_kw if tile_plan is None else dict(kv_kw, tile_attention=tile_plan, tile_shift=tile_shift_at(tile_shift, t_start + step_i))
                     dc_key = plan.deep is None or step_i % plan.deep[0] == 0      # k counts the steps this pass actually runs
+                    # the step's kind, from integers on the host: "full" (both clip-halves, today's step), "off" (outside the guidance interval)
+                    # or "cached" (inside it, on the last full step's d); the last two evaluate the conditional clip-half only
+                    kind = "full"
+                    if plan.uncond is not None:
+                        gi_lo, gi_hi, uc_n = plan.uncond
+                        if not gi_lo * fi_steps[fi] <= t_start + step_i < gi_hi * fi_steps[fi]:
+                            kind, uc_since = "off", None
+                        elif uc_since is None or uc_since + 1 >= uc_n:
+                            uc_since = 0
+                        else:
+                            kind, uc_since = "cached", uc_since + 1
                     for wi, win in enumerate(windows):
                         if window_parallel is not None and not window_parallel.mine(wi):
                             continue                                         # another rank's window (its share arrives in the all_reduce)
@@ -511,9 +562,15 @@ class MikuDanceVideoPipeline:
                         cross = den._cross(embeds[:nb], [i // f for i in range(nb * f)], dev)
                         # both clip-halves are packed from the SAME latents (batch stride 0 above): the layers in front of the first attention
                         # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
-                        pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
-                                                two_queues=self.two_queues, **sa_kw, **deep_kw(wi, 0, dc_key))
-                        accumulate(pred, ns_main, counter, wi, nb)
+                        if kind == "full":
+                            pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
+                                                    two_queues=self.two_queues, **sa_kw, **deep_kw(wi, 0, dc_key))
+                            accumulate(pred, ns_main, counter, wi, nb)
+                        else:
+                            # ---- the conditional frames only (PAG's call below without its perturbation), into the c plane with the real counter;
+                            # the u plane stays empty until cfg_uncond_cache fills it
+                            pred = den.forward_nhwc(x[f:], 1, f, torch.full((1,), float(t)), cross.rows(f, 2 * f), conditional=True, **sa_kw)
+                            accumulate(pred, ns_main[1:], counter, wi, 1)
                         if s_t > 0.0:
                             # ---- PAG / SEG: the conditional frames once more (the banks are still in place), the selected self-attention maps
                             # = identity / from blurred queries
@@ -524,6 +581,13 @@ class MikuDanceVideoPipeline:
                         writer.clear()
                     if window_parallel is not None:
                         window_parallel.reduce(noise_sum, counter)
+                    # the planes as every consumer below expects them (replicated on every rank, after the all_reduce: no new collective)
+                    if kind == "off":
+                        ops.cfg_uncond_cache(ns_main, counter, None, F_, HW, 1, scale=0.0)       # u_sum = c_sum: c - u == 0 exactly
+                    elif kind == "cached":
+                        ops.cfg_uncond_cache(ns_main, counter, uc_delta, F_, HW, 1, scale=1.0)   # u_sum = c_sum - d cnt
+                    elif uc_delta is not None:
+                        ops.cfg_uncond_cache(ns_main, counter, uc_delta, F_, HW, 0)              # a full step: d = c - u for the steps behind it
                     step(step_i, t, s_t)
                     if callback is not None and step_i % callback_steps == 0:
                         callback(step_i, t, self._latents_out(lat, latents))
@@ -542,7 +606,7 @@ class MikuDanceVideoPipeline:
                       free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop, free_init_fast, apg, apg_eta,
                       apg_norm_threshold, apg_momentum, pag_scale, pag_adaptive_scale, pag_applied_layers, kv_downsample, kv_downsample_mode,
                       seg_scale, seg_blur_sigma, seg_applied_layers, tile_attention=1, tile_attention_shift="cycle", deep_cache_interval=1,
-                      deep_cache_depth=3):
+                      deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1):
         """Every refusal of denoise()'s sampling keywords (see its docstring) that needs no model -- every value is checked whether or not its
         feature is on, and neither UNet is called -- then what they resolve to -> SamplingPlan, still holding the layer names and the
         (factors, mode) that _resolve_plan hands to the denoising UNet.  has_init: there is a clip to start from (init_latents / video);
@@ -614,6 +678,20 @@ class MikuDanceVideoPipeline:
         for name, v in (("deep_cache_interval", deep_cache_interval), ("deep_cache_depth", deep_cache_depth)):
             if not isinstance(v, numbers.Integral) or isinstance(v, bool) or v < 1:
                 raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        try:
+            gi = tuple(guidance_interval)
+            gi_lo, gi_hi = (float(v) for v in gi)
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_interval must be two finite numbers (lo, hi) with 0 <= lo <= hi <= 1, got {guidance_interval!r}") from None
+        if any(isinstance(v, (bool, str)) for v in gi) or not (math.isfinite(gi_lo) and math.isfinite(gi_hi) and 0.0 <= gi_lo <= gi_hi <= 1.0):
+            raise ValueError(f"guidance_interval must be two finite numbers (lo, hi) with 0 <= lo <= hi <= 1, got {guidance_interval!r}")
+        if not isinstance(uncond_cache_interval, numbers.Integral) or isinstance(uncond_cache_interval, bool) or uncond_cache_interval < 1:
+            raise ValueError(f"uncond_cache_interval must be an integer >= 1, got {uncond_cache_interval!r}")
+        skips_uncond = (gi_lo, gi_hi) != (0.0, 1.0) or uncond_cache_interval > 1
+        if skips_uncond and deep_cache_interval > 1:
+            raise ValueError("guidance_interval / uncond_cache_interval cannot be combined with deep_cache_interval > 1: a DeepCache slot is shaped by "
+                             "the batch of the evaluation that filled it (both clip-halves), and a conditional-only step would meet a slot of the "
+                             "other shape")
         guide = None
         if pag_s > 0.0:
             guide = Perturb("identity", pag_s, pag_a, pag_names, None)
@@ -626,7 +704,8 @@ class MikuDanceVideoPipeline:
         return SamplingPlan(context_fuse, (free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop,
                                            free_init_fast), strength, (kv_factors, kv_mode) if any(f > 1 for f in kv_factors) else None, guide,
                             (tile_factors, tile_shift) if any(f > 1 for f in tile_factors) else None,
-                            (int(deep_cache_interval), int(deep_cache_depth)) if deep_cache_interval > 1 else None)
+                            (int(deep_cache_interval), int(deep_cache_depth)) if deep_cache_interval > 1 else None,
+                            (gi_lo, gi_hi, int(uncond_cache_interval)) if skips_uncond and guidance_scale > 1.0 else None)
 
     def _resolve_plan(self, plan):
         """The refusals only the denoising UNet can make (a layer name that selects no block, more factors than levels, a level without
@@ -891,8 +970,8 @@ class MikuDanceVideoPipeline:
                  free_init_temporal_stop=0.25, free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0,
                  pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), kv_downsample=1,
                  kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), tile_attention=1,
-                 tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3, hires_scale=1, hires_strength=0.5,
-                 hires_mode="bicubic", hires_steps=None, scene_motion_lowres_npy=None, **kwargs):
+                 tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1,
+                 hires_scale=1, hires_strength=0.5, hires_mode="bicubic", hires_steps=None, scene_motion_lowres_npy=None, **kwargs):
         """The reference call (src/pipelines/pipeline_mikudance.py:362-704) with denoise()'s sampling keywords (see its docstring), and:
 
         hires_scale         two-pass high-resolution sampling (the "hires fix" of the SD-1.5 front ends), an opt-in APPROXIMATION of the
@@ -904,7 +983,8 @@ class MikuDanceVideoPipeline:
                             VAE runs, if a low side is below 64 (self.hires_min_side) or equals the full side, together with video= (pass 2 is itself the
                             video-to-video pass), and for everything either pass's sampling plan refuses at ITS latent grid (a kv_downsample
                             or tile_attention factor that fits one grid and not the other: the message names the pass).  Every sampling keyword
-                            goes to both passes unchanged (guides, kv_downsample, tile_attention, deep_cache_*, context_*, eta), except that
+                            goes to both passes unchanged (guides, kv_downsample, tile_attention, deep_cache_*, guidance_interval and
+                            uncond_cache_interval -- each pass against its own schedule --, context_*, eta), except that
                             FreeInit belongs to pass 1 only (it refuses init_latents) and `strength` is pass 1's (1.0).  Not with
                             window_parallel / dp (denoise() keeps supporting both).  Image quality on real weights has not been assessed.
                             NOISE ORDER: prepare_latents draws the low-size noise FIRST, then the full-size noise, both from `generator`;
@@ -938,8 +1018,9 @@ class MikuDanceVideoPipeline:
                        apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
                        pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode,
                        seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
-                       tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth)
-        hires = self.hires_plan(height or 768, width or 768, num_inference_steps, hires_scale, hires_strength, hires_mode, hires_steps)
+                       tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth,
+                       guidance_interval=guidance_interval, uncond_cache_interval=uncond_cache_interval)
+        hires =self.hires_plan(height or 768, width or 768, num_inference_steps, hires_scale, hires_strength, hires_mode, hires_steps)
         if hires is None:
             self._resolve_plan(self.sampling_plan(num_inference_steps, guidance_scale, video is not None,
                                                   (video_length, (height or 768) // 8, (width or 768) // 8), **loop_kw))

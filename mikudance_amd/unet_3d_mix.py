@@ -588,8 +588,12 @@ class UNet3DConditionModel(_UNetBase):
 
     # ------------------------------------------------------------------------------------------ internal NHWC forward
     def forward_nhwc(self, x, nb, f, timesteps, cross, halves_identical=False, two_queues=False, pag=None, kv_downsample=None, seg=None,
-                     tile_attention=None, tile_shift=0, deep_cache=None):
+                     tile_attention=None, tile_shift=0, deep_cache=None, conditional=False):
         """x: (nb*f, h, w, 64) fp16 (4 latent channels, zero padded); returns pred tokens [(nb*f*h*w), 4].
+        conditional: this call holds the CONDITIONAL clip-half of a classifier-free-guidance batch only (a sampling step that skips the
+        unconditional half: guidance_interval= / uncond_cache_interval=): nb must be 1, x the conditional frames, cross their context
+        (rows(f, 2f) of the batch's), and every row reads the bank -- blocks.SelfAttnCall(half=1), the conditional queue of a two_queues
+        call, launch for launch.  The unperturbed twin of pag= / seg=: not together with them, two_queues or halves_identical.
         pag: None, or the blocks of pag_blocks(): this call is then the PERTURBED evaluation of perturbed-attention guidance, a call of its own
         beside the main one: nb must be 1, x the conditional frames, cross their context (the main call's context or its rows(f, 2f): the
         cached K / V projections are shared, nothing of the main call is touched).  Not with two_queues: one clip-half has nothing to run beside.
@@ -615,7 +619,11 @@ class UNet3DConditionModel(_UNetBase):
         two_queues (with halves_identical): behind those shared layers the unconditional and the conditional half are independent all the way
         to the output (per-image GroupNorm, per-row attention and LayerNorm, per-clip-half temporal attention: src/models/unet_3d_mix.py:
         418-598, src/models/mutual_mix_attention.py:173-201), and they are evaluated as TWO KERNEL QUEUES (_forward_two_queues)."""
-        sa = SelfAttnCall(identity=pag, blur=seg, pool=kv_downsample and self._per_block(kv_downsample, x.shape[1], x.shape[2]),
+        if conditional and (nb != 1 or two_queues or halves_identical or pag is not None or seg is not None):
+            raise ValueError("forward_nhwc: conditional=True is one unperturbed clip-half on one queue: nb == 1, no two_queues, no halves_identical, "
+                             "no pag / seg")
+        sa = SelfAttnCall(half=1 if conditional else None, identity=pag, blur=seg,
+                          pool=kv_downsample and self._per_block(kv_downsample, x.shape[1], x.shape[2]),
                           tile=tile_attention and self._tile_pairs(tile_attention, x.shape[1], x.shape[2], int(tile_shift) % 4))
         if sa.perturbed and (nb != 1 or two_queues or halves_identical):
             raise ValueError(f"forward_nhwc: the perturbed evaluation ({'pag' if seg is None else 'seg'}=) is one clip-half on one queue: "
