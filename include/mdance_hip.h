@@ -40,6 +40,8 @@ const char* md_last_error(void);
 
 /* C[M,N] = epi(A[M,K] . W[N,K]^T): bias[N], act, rowadd[(m / rows_per_group)][n] (time-embedding broadcast),
  * residual[M,N] (added last), or transpose_out (C is [N][ldc], used for V^T).  K % 64 == 0.
+ * act is one of MD_ACT_*: any other value is MD_ERR_ARG with nothing launched (the conv entries likewise, which also refuse
+ * MD_ACT_GEGLU).  The transposed store writes columns [0, M) of each of the N rows and leaves columns [M, ldc) untouched.
  * Replaces nn.Linear / 1x1 Conv2d: diffusers Attention.to_q/to_k/to_v/to_out.0 and FeedForward
  * (src/models/attention.py:109-157,323-364), proj_in/proj_out (src/models/transformer_3d.py:66-68,96-98;
  * src/models/transformer_2d.py:152-154,186-188; src/models/motion_module.py:124,146), conv_shortcut and
@@ -161,7 +163,12 @@ int md_instnorm_spade_ld_f16(const void* x, int ldx, const void* gamma_beta, voi
  * of every K batch and the same columns of Vt must be readable; the V^T columns are fetched.  Pad contents may be any FINITE values and do
  * not influence the result (the scores of keys >= Lk are masked, P is exactly +0 there and 0 x finite = 0: two runs that differ only in
  * the pad give the same bits, tests/test_attention_flavours_gpu.py).  Non-finite pad values are not supported: 0 x Inf is NaN in the
- * matrix core.  The pipeline's pad is exact zeros (zero context rows through a bias-free to_v: V = 0 . W). */
+ * matrix core.  The pipeline's pad is exact zeros (zero context rows through a bias-free to_v: V = 0 . W).
+ * The generic kernel (plan 400: any of those conditions missing, e.g. kv_stride = Lk = 257 with ldvt = 264 as the CLIP vision tower calls
+ * it) has NO pad: it reads rows [0, Lk) of every K batch and columns [kb kv_stride, kb kv_stride + Lk) of Vt and nothing else -- whole
+ * 16-byte chunks only where all 8 keys are < Lk, single elements under `key < Lk` otherwise.  Columns of Vt beyond Lk (the slack of a
+ * row pitch ldvt > kv_stride that md_gemm_f16's transposed store leaves unwritten) may hold anything, NaN and Inf included, and need
+ * not be initialised: a NaN-filled slack gives the bits of a zero one (tests/test_attention_flavours_gpu.py). */
 int md_attention_fwd_f16(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O, int ldo,
                          const int* kv_index, int B, int H, int D, int Lq, int Lk, int kv_stride, float scale,
                          void* stream);

@@ -182,8 +182,9 @@ class CLIPVisionTransformer(_Packed):
         cls_row = (e.class_embedding.detach().to(device=dev, dtype=torch.float32) + pos[0]).to(torch.float16)
         return dict(wp=wp, kp=kp, k=k, pos=pos[1:].to(torch.float16).contiguous(), cls=cls_row)
 
-    def forward_tokens(self, pixel_values):
-        """pixel_values (1, 3, S, S) -> last_hidden_state tokens [n_tokens, C] fp16 (after pre_layrnorm and all layers)."""
+    def embed_tokens(self, pixel_values, out=None):
+        """pixel_values (1, 3, S, S) -> [n_tokens, C] fp16: row 0 fp16(class + pos[0]), rows 1.. patch embedding + position embedding;
+        the input of pre_layrnorm.  out: a contiguous [n_tokens, C] fp16 buffer to fill (every element is written)."""
         pk = self.packed()
         cfg = self.cfg
         if pixel_values.shape[0] != 1:
@@ -196,9 +197,16 @@ class CLIPVisionTransformer(_Packed):
         cols = torch.nn.functional.unfold(pixel_values.to(torch.float16), kernel_size=p, stride=p)[0].t()   # [grid*grid, 3*p*p]
         a = torch.zeros((cols.shape[0], pk["kp"]), device=dev, dtype=torch.float16)
         a[:, :pk["k"]] = cols
-        x = torch.empty((self.n_tokens, cfg.hidden_size), device=dev, dtype=torch.float16)
+        x = torch.empty((self.n_tokens, cfg.hidden_size), device=dev, dtype=torch.float16) if out is None else out
+        assert tuple(x.shape) == (self.n_tokens, cfg.hidden_size) and x.dtype == torch.float16 and x.is_contiguous()
         x[0] = pk["cls"]
         ops.gemm(a, pk["wp"], residual=pk["pos"], out=x[1:])                     # patch embedding + position embedding
+        return x
+
+    def forward_tokens(self, pixel_values):
+        """pixel_values (1, 3, S, S) -> last_hidden_state tokens [n_tokens, C] fp16 (after pre_layrnorm and all layers)."""
+        cfg = self.cfg
+        x = self.embed_tokens(pixel_values)
         x = ops.layernorm(x, self.pre_layrnorm.packed()["w"], self.pre_layrnorm.packed()["b"], eps=cfg.layer_norm_eps)
         for layer in self.encoder.layers:
             x = layer(x, self.n_tokens)

@@ -914,6 +914,9 @@ static int gemm_plan_checked(const GemmParams& p, bool conv, GemmPlan* plan) {
   MD_CHECK_ARG(p.K % 64 == 0, "md_gemm: K=%d must be a multiple of 64 (pad channels when packing)", p.K);
   MD_CHECK_ARG(al16(p.A) && al16(p.W), "md_gemm: A/W must be 16-byte aligned");
   MD_CHECK_ARG(conv || p.lda % 8 == 0, "md_gemm: lda=%d must be a multiple of 8", p.lda);
+  // every kernel tests p.act against the values it knows and treats the rest as "none": an unknown value must not get that far
+  MD_CHECK_ARG(p.act >= ACT_NONE && p.act <= ACT_QUICKGELU && !(conv && p.act == ACT_GEGLU),
+               "md_gemm: act=%d is not an activation of this entry (MD_ACT_NONE .. MD_ACT_QUICKGELU; no GEGLU on a conv)", p.act);
   if (p.act == ACT_GEGLU) {
     MD_CHECK_ARG(p.N % 64 == 0 && !p.transpose_out && !p.residual && !p.rowadd && p.ldc % 8 == 0 && al16(p.C),
                  "md_gemm: GEGLU needs N %% 64 == 0 (N=%d), ldc %% 8 == 0, a 16-byte aligned output and no residual/rowadd/transpose", p.N);

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import gemm_ref as R  # noqa: E402
 from mikudance_amd import _lib, ops, packing  # noqa: E402
 
-NONE, SILU, RELU, GEGLU = ops.ACT_NONE, ops.ACT_SILU, ops.ACT_RELU, ops.ACT_GEGLU
+NONE, SILU, RELU, GEGLU, QGELU = ops.ACT_NONE, ops.ACT_SILU, ops.ACT_RELU, ops.ACT_GEGLU, ops.ACT_QUICKGELU
 # plan code -> (MT, NT, MD_GEMM_SP_NT pin): gemm.hip sp_tiles; the tile is 64 MT rows x 64 NT columns
 TILES = {135: (3, 5, 5), 134: (3, 4, 4), 124: (2, 4, 2), 142: (4, 2, 42), 132: (3, 2, 32)}
 PIN_TO_CODE = {pin: code for code, (_, _, pin) in TILES.items()}
@@ -46,13 +46,16 @@ class cu_limit:
 def _out_buffer(rows, cols, form, dev):
     """(buffer, view the kernel writes).  dense: NaN.  Otherwise 7.0 around the view: slice = [:, 32:32+cols] of cols + 64; mis8 = [:, 4:4+cols]
     of cols + 8 (base 8 bytes off a 16-byte boundary, pitch % 8 == 0); ld4 = [:, :cols] of cols + 4 (pitch % 8 == 4); odd = [:, :cols] of
-    cols + 3; wide8 = [:, :cols] of cols + 8 (the transposed store with ldc_t = M + 8)."""
+    cols + 3; wide8 = [:, :cols] of cols + 8 (the transposed store with ldc_t = M + 8); pad8 = [:, :cols] of roundup8(cols), cols % 8 != 0
+    (the transposed store as the CLIP vision tower asks for it, ldc_t = pad_to(M, 8): every row 16-byte aligned, a ragged tail in each)."""
     if form == "dense":
         buf = torch.full((rows, cols), float("nan"), dtype=torch.float16, device=dev)
         return buf, buf
-    lo, extra = {"slice": (32, 64), "mis8": (4, 8), "ld4": (0, 4), "odd": (0, 3), "wide8": (0, 8)}[form]
+    lo, extra = {"slice": (32, 64), "mis8": (4, 8), "ld4": (0, 4), "odd": (0, 3), "wide8": (0, 8), "pad8": (0, -cols % 8)}[form]
     buf = torch.full((rows, cols + extra), 7.0, dtype=torch.float16, device=dev)
     view = buf[:, lo:lo + cols]
+    if form == "pad8":
+        assert extra > 0 and view.data_ptr() % 16 == 0 and view.stride(0) % 8 == 0
     if form == "mis8":
         assert view.data_ptr() % 16 == 8 and view.stride(0) % 8 == 0
     if form in ("ld4", "odd"):
@@ -237,6 +240,10 @@ def transposed_pinned_cases(dev, code):
         gemm_case(dev, f"transposed M={M} bias", 1000 + code, M, 320, 128, tr=True, seed=11)
         gemm_case(dev, f"transposed M={M}", 1000 + code, M, 320, 128, bias=False, tr=True, seed=11)
         gemm_case(dev, f"transposed M={M} ldc_t=M+8", 1000 + code, M, 320, 192, tr=True, out_form="wide8", seed=12)
+    # M = 257 (the CLIP tower's token count) is the swapped problem's N and no multiple of the 256-column tile: sp_eligible turns the
+    # swapped problem down under either pin (md_gemm_plan_call on the CPU: 303), so the ragged transposed store of gemm_kernel runs here too
+    gemm_case(dev, "transposed M=257 ldc_t=264 leaves the sp kernel", 303, 257, 320, 128, tr=True, out_form="pad8", seed=13)
+    gemm_case(dev, "transposed M=257 ldc_t=257 leaves the sp kernel", 303, 257, 320, 128, tr=True, seed=13)
 
 
 def geglu_sp_cases(dev):
@@ -257,6 +264,17 @@ def transposed_auto_cases(dev):
     gemm_case(dev, "transposed auto 110 tiles K=256", 303, 2816, 1280, 256, tr=True, seed=32)
     gemm_case(dev, "transposed auto 120 tiles K=192", 303, 3072, 1280, 192, tr=True, seed=33)
     gemm_case(dev, "transposed auto 303 ldc_t=M+8", 303, 256, 320, 128, tr=True, out_form="wide8", seed=34)
+
+
+def transposed_ragged_cases(dev):
+    """gemm_kernel's transposed epilogue stores 8 rows m .. m + 7 of one column n as one 16-byte piece of C^T[n]; M % 8 != 0 leaves a last
+    piece of M % 8 elements for the scalar branch (`m + 8 <= p.M` fails), and a row of C^T that is not 16-byte aligned takes the scalar
+    branch for every piece.  M = 257 (ViT-L/14's token count: a tail of ONE element, in the second 256-row tile) and 261 (a tail of five);
+    pitch roundup8(M) as the tower asks for it (ldc_t = pad_to(L, 8); columns [M, pitch) start as 7.0 and must stay 7.0: the epilogue does
+    not write them) and pitch M (odd: only every eighth row of C^T is aligned)."""
+    for M in (257, 261):
+        gemm_case(dev, f"transposed ragged M={M} ldc_t={M + -M % 8}", 303, M, 128, 128, tr=True, out_form="pad8", seed=35)
+        gemm_case(dev, f"transposed ragged M={M} ldc_t={M}", 303, M, 128, 128, tr=True, seed=35)
 
 
 M_STREAM = 32768 + 16 * 7
@@ -319,6 +337,96 @@ def alignment_cases(dev):
     conv_case(dev, "conv output through an odd pitch", 303, 8, 48, 48, 64, 256, out_form="odd", seed=62)
     conv_case(dev, "conv SiLU", 303, 8, 48, 48, 64, 256, act=SILU, seed=62)
     conv_case(dev, "conv ReLU", 303, 8, 48, 48, 64, 256, act=RELU, rowadd=True, seed=62)
+
+
+def quickgelu_cases(dev):
+    """MD_ACT_QUICKGELU (fc1 of the CLIP vision tower's MLP): like SiLU / ReLU it leaves the sp and the streaming kernels, so the automatic
+    dispatch reaches every flavour of gemm_kernel that can carry it.  M = 257 is ragged against the 128-row tile; N = 200: the last group
+    of 8 columns of a row is the scalar path (nv < 8).  The residual must enter AFTER the activation (tests/gemm_ref.py _epilogue), the
+    row term before it."""
+    M, N, K = 257, 200, 128
+    gemm_case(dev, "quickgelu bias", 303, M, N, K, act=QGELU, seed=81)
+    gemm_case(dev, "quickgelu no bias", 303, M, N, K, bias=False, act=QGELU, seed=81)
+    gemm_case(dev, "quickgelu bias + residual", 303, M, N, K, res="dense", act=QGELU, seed=81)
+    gemm_case(dev, "quickgelu bias + row term rpg=97", 303, M, N, K, rowadd=True, act=QGELU, seed=81)
+    gemm_case(dev, "quickgelu output a column slice", 303, M, N, K, act=QGELU, out_form="slice", seed=81)
+    gemm_case(dev, "quickgelu output pitch % 8 = 4", 303, M, N, K, act=QGELU, out_form="ld4", seed=81)
+    gemm_case(dev, "quickgelu 301 bias + residual", 301, 300, 64, 128, res="dense", act=QGELU, seed=82)
+    # 302 takes a plain GEMM from K = 2048 on (gemm_choose_kernel: conv || geglu || K >= 2048): at the shape of `geglu 302` (K = 128) the
+    # call query answers 303 for this activation, at the shape of `302 gemm K=2048 N=1288` it answers 302
+    gemm_case(dev, "quickgelu M=32768+5 N=1024 K=128", 303, 32768 + 5, 1024, 128, act=QGELU, seed=83)
+    gemm_case(dev, "quickgelu 302 K=2048 N=1288", 302, 24064 + 5, 1288, 2048, act=QGELU, seed=83)
+    conv_case(dev, "quickgelu conv Cout=200", 303, 3, 13, 11, 64, 200, act=QGELU, seed=84)
+
+
+QUICKGELU_SCREEN = (-65504.0, -1000.0, -100.0, -60.0, -20.0, -1.0, -0.0, 0.0, 1.0, 20.0, 100.0, 65504.0)
+
+
+def _ordered(t):
+    """fp16 -> integers in the order of the values (both zeros 0): neighbours in fp16 differ by 1."""
+    bits = t.view(torch.int16).to(torch.int32) & 0xFFFF
+    return torch.where(bits < 0x8000, bits, 0x8000 - bits)
+
+
+def quickgelu_screen(dev, code, M, N, K):
+    """A = 0: every output element is quickgelu(bias[n]).  The kernel forms v / (1 + exp(-1.702 v)); from v <= -52.2 on the exponential is
+    beyond fp32 (exp(88.7)) and must come out as +Inf so that the quotient is a ZERO -- a NaN (Inf / Inf, 0 x Inf) or a flush of the
+    denominator would show here and in no random case (|pre-activation| < 6 there).  Finite everywhere, within one fp16 ulp of
+    fp16(float64 x sigmoid(1.702 x)), magnitude 0 for every bias <= -60; three launches with identical bits."""
+    a = torch.zeros(M, K, dtype=torch.float16, device=dev)
+    w = R.rnd(N, K, seed=8501, scale=K ** -0.5).to(dev)
+    bias = torch.tensor([QUICKGELU_SCREEN[n % len(QUICKGELU_SCREEN)] for n in range(N)], dtype=torch.float16, device=dev)
+    name = f"quickgelu exact screen {M}x{N} [{code}]"
+    outs = []
+    for _ in range(3):
+        out = torch.full((M, N), float("nan"), dtype=torch.float16, device=dev)
+        got = ops.gemm_plan(a, w, bias=bias, act=QGELU, out=out)
+        assert got == code, f"{name}: the plan query says {got}, the case is written for {code}"
+        ops.gemm(a, w, bias=bias, act=QGELU, out=out)
+        outs.append(out)
+    torch.cuda.synchronize()
+    for o in outs[1:]:
+        assert torch.equal(o.view(torch.int16), outs[0].view(torch.int16)), f"{name}: two runs on the same inputs differ"
+    out = outs[0]
+    b64 = bias.double()
+    want = (b64 * torch.sigmoid(1.702 * b64)).half()
+    ulps = (_ordered(out) - _ordered(want)[None, :]).abs()
+    print(f"PARITY_MEASURE gemm_flavour:{name} floor=1ulp got={int(ulps.max())}ulp nonfinite={int((~torch.isfinite(out)).sum())}", flush=True)
+    assert bool(torch.isfinite(out).all()), f"{name}: non-finite output in columns {sorted(set((~torch.isfinite(out)).nonzero()[:, 1].tolist()))[:12]}"
+    assert int(ulps.max()) <= 1, f"{name}: {int(ulps.max())} fp16 ulps from quickgelu(bias)"
+    assert bool((out[:, bias <= -60.0] == 0).all()), f"{name}: a bias <= -60 must give a zero"
+    assert torch.equal(out[:, bias == 65504.0], torch.full_like(out[:, bias == 65504.0], 65504.0)), f"{name}: quickgelu(65504) is 65504"
+    _count[0] += 1
+
+
+def quickgelu_screen_cases(dev):
+    quickgelu_screen(dev, 303, 257, 200, 128)
+    quickgelu_screen(dev, 301, 300, 64, 128)
+
+
+def refused_act_case(dev):
+    """An `act` that is none of MD_ACT_*: MD_ERR_ARG from the launch and from both call queries, nothing launched, the output untouched
+    (before the check existed such a value ran as MD_ACT_NONE).  MD_ACT_GEGLU on a conv likewise."""
+    lib = _lib.load()
+    M, N, K = 257, 200, 128
+    a, w, b = R.rnd(M, K, seed=8601).to(dev), R.rnd(N, K, seed=8602).to(dev), R.rnd(N, seed=8603).to(dev)
+    st = torch.cuda.current_stream().cuda_stream
+    for act in (5, -1, 255):
+        out = torch.full((M, N), 7.0, dtype=torch.float16, device=dev)
+        args = (a.data_ptr(), K, w.data_ptr(), out.data_ptr(), N, M, N, K, b.data_ptr(), None, 0, None, 0, 0, act, 0)
+        assert lib.md_gemm_plan_call(*args, None, None) == -1, act                     # MD_ERR_ARG
+        assert lib.md_gemm_f16(*args, st) == -1 and b"act=" in lib.md_last_error(), act
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()), f"act={act}: refused, but the output was written"
+    x, wc = R.rnd(3, 13, 11, 64, seed=8604).to(dev), R.rnd(200, 576, seed=8605).to(dev)
+    for act in (5, GEGLU):
+        y = torch.full((3, 13, 11, 200), 7.0, dtype=torch.float16, device=dev)
+        args = (x.data_ptr(), 64, wc.data_ptr(), y.data_ptr(), 200, 3, 13, 11, 64, 200, 3, 1, 0, 1, b.data_ptr(), None, 0, None, 0, 0, act)
+        assert lib.md_conv_plan_call(*args) == -1, act
+        assert lib.md_conv_nhwc_f16(*args, st) == -1 and b"act=" in lib.md_last_error(), act
+        torch.cuda.synchronize()
+        assert bool((y == 7.0).all()), f"conv act={act}: refused, but the output was written"
+    _count[0] += 1
 
 
 def sp_off_cases(dev):

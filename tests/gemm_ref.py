@@ -2,7 +2,8 @@
 tests/test_gemm_floor_cpu.py).  Plain PyTorch, independent of the library; every function runs on the device its operands live on (the
 CPU, or float64 / float32 torch matmul on the GPU for the cases whose float64 product would take seconds on the CPU).
 
-`reference`   float64 on the fp16-rounded operands.  GEMM: A W^T (+ bias) (+ rowadd[row // rows_per_group]), SiLU / ReLU, (+ residual) --
+`reference`   float64 on the fp16-rounded operands.  GEMM: A W^T (+ bias) (+ rowadd[row // rows_per_group]), SiLU / ReLU / QuickGELU
+              (x sigmoid(1.702 x), the CLIP vision tower's MLP), (+ residual) --
               the residual is added LAST, after the activation, as include/mdance_hip.h states for md_gemm_f16 -- or GEGLU
               h * gelu_erf(g) on the UNPACKED halves (w = [h rows | g rows], packing.geglu_weight interleaves them for the kernel);
               transpose_out returns the transpose of the same.  Conv: `conv_patches` writes the implicit-GEMM A matrix out from shifted
@@ -24,7 +25,7 @@ import torch
 from parity_budget import KERNEL_FACTOR  # noqa: F401  (re-exported: the factor of the pass rule)
 from test_gelu_scheme_cpu import gelu_fast
 
-ACT_NONE, ACT_SILU, ACT_RELU, ACT_GEGLU = 0, 1, 2, 3
+ACT_NONE, ACT_SILU, ACT_RELU, ACT_GEGLU, ACT_QUICKGELU = 0, 1, 2, 3, 4
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -69,6 +70,8 @@ def _epilogue(acc, bias, rowadd, rows_per_group, residual, act, gelu):
         acc = torch.nn.functional.silu(acc)
     elif act == ACT_RELU:
         acc = acc.clamp_min(0)
+    elif act == ACT_QUICKGELU:
+        acc = acc * torch.sigmoid(1.702 * acc)                      # in acc's dtype: float64 (reference) or fp32 (emulation)
     elif act == ACT_GEGLU:
         inner = acc.shape[1] // 2
         acc = acc[:, :inner] * gelu(acc[:, inner:]).to(dt)

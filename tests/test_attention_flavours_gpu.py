@@ -9,7 +9,8 @@ attention_v2s.h attn2s_eligible); md_attention_plan answers which one, and every
       of a plain PyTorch emulation of the documented arithmetic (tests/attention_ref.py: computed from the reference alone, not recorded).
 Dense outputs start as NaN, so a row no workgroup wrote fails (c).  K and V use other seeds than Q.
 profiles/attention_flavour_tests.log: floor and measured value of every case on MI355X (kernels at 1.00-1.07 x their floor), and the
-mutations of attn2s (a q-block skipped, the key mask off by one, P cut to 8 bits) that these cases catch and the older tests do not."""
+mutations of attn2s (a q-block skipped, the key mask off by one, P cut to 8 bits) that these cases catch and the older tests do not.
+profiles/clip_kernel_tests.log: the same for the call of the CLIP vision tower (plan 400 at D = 64 with an unwritten V^T slack)."""
 import functools
 
 import pytest
@@ -57,10 +58,12 @@ def _checker(rows, cols):
     return 1.0 - 2.0 * ((torch.arange(rows)[:, None] + torch.arange(cols)[None, :]) % 2).float()
 
 
-def launch(dev, pr, flavour, stride, pad=0.0, form="dense", vt_form="dense", runs=3):
+def launch(dev, pr, flavour, stride, pad=0.0, form="dense", vt_form="dense", runs=3, vt_slack=0.0):
     """Builds the operands of `pr` in the requested form, asserts the plan, launches `runs` times; returns the outputs (CPU).
     form: dense | slices (Q, K, O column slices of wider buffers: garbage around Q and K, 7.0 around O) | halves (Q | K the two column
-    halves of one [B*L, 2C] buffer, O a slice).  vt_form: dense | misaligned (base 8 bytes off a 16-byte boundary) | odd_ld (ldvt % 8 = 4).
+    halves of one [B*L, 2C] buffer, O a slice).  vt_form: dense | misaligned (base 8 bytes off a 16-byte boundary) | odd_ld (ldvt % 8 = 4) |
+    pitch8 (row pitch roundup8(nkv * stride) > nkv * stride, base 16-byte aligned: V^T as md_gemm_f16's transposed store leaves it for the
+    CLIP vision tower; the columns behind the last batch, which that store does not write, hold `vt_slack`).
     pad: rows [Lk, stride) of every K batch and the same columns of V^T hold +/-pad in a checkerboard."""
     B, H, D, Lq, Lk, nkv = pr.B, pr.H, pr.D, pr.Lq, pr.Lk, pr.nkv
     C, n = H * D, nkv * stride
@@ -87,6 +90,12 @@ def launch(dev, pr, flavour, stride, pad=0.0, form="dense", vt_form="dense", run
         wide[:, 4:4 + n] = vt
         vtd = wide.to(dev)[:, 4:4 + n]
         assert vtd.data_ptr() % 16 == 8 and vtd.stride(0) % 8 == 0
+    elif vt_form == "pitch8":
+        assert n % 8 != 0
+        wide = torch.full((C, n + -n % 8), vt_slack, dtype=torch.float16)
+        wide[:, :n] = vt
+        vtd = wide.to(dev)[:, :n]
+        assert vtd.data_ptr() % 16 == 0 and vtd.stride(0) % 8 == 0 and vtd.stride(0) == n + -n % 8
     else:
         assert vt_form == "odd_ld"
         wide = rnd(C, n + 4, seed=3, scale=50.0)
@@ -186,7 +195,7 @@ def test_ring_four_waves_self_attention_past_1024(dev):
 
 
 # --------------------------------------------------------------------------------------------- generic attn_kernel (400)
-@pytest.mark.parametrize("D", [8, 16, 32, 80, 160])
+@pytest.mark.parametrize("D", [8, 16, 32, 40, 64, 80, 160])
 def test_generic_kernel_every_head_dim(dev, D):
     """Lk = 77 = kv_stride is no multiple of 8; Lq = 130 is ragged against the kernel's 128-row block."""
     run_case(dev, f"generic D={D}", GENERIC, 2, 8, D, 130, 77)
@@ -197,6 +206,21 @@ def test_generic_kernel_is_taken_for_an_unaligned_vt_alone(dev, vt_form):
     """Everything else qualifies for the DMA kernels (stride 264, Lk = 257): only the V^T base (a [:, 4:] view of a wider buffer) or only
     ldvt % 8 sends the call to the generic kernel, whose element-wise V^T loads must then cope with it."""
     run_case(dev, f"generic vt {vt_form}", GENERIC, 2, 8, 40, 130, 257, stride=264, kv_index=(1, 0), vt_form=vt_form)
+
+
+@pytest.mark.parametrize("H,D,L", [(16, 64, 257),       # ViT-L/14: 16 heads of 64, 257 tokens, ldvt = 264
+                                   (4, 32, 17)])        # the reduced tower of tests/test_clip_gpu.py: ldvt = 24
+def test_clip_tower_call_never_reads_the_vt_slack(dev, H, D, L):
+    """mikudance_amd/clip_vision.py _ClipLayer.forward: ops.attention(qk[:, :C], qk[:, C:], vt, 1, H, C // H, L, L) -- one batch, Q | K the
+    halves of one GEMM output, kv_stride = Lk = L, and V^T from a transposed store with ldc_t = pad_to(L, 8) into a torch.empty buffer: its
+    columns [L, ldvt) are never written.  roundup8(L) > kv_stride makes this plan 400, and include/mdance_hip.h promises that the generic
+    kernel reads no V^T column >= Lk.  So NaN there must give the bits of zeros there (and both must pass the float64 rule): a whole
+    16-byte chunk loaded across Lk turns the NaN run non-finite (0 x NaN in the matrix core), whatever the key mask does."""
+    name = f"clip tower H={H} D={D} L={L}"
+    pr, zero = run_case(dev, f"{name} zero slack", GENERIC, 1, H, D, L, L, form="halves", vt_form="pitch8")
+    loud = launch(dev, pr, GENERIC, L, form="halves", vt_form="pitch8", vt_slack=float("nan"))[0]
+    check(f"{name} NaN slack", pr, loud)
+    assert torch.equal(loud.view(torch.int16), zero.view(torch.int16)), "the contents of V^T columns [Lk, ldvt) moved the output"
 
 
 # --------------------------------------------------------------------------------------------- operand forms of the pipeline

@@ -23,8 +23,15 @@ Which case asserts which plan code (t = 135 / 134 / 124 / 142 / 132 under MD_GEM
                      (K = 128, packed N = 1024, M = 32768 + 5), sp_off_cases (MD_GEMM_SP=0)
   303                test_occupancy_small (N = 200, 1288), test_alignment_alone (output base, output pitch, residual base, odd conv pitch,
                      SiLU / ReLU on a conv), SiLU / ReLU in sp_gemm_cases, test_geglu_automatic (K = 128), sp_off_cases
+The calls of the CLIP vision tower (mikudance_amd/clip_vision.py), all on gemm_kernel:
+  MD_ACT_QUICKGELU   test_quickgelu_automatic: 303 at M = 257, N = 200 (ragged rows, scalar last column group) with bias / none / residual
+                     after the activation / row term / column slice / pitch % 8 = 4, and at M = 32768 + 5, K = 128; 301 (N = 64); 302
+                     (K = 2048); a conv (303).  test_quickgelu_exact_screen: A = 0 over a bias table from -65504 to 65504 (303 and 301)
+  transposed store   test_transposed_ragged_m: M = 257 / 261 (M % 8 = 1 / 5: the scalar tail) into pitch roundup8(M) with a 7.0 guard behind
+                     column M and into pitch M (odd); M = 257, N = 320 under pins 4 and 2 (transposed_pinned_cases: 303, M % 256 != 0)
+  act outside 0..4   test_unknown_activation_is_refused: MD_ERR_ARG from launch and call query, output untouched (GEGLU on a conv too)
 profiles/gemm_flavour_tests.log: floor and measured value of every case on MI355X, the wall time of each test, and the mutations of the
-kernels that these cases catch."""
+kernels that these cases catch; profiles/clip_kernel_tests.log: the same for the tower's cases."""
 import os
 import subprocess
 import sys
@@ -88,8 +95,24 @@ def test_transposed_automatic(dev):
     C.transposed_auto_cases(dev)
 
 
+def test_transposed_ragged_m(dev):
+    C.transposed_ragged_cases(dev)
+
+
 def test_geglu_automatic(dev):
     C.geglu_auto_cases(dev)
+
+
+def test_quickgelu_automatic(dev):
+    C.quickgelu_cases(dev)
+
+
+def test_quickgelu_exact_screen(dev):
+    C.quickgelu_screen_cases(dev)
+
+
+def test_unknown_activation_is_refused(dev):
+    C.refused_act_case(dev)
 
 
 def test_occupancy_small(dev):

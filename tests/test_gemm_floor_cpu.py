@@ -13,8 +13,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gemm_ref import (ACT_GEGLU, ACT_NONE, ACT_RELU, ACT_SILU, KERNEL_FACTOR, conv_emulation, conv_patches, conv_reference, emulation,
-                      reference, rel_l2, rnd)
+from gemm_ref import (ACT_GEGLU, ACT_NONE, ACT_QUICKGELU, ACT_RELU, ACT_SILU, KERNEL_FACTOR, conv_emulation, conv_patches, conv_reference,
+                      emulation, reference, rel_l2, rnd)
 
 
 def _unpack3x3(wpk, cin):                              # [Cout, (ky, kx, c)] -> [Cout, Cin, 3, 3]
@@ -75,6 +75,13 @@ def test_reference_epilogues():
     assert torch.equal(reference(a, w, bias=bias, act=ACT_SILU), F.silu(base + bias.double()))
     assert torch.equal(reference(a, w, bias=bias, act=ACT_RELU), F.relu(base + bias.double()))
     assert torch.equal(reference(a, w, bias=bias, transpose_out=True), (base + bias.double()).t())
+    # QuickGELU x sigmoid(1.702 x), written here the other way (x / (1 + exp(-1.702 x))); bias and row term before it, the residual after it
+    qg = lambda x: x / (1.0 + torch.exp(-1.702 * x))
+    assert float((reference(a, w, bias=bias, act=ACT_QUICKGELU) - qg(base + bias.double())).abs().max()) < 1e-14
+    got = reference(a, w, bias=bias, rowadd=radd, rows_per_group=7, residual=res, act=ACT_QUICKGELU)
+    assert float((got - (qg(full) + res.double())).abs().max()) < 1e-14
+    assert float((got - qg(full + res.double())).abs().max()) > 0.1              # the other order is another function
+    assert emulation(a, w, bias=bias, act=ACT_QUICKGELU).dtype == torch.float16
     hg = base + bias.double()
     assert float((reference(a, w, bias=bias, act=ACT_GEGLU) - hg[:, :8] * F.gelu(hg[:, 8:])).abs().max()) < 1e-14
     assert emulation(a, w, bias=bias, residual=res).dtype == torch.float16
@@ -132,12 +139,16 @@ def test_tanh_gelu_in_geglu_lands_above_the_factor(K, inner):
 
 
 def test_emulation_of_every_epilogue_sits_at_one_rounding():
-    """Bias, row term, residual, SiLU / ReLU in fp32 and one rounding: the floor stays the output rounding (1.9e-4 .. 2.3e-4) for every form."""
+    """Bias, row term, residual, SiLU / ReLU / QuickGELU in fp32 and one rounding: the floor stays the output rounding (1.9e-4 .. 2.3e-4) for
+    every form (QuickGELU measured: 2.05e-4 alone or with a bias, 2.08e-4 / 2.09e-4 with a residual / a row term; the printed lines say so)."""
     M, N, K = 400, 128, 192
     a, w = rnd(M, K, seed=21), rnd(N, K, seed=22, scale=K ** -0.5)
     bias, radd, res = rnd(N, seed=23), rnd(5, N, seed=24), rnd(M, N, seed=25)
     for kw in (dict(bias=bias), dict(bias=bias, residual=res), dict(rowadd=radd, rows_per_group=97), dict(bias=bias, act=ACT_SILU),
                dict(bias=bias, act=ACT_RELU), dict(bias=bias, rowadd=radd, rows_per_group=97, residual=res), dict(transpose_out=True),
-               dict(act=ACT_NONE)):
+               dict(act=ACT_NONE), dict(bias=bias, act=ACT_QUICKGELU), dict(act=ACT_QUICKGELU),
+               dict(bias=bias, residual=res, act=ACT_QUICKGELU), dict(bias=bias, rowadd=radd, rows_per_group=97, act=ACT_QUICKGELU)):
         floor = rel_l2(emulation(a, w, **kw), reference(a, w, **kw))
+        if kw.get("act") == ACT_QUICKGELU:
+            print(f"\nPARITY_MEASURE gemm_floor_cpu:quickgelu {'+'.join(sorted(k for k in kw if k not in ('act', 'rows_per_group')))} floor={floor:.6e}")
         assert 1.8e-4 < floor < 2.4e-4, (sorted(kw), floor)

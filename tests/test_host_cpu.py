@@ -368,6 +368,12 @@ def test_plan_of_the_call_returns_every_refusal_of_the_launch():
     assert q.gemm(18432, 1280, 1280, tr=1, epi=6) < 0 and q.gemm(18432, 1280, 1280, tr=1, epi=5) < 0              # transposed with a row term / residual
     assert q.gemm(18432, 1280, 1280, tr=1, act=1) < 0
     assert q.gemm(18432, 1280, 1280, epi=2, rpg=0) < 0                                                            # row term without rows_per_group
+    # an activation the kernels do not know would run as "none": 4 (QuickGELU) is the last one, GEGLU has no conv form
+    assert q.gemm(18432, 1280, 1280, epi=4, act=4) == 303 and q.gemm(18432, 1280, 1280, epi=5, act=4) == 303
+    assert q.gemm(18432, 1280, 1280, act=5) == -1 and q.gemm(18432, 1280, 1280, act=-1) == -1 and q.gemm(18432, 1280, 1280, act=1 << 16) == -1
+    assert b"act=" in q.lib.md_last_error()
+    assert q.conv(32, 96, 320, 320, epi=4, act=4) == 302 and q.conv(32, 96, 320, 320, act=5) == -1 and q.conv(32, 96, 320, 320, act=-1) == -1
+    assert q.conv(32, 96, 320, 320, act=G) == -1 and b"act=3" in q.lib.md_last_error()
     assert q.gemm(18432, 1280, 1280, epi=1, res=q.C + 2 * 1280 * 10) < 0                                          # residual ten rows into the output
     assert q.gemm(18432, 1280, 1280, epi=1, res=q.C + 2 * 640, ldc=2560, ldr=2560) < 0                            # sibling slices that share columns
     assert q.gemm(18432, 1280, 1280, epi=1, res=q.C + 2 * 1280, ldc=2560, ldr=2560) == 2134                       # sibling slices that do not
