@@ -318,6 +318,31 @@ int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, const void* 
                               const void* perturbed_sum, int Ftot, int HW, int halves, float guidance, float pag_scale, float alpha_s,
                               float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
 
+/* (noise_pred / counter) -> classifier-free guidance -> one UniPC step (Zhao et al., "UniPC: A Unified Predictor-Corrector Framework for Fast
+ * Sampling of Diffusion Models", arXiv 2302.04867; diffusers UniPCMultistepScheduler, data prediction, orders 1 - 3), latents updated in
+ * place.  The corrector of the step that produced these latents and the predictor to the next point are ONE pass per pixel:
+ *   m_t = alpha_s x - sigma_s v                                      x: the fp16 latents, v: the guided output as md_cfg_ddim_step forms it
+ *   x^c = cc_x x_last + cc_m m_t + cc_0 H0 + cc_1 H1 + cc_2 H2       corrector on; off: x^c = x
+ *   x'  = pc_x x^c + pc_m m_t + pc_0 H0 + pc_1 H1                    -> latents (fp32 arithmetic, one rounding)
+ *   x_last <- x^c;  H0 <- m_t;  H1 <- H0;  H2 <- H1
+ * state: fp32 [4][Ftot][HW][4], the planes x_last, H0, H1, H2 (the corrected sample and the data predictions of the last three steps), kept by
+ * the caller between steps.  A plane is read only where one of its weights is non-zero (x_last only with the corrector on), and only a plane
+ * that was read moves down a slot: a first step (corrector off, pc_0 = pc_1 = 0) may be given uninitialised memory.
+ * row: 12 floats in HOST memory, read before the call returns: alpha_s, sigma_s, cc_x, cc_m, cc_0, cc_1, cc_2, pc_x, pc_m, pc_0, pc_1 and the
+ * corrector flag (0 or 1), as UniPCMultistepScheduler.unipc_coefficients gives them; all finite.
+ * noise_sum, counter, Ftot, HW, halves, guidance as md_cfg_ddim_step; the _scaled / _apg / _pag entries add what the entries of the same name
+ * of md_cfg_multistep_step add (md_cfg_apg_prepare is called with this row's alpha_s, sigma_s).  Latents 8-byte, noise_sum / state / momentum_buf /
+ * perturbed_sum 16-byte, counter / vscale / coef 4-byte aligned.  MD_ERR_ARG otherwise, with nothing launched.
+ * src/pipelines/pipeline_mikudance.py:45-52 (UniPCMultistepScheduler is not among the reference's schedulers: an addition) and :670-678. */
+int md_cfg_unipc_step(void* latents, const void* noise_sum, const void* counter, void* state, int Ftot, int HW, int halves, float guidance,
+                      const float* row, void* stream);
+int md_cfg_unipc_step_scaled(void* latents, const void* noise_sum, const void* counter, void* state, const float* vscale, int Ftot, int HW,
+                             int halves, float guidance, const float* row, void* stream);
+int md_cfg_unipc_step_apg(void* latents, const void* noise_sum, const void* counter, void* state, const void* momentum_buf, const float* coef,
+                          int Ftot, int HW, int halves, float guidance, const float* row, void* stream);
+int md_cfg_unipc_step_pag(void* latents, const void* noise_sum, const void* counter, void* state, const void* perturbed_sum, int Ftot, int HW,
+                          int halves, float guidance, float pag_scale, const float* row, void* stream);
+
 /* The unconditional plane of a sampling step that evaluated the conditional half only (guidance_interval= after Kynkaanniemi et al.,
  * "Applying Guidance in a Limited Interval", arXiv 2404.07724; uncond_cache_interval= after the CFG cache of FasterCache, arXiv 2410.19355,
  * the idea only): an opt-in approximation, between src/pipelines/pipeline_mikudance.py:662-668 (the windows) and :670-678 (CFG + step).

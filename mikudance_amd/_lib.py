@@ -71,6 +71,10 @@ SIGNATURES = {
     "md_cfg_ddim_step_pag": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P]),
     "md_cfg_multistep_step_pag": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
                                           c_float, P]),
+    "md_cfg_unipc_step": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P, P]),
+    "md_cfg_unipc_step_scaled": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P, P]),
+    "md_cfg_unipc_step_apg": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P]),
+    "md_cfg_unipc_step_pag": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P]),
     "md_cfg_uncond_cache": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
     "md_add_noise_f16": (c_int, [P, P, c_long, c_float, c_float, P]),
     "md_free_init_plan": (c_int, [c_int, c_int, c_int]),

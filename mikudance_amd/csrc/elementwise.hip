@@ -526,6 +526,130 @@ extern "C" int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, c
                               stream, step_pag(perturbed_sum, pag_scale), "md_cfg_multistep_step_pag");
 }
 
+// ---- CFG combine + UniPC correct-then-predict step (orders 1 - 3; Zhao et al., arXiv 2302.04867, data-prediction form) -----------------
+//   v    = guided_v                                          (the *_scaled entry: times *vscale; *_apg: apg_v; *_pag: pag_v)
+//   m_t  = alpha_s x - sigma_s v                             data prediction at this step's point, x the fp16 latent the UNet saw
+//   x^c  = cc_x x_last + cc_m m_t + cc_0 H0 + cc_1 H1 + cc_2 H2      UniC from the previous point to this one; corrector off: x^c = x
+//   x'   = pc_x x^c + pc_m m_t + pc_0 H0 + pc_1 H1                   UniP from this point to the next, stored as the fp16 latent
+//   x_last <- x^c;  H0 <- m_t;  H1 <- H0;  H2 <- H1
+// Every solver variant is this one update: the weights are host scalars (UniPCMultistepScheduler.unipc_coefficients, the <= 3 x 3 systems
+// solved there in float64).  state: fp32 planes [x_last, H0, H1, H2], each [Ftot][HW][4].  One thread owns one pixel: an 8-byte latent
+// access and 16-byte plane accesses, the rotation a register move.  A plane is read only where one of its weights is non-zero (x_last only
+// with the corrector on) and only a plane that was read moves down a slot, so the first step runs on an uninitialised state; the scheduler's
+// docstring shows that no later step misses a plane that was left behind.
+struct UniPCRow {
+  float alpha_s, sigma_s;
+  float cc_x, cc_m, cc_0, cc_1, cc_2;
+  float pc_x, pc_m, pc_0, pc_1;
+  int correct;
+};
+
+enum { UNIPC_PLAIN = 0, UNIPC_SCALED, UNIPC_APG, UNIPC_PAG };
+
+// aux0 / aux1 / auxs: SCALED (vscale, -, -), APG (mom, coef, gs = (guidance - 1) / sigma_s), PAG (pag_sum, -, pag_scale)
+template <int FLAVOUR>
+__global__ __launch_bounds__(256) void cfg_unipc_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum,
+                                                        const float* __restrict__ counter, float* __restrict__ state, int Ftot, int HW, int halves,
+                                                        float guidance, UniPCRow r, const float* __restrict__ aux0, const float* __restrict__ aux1,
+                                                        float auxs) {
+  const long total = (long)Ftot * HW;  // pixels
+  const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
+  const floatx4* a4 = reinterpret_cast<const floatx4*>(aux0);
+  half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
+  floatx4* xl = reinterpret_cast<floatx4*>(state);
+  floatx4 *H0 = xl + total, *H1 = H0 + total, *H2 = H1 + total;
+  const bool rd0 = r.cc_0 != 0.f || r.pc_0 != 0.f, rd1 = r.cc_1 != 0.f || r.pc_1 != 0.f, rd2 = r.cc_2 != 0.f;
+  const float vs = FLAVOUR == UNIPC_SCALED ? *aux0 : 1.f;
+  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+    const floatx4 x = __builtin_convertvector(lat4[p], floatx4);
+    const int fr = (int)(p / HW);
+    floatx4 v;
+    if constexpr (FLAVOUR == UNIPC_APG)
+      v = apg_v(ns, counter, a4, aux1, p, total, fr, guidance, r.alpha_s, r.sigma_s, auxs, x);
+    else if constexpr (FLAVOUR == UNIPC_PAG)
+      v = pag_v(ns, a4, counter, p, total, fr, halves, guidance, auxs);
+    else
+      v = guided_v(ns, counter, p, total, fr, halves, guidance);
+    if constexpr (FLAVOUR == UNIPC_SCALED) v *= vs;
+    const floatx4 mt = r.alpha_s * x - r.sigma_s * v;
+    floatx4 h0, h1, h2;
+    if (rd0) h0 = H0[p];
+    if (rd1) h1 = H1[p];
+    if (rd2) h2 = H2[p];
+    floatx4 xc = x;
+    if (r.correct) {
+      xc = r.cc_x * xl[p] + r.cc_m * mt;
+      if (r.cc_0 != 0.f) xc += r.cc_0 * h0;
+      if (r.cc_1 != 0.f) xc += r.cc_1 * h1;
+      if (r.cc_2 != 0.f) xc += r.cc_2 * h2;
+    }
+    floatx4 out = r.pc_x * xc + r.pc_m * mt;
+    if (r.pc_0 != 0.f) out += r.pc_0 * h0;
+    if (r.pc_1 != 0.f) out += r.pc_1 * h1;
+    lat4[p] = __builtin_convertvector(out, half4_t);
+    xl[p] = xc;
+    H0[p] = mt;
+    if (rd0) H1[p] = h0;
+    if (rd1) H2[p] = h1;
+  }
+}
+
+// row: 12 host floats, (alpha_s, sigma_s, cc_x, cc_m, cc_0, cc_1, cc_2, pc_x, pc_m, pc_0, pc_1, corrector on: 0 or 1)
+static int cfg_unipc_launch(void* latents, const void* noise_sum, const void* counter, void* state, int Ftot, int HW, int halves, float guidance,
+                            const float* row, void* stream, const StepExtra& ex, const char* who) {
+  MD_CHECK_ARG(row, "%s: null coefficient row", who);
+  if (cfg_step_check(who, latents, noise_sum, counter, nullptr, ex, Ftot, HW, halves, 0.f,
+                     {guidance, row[0], row[1], row[2], row[3], row[4], row[5], row[6], row[7], row[8], row[9], row[10]}))
+    return MD_ERR_ARG;
+  MD_CHECK_ARG(row[11] == 0.f || row[11] == 1.f, "%s: the corrector flag must be 0 or 1", who);
+  MD_CHECK_ARG(state, "%s: null state", who);
+  if (cfg_pixel_alignment_check(who, latents, noise_sum, state, nullptr, ex)) return MD_ERR_ARG;
+  MD_CHECK_ARG(((uintptr_t)counter % 4) == 0, "%s: counter needs 4-byte alignment", who);
+  MD_CHECK_ARG(!ex.apg || row[1] > 0.f, "%s: APG divides by sigma_s: it must be > 0", who);
+  const UniPCRow r = {row[0], row[1], row[2], row[3], row[4], row[5], row[6], row[7], row[8], row[9], row[10], row[11] != 0.f};
+  const long total = (long)Ftot * HW;
+  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  const dim3 g(grid), b(256);
+  half_t* lat = (half_t*)latents;
+  const float *ns = (const float*)noise_sum, *cnt = (const float*)counter;
+  float* st = (float*)state;
+  hipStream_t s = (hipStream_t)stream;
+  if (ex.apg)
+    hipLaunchKernelGGL(cfg_unipc_kernel<UNIPC_APG>, g, b, 0, s, lat, ns, cnt, st, Ftot, HW, halves, guidance, r, ex.mom, ex.coef,
+                       (guidance - 1.f) / r.sigma_s);
+  else if (ex.pag)
+    hipLaunchKernelGGL(cfg_unipc_kernel<UNIPC_PAG>, g, b, 0, s, lat, ns, cnt, st, Ftot, HW, halves, guidance, r, ex.pag_sum, nullptr, ex.pag_scale);
+  else if (ex.scaled)
+    hipLaunchKernelGGL(cfg_unipc_kernel<UNIPC_SCALED>, g, b, 0, s, lat, ns, cnt, st, Ftot, HW, halves, guidance, r, ex.vscale, nullptr, 0.f);
+  else
+    hipLaunchKernelGGL(cfg_unipc_kernel<UNIPC_PLAIN>, g, b, 0, s, lat, ns, cnt, st, Ftot, HW, halves, guidance, r, nullptr, nullptr, 0.f);
+  MD_CHECK_LAUNCH(who);
+  return MD_OK;
+}
+
+extern "C" int md_cfg_unipc_step(void* latents, const void* noise_sum, const void* counter, void* state, int Ftot, int HW, int halves, float guidance,
+                                 const float* row, void* stream) {
+  return cfg_unipc_launch(latents, noise_sum, counter, state, Ftot, HW, halves, guidance, row, stream, StepExtra(), "md_cfg_unipc_step");
+}
+
+extern "C" int md_cfg_unipc_step_scaled(void* latents, const void* noise_sum, const void* counter, void* state, const float* vscale, int Ftot, int HW,
+                                        int halves, float guidance, const float* row, void* stream) {
+  return cfg_unipc_launch(latents, noise_sum, counter, state, Ftot, HW, halves, guidance, row, stream, step_scaled(vscale),
+                          "md_cfg_unipc_step_scaled");
+}
+
+extern "C" int md_cfg_unipc_step_apg(void* latents, const void* noise_sum, const void* counter, void* state, const void* momentum_buf,
+                                     const float* coef, int Ftot, int HW, int halves, float guidance, const float* row, void* stream) {
+  return cfg_unipc_launch(latents, noise_sum, counter, state, Ftot, HW, halves, guidance, row, stream, step_apg(momentum_buf, coef),
+                          "md_cfg_unipc_step_apg");
+}
+
+extern "C" int md_cfg_unipc_step_pag(void* latents, const void* noise_sum, const void* counter, void* state, const void* perturbed_sum, int Ftot,
+                                     int HW, int halves, float guidance, float pag_scale, const float* row, void* stream) {
+  return cfg_unipc_launch(latents, noise_sum, counter, state, Ftot, HW, halves, guidance, row, stream, step_pag(perturbed_sum, pag_scale),
+                          "md_cfg_unipc_step_pag");
+}
+
 // ---- the unconditional plane of a step that did not evaluate it (guidance_interval=, uncond_cache_interval=) ---------------------------
 // A step that runs the conditional evaluation only leaves plane 0 (u) of the accumulator empty.  This kernel fills it so that every
 // consumer of the planes (guided_v and with it both steps, the rescale, APG, PAG / SEG) works unchanged:

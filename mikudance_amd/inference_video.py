@@ -11,7 +11,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                                                              unet_additional_kwargs=infer_config.unet_additional_kwargs)  (:90-95)
     image_enc      = CLIPVisionModelWithProjection.from_pretrained(config.image_encoder_path)      (:97-99)
     scheduler      = DDIMScheduler(**infer_config.noise_scheduler_kwargs)                          (:101-102)
-                     (--sampler dpmpp_2m / dpmpp_2m_sde: DPMSolverMultistepScheduler from the same kwargs; an addition)
+                     (--sampler dpmpp_2m / dpmpp_2m_sde: DPMSolverMultistepScheduler from the same kwargs; --sampler unipc:
+                     UniPCMultistepScheduler from the same kwargs with --solver_order and --unipc_solver_type; additions)
     pipe(..., guidance_rescale=--guidance_rescale)                                                 (an addition; default 0.0 = off)
     pipe(..., video=read_frames(--init_video), strength=--strength)                                (an addition: video-to-video)
     pipe(..., context_schedule=, context_fuse=, context_frames=, context_overlap=)                 (additions: how a clip longer than the
@@ -53,17 +54,18 @@ import torch
 from PIL import Image
 
 from . import (AutoencoderKL, AutoencoderKLTemporalDecoder, CLIPVisionModelWithProjection, DDIMScheduler, DPMSolverMultistepScheduler,
-               MikuDanceVideoPipeline, UNet2DConditionModel, UNet2DConditionModelPlain, UNet3DConditionModel)
+               MikuDanceVideoPipeline, UNet2DConditionModel, UNet2DConditionModelPlain, UNet3DConditionModel, UniPCMultistepScheduler)
 from .free_init import FILTERS as FREE_INIT_FILTERS
 from .io_utils import frames_to_tensor, get_fps, load_config, read_frames, resize_depth, save_videos_grid, to_container
 from .scene_motion import camera_to_scene_motion
 
 
 # --sampler -> the scheduler built from the YAML's noise_scheduler_kwargs (the YAML's own `sampler: DDIM` key stays ignored, as in the
-# reference script)
+# reference script); "unipc" also takes the solver's own keywords (--solver_order -> solver_order, --unipc_solver_type -> solver_type)
 SAMPLERS = {"ddim": lambda kw: DDIMScheduler(**kw),
             "dpmpp_2m": lambda kw: DPMSolverMultistepScheduler.from_config(kw, solver_order=2, algorithm_type="dpmsolver++"),
-            "dpmpp_2m_sde": lambda kw: DPMSolverMultistepScheduler.from_config(kw, solver_order=2, algorithm_type="sde-dpmsolver++")}
+            "dpmpp_2m_sde": lambda kw: DPMSolverMultistepScheduler.from_config(kw, solver_order=2, algorithm_type="sde-dpmsolver++"),
+            "unipc": lambda kw, **solver: UniPCMultistepScheduler.from_config(kw, **solver)}
 
 
 def _factors(text):
@@ -103,8 +105,13 @@ def parse_args(argv=None):
                         help="The temporal decoder produces less noise in the results but leads to longer inference times.")
     parser.add_argument("--output_dir", default="output", help="(addition) root of the dated output tree")
     parser.add_argument("--sampler", choices=tuple(SAMPLERS), default="ddim",
-                        help="(addition) ddim (the reference's), dpmpp_2m or dpmpp_2m_sde (DPM-Solver++ 2M, ODE / SDE), all built from "
+                        help="(addition) ddim (the reference's), dpmpp_2m or dpmpp_2m_sde (DPM-Solver++ 2M, ODE / SDE) or unipc (UniPC, "
+                             "arXiv 2302.04867: a predictor-corrector multistep solver, no extra UNet evaluation), all built from "
                              "noise_scheduler_kwargs")
+    parser.add_argument("--solver_order", type=int, choices=(1, 2, 3), default=2,
+                        help="(addition) with --sampler unipc: the order of the predictor (the corrector follows it); 2 = diffusers' default")
+    parser.add_argument("--unipc_solver_type", choices=("bh1", "bh2"), default="bh2",
+                        help="(addition) with --sampler unipc: B(h) = h (bh1) or expm1(h) (bh2, diffusers' default)")
     parser.add_argument("--guidance_rescale", type=float, default=0.0,
                         help="(addition) phi of rescaled classifier-free guidance (arXiv 2305.08891 section 3.4, diffusers guidance_rescale), "
                              "in [0, 1]; 0.0 = off (the reference's behaviour), 0.7 the paper's value.  Works with every --sampler")
@@ -211,13 +218,16 @@ def _none(v):
     return v is None or v == "None"
 
 
-def build_scheduler(infer_config, sampler="ddim"):
-    """scripts/inference_video.py:101-102 (`--sampler ddim`), or the DPM-Solver++ 2M scheduler from the same keyword arguments."""
-    return SAMPLERS[sampler](to_container(infer_config.noise_scheduler_kwargs))
+def build_scheduler(infer_config, sampler="ddim", **solver):
+    """scripts/inference_video.py:101-102 (`--sampler ddim`), or the DPM-Solver++ 2M / UniPC scheduler from the same keyword arguments.
+    solver: with "unipc" only, the solver's own keywords (solver_order, solver_type, disable_corrector)."""
+    if solver and sampler != "unipc":
+        raise ValueError(f"sampler {sampler!r} takes no solver keywords, got {sorted(solver)}")
+    return SAMPLERS[sampler](to_container(infer_config.noise_scheduler_kwargs), **solver)
 
 
-def build_pipeline(config, infer_config, weight_dtype, device="cuda", video_decoder=False, sampler="ddim"):
-    """scripts/inference_video.py:72-130."""
+def build_pipeline(config, infer_config, weight_dtype, device="cuda", video_decoder=False, sampler="ddim", solver=None):
+    """scripts/inference_video.py:72-130.  solver: build_scheduler's keywords for `sampler`."""
     if video_decoder:
         vae = AutoencoderKLTemporalDecoder.from_pretrained(config.pretrained_temporal_vae_path).to(device, dtype=weight_dtype)
     else:
@@ -229,7 +239,7 @@ def build_pipeline(config, infer_config, weight_dtype, device="cuda", video_deco
         config.pretrained_base_model_path, config.motion_module_path, subfolder="unet",
         unet_additional_kwargs=infer_config.unet_additional_kwargs).to(dtype=weight_dtype, device=device)
     image_enc = CLIPVisionModelWithProjection.from_pretrained(config.image_encoder_path).to(dtype=weight_dtype, device=device)
-    scheduler = build_scheduler(infer_config, sampler)
+    scheduler = build_scheduler(infer_config, sampler, **(solver or {}))
     denoising_unet.load_state_dict(torch.load(config.denoising_unet_path, map_location="cpu", weights_only=True), strict=False)
     reference_unet.load_state_dict(torch.load(config.reference_unet_path, map_location="cpu", weights_only=True))
     denoising_unet.eval()
@@ -253,7 +263,8 @@ def main(argv=None):
     generator = torch.manual_seed(args.seed)
     width, height = args.W, args.H
     assert width % 8 == 0 and height % 8 == 0      # the vae works at 1/8 resolution (scripts/inference_video.py:108)
-    pipe = build_pipeline(config, infer_config, weight_dtype, video_decoder=args.video_decoder, sampler=args.sampler)
+    solver = dict(solver=dict(solver_order=args.solver_order, solver_type=args.unipc_solver_type)) if args.sampler == "unipc" else {}
+    pipe = build_pipeline(config, infer_config, weight_dtype, video_decoder=args.video_decoder, sampler=args.sampler, **solver)
 
     date_str = datetime.now().strftime("%Y%m%d")
     time_str = datetime.now().strftime("%H%M%S")

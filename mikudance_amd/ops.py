@@ -483,6 +483,40 @@ def cfg_multistep_step_pag(latents, noise_sum, counter, history, perturbed_sum, 
               float(pag_scale), float(alpha_s), float(sigma_s), float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
 
 
+def _unipc_state_row(state, row, ftot, hw):
+    """The checks the cfg_unipc_step* wrappers share -> (state pointer, the row as 12 C floats in host memory)."""
+    _chk(state, "state", torch.float32)
+    assert state.is_contiguous() and state.numel() == 4 * ftot * hw * 4
+    assert len(row) == 12
+    return state.data_ptr(), (ctypes.c_float * 12)(*(float(v) for v in row))
+
+
+def cfg_unipc_step(latents, noise_sum, counter, state, ftot, hw, guidance, row, halves=2, vscale=None):
+    """UniPC correct-then-predict update (md_cfg_unipc_step): `state` is the fp32 (4, ftot, hw, 4) buffer (x_last and the data predictions of
+    the last three steps) the caller keeps between steps, uninitialised before the first; `row` is
+    UniPCMultistepScheduler.unipc_coefficients(step_index).  vscale: as in cfg_ddim_step (md_cfg_unipc_step_scaled)."""
+    bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, 0.0, None, vscale)
+    sp, rp = _unipc_state_row(state, row, ftot, hw)
+    _lib.call("md_cfg_unipc_step" if vscale is None else "md_cfg_unipc_step_scaled", *bufs, sp, *(() if vscale is None else (vscale.data_ptr(),)),
+              ftot, hw, halves, float(guidance), rp, _st(), meta=(f"cfg_unipc_step F={ftot} HW={hw}", 0.0, (4.0 + 4.0 * halves + 32.0) * ftot * hw * 4))
+
+
+def cfg_unipc_step_apg(latents, noise_sum, counter, state, momentum_buf, coef, ftot, hw, guidance, row):
+    """cfg_unipc_step under CFG with APG's guided output (md_cfg_unipc_step_apg): `momentum_buf` and `coef` as cfg_apg_prepare left them for
+    this step at the row's alpha_s, sigma_s; the data prediction kept in `state` is alpha_s x - sigma_s v_g."""
+    bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, 0.0, None, None)
+    sp, rp = _unipc_state_row(state, row, ftot, hw)
+    _lib.call("md_cfg_unipc_step_apg", *bufs, sp, *_apg_buffers(momentum_buf, coef, ftot, hw), ftot, hw, 2, float(guidance), rp, _st())
+
+
+def cfg_unipc_step_pag(latents, noise_sum, counter, state, perturbed_sum, ftot, hw, guidance, pag_scale, row, halves=2):
+    """cfg_unipc_step with perturbed-attention guidance (md_cfg_unipc_step_pag): `perturbed_sum` and pag_scale as in cfg_ddim_step_pag."""
+    bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, 0.0, None, None)
+    sp, rp = _unipc_state_row(state, row, ftot, hw)
+    _lib.call("md_cfg_unipc_step_pag", *bufs, sp, _pag_plane(perturbed_sum, ftot, hw), ftot, hw, halves, float(guidance), float(pag_scale), rp,
+              _st())
+
+
 def cfg_uncond_cache(noise_sum, counter, delta, ftot, hw, mode, scale=1.0):
     """The unconditional plane of a step that evaluated the conditional half only (md_cfg_uncond_cache).  noise_sum: fp32 (2, ftot, hw, 4),
     planes [u, c]; counter: fp32 (ftot,); delta: fp32 (ftot, hw, 4).  mode 0 stores delta = c_sum / cnt - u_sum / cnt; mode 1 restores

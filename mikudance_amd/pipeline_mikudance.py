@@ -86,6 +86,7 @@ class SamplingPlan:
     tile: Union[None, tuple] = None                # None: no tiled self-attention; (factors, shift), resolved: (UNet3DConditionModel.tile_attention_plan, shift)
     deep: Union[None, tuple] = None                # None: deep_cache_interval == 1, no DeepCache; (interval N, depth d), d checked against the UNet by _resolve_plan
     uncond: Union[None, tuple] = None              # None: guidance on every step from a full evaluation (the defaults, or no CFG); (lo, hi, n) of guidance_interval / uncond_cache_interval
+    sampler: str = "ddim"                          # which step the loop calls: "ddim" (md_cfg_ddim_step*), "dpm" (md_cfg_multistep_step*) or "unipc" (md_cfg_unipc_step*)
 
 
 # the step forms v in ONE way: (asked for, beside, why not), in the order the refusals are made
@@ -174,8 +175,15 @@ class MikuDanceVideoPipeline:
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
         ref_latents         (1, F, 22, h, w) 20 VAE-latent guidance channels + 2 scene-motion channels
         image_prompt_embeds (2, L, D) = [zeros, CLIP tokens] when guidance_scale > 1, else (1, L, D)
-        scheduler           self.scheduler: DDIMScheduler (md_cfg_ddim_step) or DPMSolverMultistepScheduler (md_cfg_multistep_step with a
-                            fp32 data-prediction history of (F, h*w, 4) for this call; its SDE variant draws z every step like eta below)
+        scheduler           self.scheduler: DDIMScheduler (md_cfg_ddim_step), DPMSolverMultistepScheduler (md_cfg_multistep_step with a
+                            fp32 data-prediction history of (F, h*w, 4) for this call; its SDE variant draws z every step like eta below) or
+                            UniPCMultistepScheduler (md_cfg_unipc_step: the corrector of the last step and the predictor of this one in one
+                            launch per step, on a fp32 state of (4, F, h*w, 4) for this call -- the corrected sample and three data
+                            predictions; two denoise() calls, as under hires_scale, have a state each.  The state starts over with every
+                            FreeInit pass and at a video-to-video start: the first row of a schedule reads none of it, so it is allocated
+                            uninitialised and never cleared.  Every guide, approximation, window schedule and fuse mode acts in front of the
+                            step and composes with it; under window_parallel the step and its state are replicated on every rank.  eta > 0 is
+                            refused with it: UniPC has no stochastic variant here)
         eta, generator      DDIM's stochastic variant (reference :152-171 -> scheduler.step(eta=, generator=)): one N(0, 1) draw of
                             the latents' shape and dtype per step from `generator` (on ITS device, like diffusers' randn_tensor).
                             The kernels compute in fp16: the draw is ROUNDED TO fp16 on its way into md_cfg_ddim_step_eta, so an
@@ -371,7 +379,7 @@ class MikuDanceVideoPipeline:
         returns latents (1, 4, F, h, w) in the input dtype.
         """
         plan = self.sampling_plan(
-            num_inference_steps, guidance_scale, init_latents is not None, tuple(latents.shape[2:]), guidance_rescale=guidance_rescale, strength=strength, context_fuse=context_fuse, free_init_iters=free_init_iters,
+            num_inference_steps, guidance_scale, init_latents is not None, tuple(latents.shape[2:]), sampler=self._sampler(), eta=eta, guidance_rescale=guidance_rescale, strength=strength, context_fuse=context_fuse, free_init_iters=free_init_iters,
             free_init_filter=free_init_filter, free_init_order=free_init_order, free_init_spatial_stop=free_init_spatial_stop,
             free_init_temporal_stop=free_init_temporal_stop, free_init_fast=free_init_fast, apg=apg, apg_eta=apg_eta,
             apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
@@ -390,9 +398,9 @@ class MikuDanceVideoPipeline:
         do_cfg = guidance_scale > 1.0
         nb = 2 if do_cfg else 1
         den, refu, sch = self.denoising_unet, self.reference_unet, self.scheduler
-        from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
-        multistep = isinstance(sch, DPMSolverMultistepScheduler)
-        if not multistep and not isinstance(sch, DDIMScheduler):
+        from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
+        multistep, unipc = isinstance(sch, DPMSolverMultistepScheduler), plan.sampler == "unipc"
+        if not multistep and not unipc and not isinstance(sch, DDIMScheduler):
             raise TypeError(f"MikuDanceVideoPipeline.denoise: unsupported scheduler {type(sch).__name__}; the supported ones are "
                             "mikudance_amd.DDIMScheduler and mikudance_amd.DPMSolverMultistepScheduler")
         if multistep and eta > 0:
@@ -473,6 +481,8 @@ class MikuDanceVideoPipeline:
         embeds = image_prompt_embeds
         # DPM-Solver++: the previous step's data prediction, fp32, per call (under window_parallel every rank keeps its own identical copy)
         history = torch.zeros((F_, HW, 4), device=dev, dtype=torch.float32) if multistep else None
+        # UniPC: x_last and the data predictions of the last three steps, fp32, per call; the first row of a schedule reads none of it
+        unipc_state = torch.empty((4, F_, HW, 4), device=dev, dtype=torch.float32) if unipc else None
         # guidance rescale: one fp32 factor per step; APG: the momentum buffer and the per-frame (S, K).  All written and read on the device
         # (no host sync); another guide: none of them, and the other entry points called exactly as without the keywords
         if rescale:
@@ -488,9 +498,12 @@ class MikuDanceVideoPipeline:
                 ops.window_accumulate_weighted(pred, planes, count, win_dev[wi], wts_dev[wi], len(windows[wi]), F_, HW, halves=halves)
 
         def step(step_i, t, s_t):
-            """The CFG + scheduler update of lat from the accumulated planes: ops.cfg_ddim_step / ops.cfg_multistep_step, or the guide's flavour
-            of it (_apg, _pag).  The same statistics on every rank: same buffers, same arithmetic."""
-            if multistep:
+            """The CFG + scheduler update of lat from the accumulated planes: ops.cfg_ddim_step / ops.cfg_multistep_step / ops.cfg_unipc_step, or
+            the guide's flavour of it (_apg, _pag).  The same statistics on every rank: same buffers, same arithmetic."""
+            if unipc:
+                row = sch.unipc_coefficients(t_start + step_i)
+                name, state, (a, s), co, kw = "cfg_unipc_step", (unipc_state,), row[:2], (row,), {}
+            elif multistep:
                 z = self._draw_noise(latents, generator) if sch.is_sde else None       # every step, like the eta path
                 co = sch.multistep_coefficients(t_start + step_i)
                 name, state, (a, s), kw = "cfg_multistep_step", (history,), co[:2], dict(variance_noise=z)
@@ -606,11 +619,12 @@ class MikuDanceVideoPipeline:
                       free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop, free_init_fast, apg, apg_eta,
                       apg_norm_threshold, apg_momentum, pag_scale, pag_adaptive_scale, pag_applied_layers, kv_downsample, kv_downsample_mode,
                       seg_scale, seg_blur_sigma, seg_applied_layers, tile_attention=1, tile_attention_shift="cycle", deep_cache_interval=1,
-                      deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1):
+                      deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1, sampler="ddim", eta=0.0):
         """Every refusal of denoise()'s sampling keywords (see its docstring) that needs no model -- every value is checked whether or not its
         feature is on, and neither UNet is called -- then what they resolve to -> SamplingPlan, still holding the layer names and the
         (factors, mode) that _resolve_plan hands to the denoising UNet.  has_init: there is a clip to start from (init_latents / video);
-        shape: the latents' shape behind (batch, channels), (F, h, w)."""
+        shape: the latents' shape behind (batch, channels), (F, h, w).  sampler: "ddim", "dpm" or "unipc", what self.scheduler selects (_sampler);
+        eta: denoise()'s, refused here with "unipc" (with "dpm" denoise() refuses it itself, behind the plan)."""
         from .unet_3d_mix import (check_kv_downsample, check_kv_downsample_grid, check_pag_layer_names, check_tile_attention,
                                   check_tile_attention_grid)
         asked = []
@@ -692,6 +706,11 @@ class MikuDanceVideoPipeline:
             raise ValueError("guidance_interval / uncond_cache_interval cannot be combined with deep_cache_interval > 1: a DeepCache slot is shaped by "
                              "the batch of the evaluation that filled it (both clip-halves), and a conditional-only step would meet a slot of the "
                              "other shape")
+        if sampler not in ("ddim", "dpm", "unipc"):
+            raise ValueError(f"sampler must be 'ddim', 'dpm' or 'unipc', got {sampler!r}")
+        if sampler == "unipc" and eta != 0:
+            raise ValueError(f"eta={eta} cannot be combined with UniPCMultistepScheduler: UniPC is a deterministic solver here (eta applies to "
+                             "DDIMScheduler only; for stochastic sampling use DPMSolverMultistepScheduler(algorithm_type='sde-dpmsolver++'))")
         guide = None
         if pag_s > 0.0:
             guide = Perturb("identity", pag_s, pag_a, pag_names, None)
@@ -705,7 +724,12 @@ class MikuDanceVideoPipeline:
                                            free_init_fast), strength, (kv_factors, kv_mode) if any(f > 1 for f in kv_factors) else None, guide,
                             (tile_factors, tile_shift) if any(f > 1 for f in tile_factors) else None,
                             (int(deep_cache_interval), int(deep_cache_depth)) if deep_cache_interval > 1 else None,
-                            (gi_lo, gi_hi, int(uncond_cache_interval)) if skips_uncond and guidance_scale > 1.0 else None)
+                            (gi_lo, gi_hi, int(uncond_cache_interval)) if skips_uncond and guidance_scale > 1.0 else None, sampler)
+
+    def _sampler(self):
+        """The sampling plan's name for what self.scheduler selects; any other scheduler counts as "ddim" until denoise() refuses it."""
+        from .scheduler import DPMSolverMultistepScheduler, UniPCMultistepScheduler
+        return "unipc" if isinstance(self.scheduler, UniPCMultistepScheduler) else "dpm" if isinstance(self.scheduler, DPMSolverMultistepScheduler) else "ddim"
 
     def _resolve_plan(self, plan):
         """The refusals only the denoising UNet can make (a layer name that selects no block, more factors than levels, a level without
@@ -1023,7 +1047,7 @@ class MikuDanceVideoPipeline:
         hires =self.hires_plan(height or 768, width or 768, num_inference_steps, hires_scale, hires_strength, hires_mode, hires_steps)
         if hires is None:
             self._resolve_plan(self.sampling_plan(num_inference_steps, guidance_scale, video is not None,
-                                                  (video_length, (height or 768) // 8, (width or 768) // 8), **loop_kw))
+                                                  (video_length, (height or 768) // 8, (width or 768) // 8), sampler=self._sampler(), eta=eta, **loop_kw))
         else:
             # two passes, two plans: both are built and resolved here, before the CLIP tower or the VAE runs
             if video is not None:
@@ -1033,7 +1057,7 @@ class MikuDanceVideoPipeline:
             for what, steps, has_init, (hp, wp), kw in ((f"hires pass 1 ({width_lo} x {height_lo})", num_inference_steps, False, (height_lo, width_lo), loop_kw),
                                                         (f"hires pass 2 ({width or 768} x {height or 768})", steps_hi, True, (height or 768, width or 768), hi_kw)):
                 try:
-                    self._resolve_plan(self.sampling_plan(steps, guidance_scale, has_init, (video_length, hp // 8, wp // 8), **kw))
+                    self._resolve_plan(self.sampling_plan(steps, guidance_scale, has_init, (video_length, hp // 8, wp // 8), sampler=self._sampler(), eta=eta, **kw))
                 except ValueError as e:
                     raise ValueError(f"{what}: {e}") from None
             if scene_motion_lowres_npy is not None and tuple(np.shape(scene_motion_lowres_npy)) != (video_length, 2, height_lo // 8, width_lo // 8):
