@@ -457,6 +457,30 @@ int md_token_tile_f16(const void* x, void* y, int B, int Hh, int Ww, int C, int 
  * with nothing launched and y untouched. */
 int md_latent_resize_f16(const void* x, void* y, int F, int Hi, int Wi, int Ho, int Wo, int mode, void* stream);
 
+/* Seam blending of tiled VAE encode / decode (AutoencoderKL.enable_tiling(); the rules of diffusers 0.24's tiled_encode / tiled_decode): one
+ * launch per tile in the place of blend_v -> blend_h -> crop -> torch.cat -> layout change.
+ * cur: (B, Th, Tw, ldc) fp16 NHWC with C <= ldc valid channels, the tile as the encoder + quant_conv or the decoder left it, updated IN PLACE;
+ * above: (B, Ah, Tw, ldc), the tile above as it stands after its own call, or NULL (Ah is then ignored); left: (B, Th, Lw, ldc), the tile to
+ * the left, likewise, or NULL; dst: fp16 or fp32 (dst_is_f32), element (b, c, y, x) at b sB + c sC + y sY + x sX in elements, as in
+ * md_unpack_nhwc_f16: the caller's final tensor, already offset to the tile's corner.  For every b < B, y < Th, x < Tw, c < C:
+ *   v = cur[y][x]
+ *   if above and y < ev':  v = above[Ah - ev' + y][x] (1 - y / ev') + v (y / ev')      ev' = min(Ah, Th, ev)
+ *   if left  and x < eh':  v = left[y][Lw - eh' + x]  (1 - x / eh') + v (x / eh')      eh' = min(Lw, Tw, eh)
+ *   cur[y][x] = fp16(v)                                 the whole tile: the tiles below and to the right read it
+ *   if y < keep_h and x < keep_w:  dst[b, c, y, x] = v  the cropped part (rounded once to fp16 for an fp16 dst)
+ * Vertical first, then horizontal, both reading the neighbour after ITS blends, the weights from the clamped extents: diffusers' order and
+ * in-place dependence.  An extent of 0 blends nothing.  In place is safe: element (y, x) of cur depends on itself and on other buffers only.
+ * fp32 operations, ONE rounding to fp16 (diffusers rounds after every operation); the weights and sums are carried as pairs of floats, so
+ * a blend that cancels to little is still within an fp16 ulp of the float64 result.  Weight 0 (y = 0 / x = 0) returns the neighbour exactly.
+ * Non-finite inputs give non-finite outputs (0 * Inf, as in torch).  One thread per 8 bytes of channels (ldc % 4 == 0 and cur / above / left
+ * 8-byte aligned) or per pixel (anything else, e.g. the decoder's 3-channel image); no atomics: two calls give the same bits.  Nothing
+ * outside the C valid channels of cur and the keep_h x keep_w window of dst is written; the strides of dst are the caller's word.
+ * cur and dst not NULL; B, Th, Tw, C, ldc positive, C <= ldc; ev, eh >= 0; 1 <= keep_h <= Th, 1 <= keep_w <= Tw; Ah > 0 with above, Lw > 0
+ * with left; every tile below 2^31 elements; cur / above / left 2-byte aligned and dst to its element; cur not overlapping above or left;
+ * MD_ERR_ARG otherwise, with nothing launched and every buffer untouched. */
+int md_tile_blend_f16(void* cur, int ldc, const void* above, int Ah, const void* left, int Lw, void* dst, int dst_is_f32, int B, int Th,
+                      int Tw, int C, int ev, int eh, int keep_h, int keep_w, long sB, long sC, long sY, long sX, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

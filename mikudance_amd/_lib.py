@@ -86,6 +86,8 @@ SIGNATURES = {
     "md_token_mean_f16": (c_int, [P, P, c_int, c_int, c_int, P, P]),
     "md_token_tile_f16": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "md_latent_resize_f16": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "md_tile_blend_f16": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_long, c_long, c_long, c_long, P]),
 }
 
 _lib = None

@@ -28,34 +28,7 @@
 // that error twice, so it is switched off for this file; the fmaf calls stay fused.
 #pragma clang fp contract(off)
 
-struct ff_t {                                                     // the value h + l, |l| <= ulp(h) / 2
-  float h, l;
-};
-
-__host__ __device__ __forceinline__ ff_t ff_fast_sum(float a, float b) {    // |a| >= |b| or a == 0
-  const float s = a + b;
-  return {s, b - (s - a)};
-}
-__host__ __device__ __forceinline__ ff_t ff_sum(float a, float b) {
-  const float s = a + b, bb = s - a;
-  return {s, (a - (s - bb)) + (b - bb)};
-}
-__host__ __device__ __forceinline__ ff_t ff_add(ff_t a, ff_t b) {
-  const ff_t s = ff_sum(a.h, b.h);
-  return ff_fast_sum(s.h, s.l + (a.l + b.l));
-}
-__host__ __device__ __forceinline__ ff_t ff_add(ff_t a, float b) {
-  const ff_t s = ff_sum(a.h, b);
-  return ff_fast_sum(s.h, s.l + a.l);
-}
-__host__ __device__ __forceinline__ ff_t ff_mul(ff_t a, ff_t b) {
-  const float p = a.h * b.h;
-  return ff_fast_sum(p, fmaf(a.h, b.h, -p) + (a.h * b.l + a.l * b.h));
-}
-__host__ __device__ __forceinline__ ff_t ff_mul(ff_t a, float b) {
-  const float p = a.h * b;
-  return ff_fast_sum(p, fmaf(a.h, b, -p) + a.l * b);
-}
+#include "ff_pair.h"
 
 // The taps of output o along one axis: TAPS input indices, all inside [0, ni), and their weights.  rem and den are exact as floats while
 // no < 2^23 (beyond that the fraction is an fp32 quotient, no worse than a rounded coordinate); q (den) - rem is then exact too.

@@ -38,6 +38,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
          scene_motion_lowres_npy=camera_to_scene_motion at the first pass's grid)
                      (an addition: two-pass high-resolution sampling, the whole schedule at -W / S x -H / S, the latents enlarged on the GPU,
                      the tail of the schedule at -W x -H; default 1 = off)
+    pipe(..., vae_tiling=--vae_tiling, vae_tile_size=--vae_tile_size)
+                     (an addition: tiled VAE encode / decode, diffusers' enable_vae_tiling; default off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -206,7 +208,17 @@ def parse_args(argv=None):
                         help="(addition) with --hires_scale: how the latents are enlarged")
     parser.add_argument("--hires_steps", type=int, default=None,
                         help="(addition) with --hires_scale: steps of the second pass's schedule before --hires_strength cuts it; default --steps")
+    parser.add_argument("--vae_tiling", action="store_true",
+                        help="(addition) tiled VAE encode / decode (diffusers' enable_vae_tiling): overlapping tiles with blended seams, so that "
+                             "memory and the VAE's attention scale with the tile and not with -W x -H.  A different result by design (each "
+                             "tile is normalised on its own); image quality on real weights has not been assessed.  Not with --video_decoder")
+    parser.add_argument("--vae_tile_size", type=int, default=None, metavar="PIXELS",
+                        help="(addition) with --vae_tiling: the tile side in image pixels, a multiple of 32; default: the VAE's sample_size")
     args = parser.parse_args(argv)
+    if args.vae_tile_size is not None and not args.vae_tiling:
+        parser.error(f"--vae_tile_size {args.vae_tile_size} needs --vae_tiling")
+    if args.vae_tiling and args.video_decoder:
+        parser.error("--vae_tiling cannot be combined with --video_decoder: the temporal decoder has no tiling")
     if args.strength != 1.0 and args.init_video is None:
         parser.error(f"--strength {args.strength} needs --init_video")
     if args.hires_scale != 1.0 and args.init_video is not None:
@@ -322,7 +334,7 @@ def main(argv=None):
                deep_cache_interval=args.deep_cache_interval, deep_cache_depth=args.deep_cache_depth,
                guidance_interval=args.guidance_interval, uncond_cache_interval=args.uncond_cache_interval,
                hires_scale=args.hires_scale, hires_strength=args.hires_strength, hires_mode=args.hires_mode, hires_steps=args.hires_steps,
-               scene_motion_lowres_npy=scene_motion_lowres_npy)
+               scene_motion_lowres_npy=scene_motion_lowres_npy, vae_tiling=args.vae_tiling, vae_tile_size=args.vae_tile_size)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

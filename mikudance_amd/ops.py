@@ -644,6 +644,35 @@ def latent_resize(x, F, hi, wi, ho, wo, mode="bicubic", out=None):
     return out
 
 
+def tile_blend(cur, dst, c, above=None, left=None, extent=(0, 0)):
+    """Seam blending of one tile of a tiled VAE pass (md_tile_blend_f16): cur (B, Th, Tw, ldc) contiguous NHWC fp16 with c <= ldc valid channels is
+    blended IN PLACE over its first extent[0] rows with the last rows of `above` (B, Ah, Tw, ldc) and then over its first extent[1] columns with
+    the last columns of `left` (B, Th, Lw, ldc), both as they stand after their own calls (the extents clamped to the tiles' sizes), and its
+    top-left keep_h x keep_w corner is written to dst: a (B, c, keep_h, keep_w) fp16 / fp32 VIEW of the final NCHW tensor at the tile's place, any
+    strides.  Returns cur."""
+    _chk(cur, "cur"); _chk(above, "above"); _chk(left, "left")
+    if cur.dim() != 4 or not cur.is_contiguous():
+        raise _lib.MdanceHipError(f"tile_blend: cur must be a contiguous (B, Th, Tw, ldc) tensor, got shape {tuple(cur.shape)} strides {tuple(cur.stride())}")
+    B, Th, Tw, ldc = cur.shape
+    if above is not None and (above.dim() != 4 or not above.is_contiguous() or (above.shape[0], above.shape[2], above.shape[3]) != (B, Tw, ldc)):
+        raise _lib.MdanceHipError(f"tile_blend: above must be contiguous (B, Ah, Tw, ldc) = ({B}, *, {Tw}, {ldc}), got {tuple(above.shape)}")
+    if left is not None and (left.dim() != 4 or not left.is_contiguous() or (left.shape[0], left.shape[1], left.shape[3]) != (B, Th, ldc)):
+        raise _lib.MdanceHipError(f"tile_blend: left must be contiguous (B, Th, Lw, ldc) = ({B}, {Th}, *, {ldc}), got {tuple(left.shape)}")
+    if not dst.is_cuda or dst.dtype not in (torch.float16, torch.float32):
+        raise _lib.MdanceHipError("tile_blend: dst must be a CUDA fp16/fp32 tensor")
+    if dst.dim() != 4 or dst.shape[0] != B or dst.shape[1] != c or not (1 <= dst.shape[2] <= Th and 1 <= dst.shape[3] <= Tw):
+        raise _lib.MdanceHipError(f"tile_blend: dst must be a (B, c, keep_h <= Th, keep_w <= Tw) = ({B}, {c}, <= {Th}, <= {Tw}) view, got {tuple(dst.shape)}")
+    sB, sC, sY, sX = dst.stride()
+    keep_h, keep_w = dst.shape[2:]
+    ev, eh = extent
+    n = B * Th * Tw * c
+    _lib.call("md_tile_blend_f16", cur.data_ptr(), ldc, _p(above), 0 if above is None else above.shape[1], _p(left),
+              0 if left is None else left.shape[2], dst.data_ptr(), int(dst.dtype == torch.float32), B, Th, Tw, c, int(ev), int(eh), keep_h, keep_w,
+              sB, sC, sY, sX, _st(),
+              meta=(f"tile_blend B={B} {Th}x{Tw} C={c}", 0.0, 4.0 * n + dst.element_size() * B * c * keep_h * keep_w))
+    return cur
+
+
 def blur_kernel_size(sigma, n):
     """Taps of SEG's Gaussian along a grid axis of n tokens: the official gaussian_blur_2d's ceil(6 sigma) + 1 - ceil(6 sigma) % 2, clamped to
     the largest odd number a reflect-padded axis of n allows (n if n is odd, else n + 1); 1 for n = 1."""

@@ -15,6 +15,7 @@ Result-preserving reductions (proven identical on the
   * unconditional rows ignore the bank -> one attention pass with a per-row K/V source replaces two.
 `reference_reuse=False` restores the literal per-step evaluation (same results, for A/B timing).
 """
+import contextlib
 import math
 import os
 from dataclasses import dataclass, replace
@@ -140,6 +141,51 @@ class MikuDanceVideoPipeline:
     @property
     def _execution_device(self):
         return self._device
+
+    # ---- VAE tiling / slicing: diffusers' pipeline-level names, forwarded to the VAE (AutoencoderKL.enable_tiling / enable_slicing)
+    def enable_vae_tiling(self):
+        self.vae.enable_tiling()
+
+    def disable_vae_tiling(self):
+        self.vae.disable_tiling()
+
+    def enable_vae_slicing(self):
+        self.vae.enable_slicing()
+
+    def disable_vae_slicing(self):
+        self.vae.disable_slicing()
+
+    @contextlib.contextmanager
+    def vae_tiling_scope(self, sizes, vae_tiling=False, vae_tile_size=None):
+        """__call__'s vae_tiling= / vae_tile_size=: checks them against the (height, width) pairs in `sizes` -- every image size the call
+        encodes and decodes at -- and holds the VAE's tiling state for the duration of the `with` block; the state the VAE had comes back
+        afterwards.  With the defaults the VAE's state is not changed (whatever enable_vae_tiling() set stays in force, and its tile grid
+        is checked here all the same).  ValueError, before
+        the block runs, for a vae_tiling that is no bool, a vae_tile_size that is no positive multiple of 32 or comes without tiling, a VAE
+        without tiling (the temporal decoder) and a tile grid the VAE's operators cannot run (AutoencoderKL.tile_grid names the tile)."""
+        if not isinstance(vae_tiling, bool):
+            raise ValueError(f"vae_tiling must be True or False, got {vae_tiling!r}")
+        vae = self.vae
+        if not vae_tiling and vae_tile_size is None and not (getattr(vae, "use_tiling", False) and hasattr(vae, "tile_grid")):
+            yield
+            return
+        if not all(hasattr(vae, a) for a in ("enable_tiling", "set_tile_size", "tile_grid")):
+            raise ValueError(f"vae_tiling / vae_tile_size: {type(vae).__name__} has no tiling (AutoencoderKL has; the temporal decoder has none)")
+        if not (vae_tiling or vae.use_tiling):
+            raise ValueError(f"vae_tile_size={vae_tile_size!r} needs vae_tiling=True (or enable_vae_tiling())")
+        saved = (vae.use_tiling, vae.tile_sample_min_size, vae.tile_latent_min_size)
+        try:
+            if vae_tile_size is not None:
+                vae.set_tile_size(vae_tile_size)
+            vae.enable_tiling(vae_tiling or vae.use_tiling)
+            for h, w in sizes:
+                if max(h, w) > vae.tile_sample_min_size:
+                    vae.tile_grid(h, w, encode=True)
+                if max(h, w) // self.vae_scale_factor > vae.tile_latent_min_size:
+                    vae.tile_grid(h // self.vae_scale_factor, w // self.vae_scale_factor, encode=False)
+            yield
+        finally:
+            vae.use_tiling, vae.tile_sample_min_size, vae.tile_latent_min_size = saved
 
     def progress_bar(self, iterable=None, total=None):
         from tqdm import tqdm
@@ -995,8 +1041,19 @@ class MikuDanceVideoPipeline:
                  pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid",), kv_downsample=1,
                  kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), tile_attention=1,
                  tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1,
-                 hires_scale=1, hires_strength=0.5, hires_mode="bicubic", hires_steps=None, scene_motion_lowres_npy=None, **kwargs):
+                 hires_scale=1, hires_strength=0.5, hires_mode="bicubic", hires_steps=None, scene_motion_lowres_npy=None, vae_tiling=False,
+                 vae_tile_size=None, **kwargs):
         """The reference call (src/pipelines/pipeline_mikudance.py:362-704) with denoise()'s sampling keywords (see its docstring), and:
+
+        vae_tiling          True: the VAE encodes and decodes this call's images tile by tile (AutoencoderKL.enable_tiling(): diffusers' tiled
+                            VAE, overlapping tiles with blended seams; memory and the mid-block attention then scale with the tile, not the
+                            image).  A different result by design, each tile's GroupNorm and attention see that tile only; image quality on
+                            real weights has not been assessed.  For this call only: the VAE's own state (enable_vae_tiling()) comes back
+                            afterwards.  False (the default): the VAE is left as it is, and the call is bitwise what it was.  ValueError,
+                            before the CLIP tower or the VAE runs, for a tile grid the VAE cannot run at this call's sizes (both of them under
+                            hires_scale) and for a VAE without tiling (video_decoder)
+        vae_tile_size       the tile side in image pixels, a positive multiple of 32 (sets tile_sample_min_size and tile_latent_min_size
+                            together); None: the VAE's own (config.sample_size).  Needs tiling on
 
         hires_scale         two-pass high-resolution sampling (the "hires fix" of the SD-1.5 front ends), an opt-in APPROXIMATION of the
                             one-pass clip: a finite number >= 1.  With s > 1 the WHOLE schedule is sampled at the low size
@@ -1068,44 +1125,47 @@ class MikuDanceVideoPipeline:
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
                           "fails for two or more windows per batch, pipeline_mikudance.py:662); results are those of context_batch_size = 1")
             self._warned_context_batch = True
-        height = height or 768
-        width = width or 768
-        device = self._execution_device
-        do_cfg = guidance_scale > 1.0
-        batch_size = 1
-        image_prompt_embeds = self.clip_embeds(ref_image)
-        if do_cfg:
-            image_prompt_embeds = torch.cat([torch.zeros_like(image_prompt_embeds), image_prompt_embeds], dim=0)
-        images = (ref_image, ref_skel_image, [list(tgt_pose_images), list(tgt_face_images), list(tgt_hand_images)])
-        noise_args = (video_length, image_prompt_embeds.dtype, device, generator)
-        window_args = (context_schedule, context_frames, context_stride, context_overlap)
-        if hires is None:
-            latents = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width, height, *noise_args)
-            # (the noise is drawn before the video-to-video frames are encoded, so the generator stream does not depend on video=)
-            ref_latents, init_latents = self._condition_latents(*images, video, scene_motion_npy, height, width, video_length)
-            latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, *window_args, callback,
-                                   callback_steps, eta=eta, generator=generator, init_latents=init_latents, **loop_kw)
-        else:
-            # the noise of the low size FIRST, then of the full size (the order the docstring states); the images of each size through the VAE
-            # in batches of their own; the CLIP embeddings above serve both passes
-            noise_lo = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width_lo, height_lo, *noise_args)
-            noise = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width, height, *noise_args)
-            motion_lo = scene_motion_lowres_npy
-            if motion_lo is None:
-                motion_lo = self.lowres_scene_motion(scene_motion_npy, height_lo // 8, width_lo // 8)
-            ref_latents_lo, _ = self._condition_latents(*images, None, motion_lo, height_lo, width_lo, video_length)
-            ref_latents, _ = self._condition_latents(*images, None, scene_motion_npy, height, width, video_length)
-            latents = self.denoise(noise_lo, ref_latents_lo, image_prompt_embeds, num_inference_steps, guidance_scale, *window_args, callback,
-                                   callback_steps, eta=eta, generator=generator, init_latents=None, **loop_kw)
-            latents = self.upscale_latents(latents, height, width, hires_mode)
-            callback_hi = None if callback is None else (lambda i, t, x: callback(num_inference_steps + i, t, x))
-            latents = self.denoise(noise, ref_latents, image_prompt_embeds, steps_hi, guidance_scale, *window_args, callback_hi,
-                                   callback_steps, eta=eta, generator=generator, init_latents=latents, **hi_kw)
-        if interpolation_factor > 0:
-            latents = self.interpolate_latents(latents, interpolation_factor, device)
-        images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)
-        if output_type == "tensor":
-            images = torch.from_numpy(images)
-        if not return_dict:
-            return images
-        return MikuDanceVideoPipelineOutput(videos=images)
+        # vae_tiling / vae_tile_size: checked against every size this call runs the VAE at, in force inside the block only
+        sizes = [(height or 768, width or 768)] + ([] if hires is None else [(hires[0], hires[1])])
+        with self.vae_tiling_scope(sizes, vae_tiling, vae_tile_size):
+            height = height or 768
+            width = width or 768
+            device = self._execution_device
+            do_cfg = guidance_scale > 1.0
+            batch_size = 1
+            image_prompt_embeds = self.clip_embeds(ref_image)
+            if do_cfg:
+                image_prompt_embeds = torch.cat([torch.zeros_like(image_prompt_embeds), image_prompt_embeds], dim=0)
+            images = (ref_image, ref_skel_image, [list(tgt_pose_images), list(tgt_face_images), list(tgt_hand_images)])
+            noise_args = (video_length, image_prompt_embeds.dtype, device, generator)
+            window_args = (context_schedule, context_frames, context_stride, context_overlap)
+            if hires is None:
+                latents = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width, height, *noise_args)
+                # (the noise is drawn before the video-to-video frames are encoded, so the generator stream does not depend on video=)
+                ref_latents, init_latents = self._condition_latents(*images, video, scene_motion_npy, height, width, video_length)
+                latents = self.denoise(latents, ref_latents, image_prompt_embeds, num_inference_steps, guidance_scale, *window_args, callback,
+                                       callback_steps, eta=eta, generator=generator, init_latents=init_latents, **loop_kw)
+            else:
+                # the noise of the low size FIRST, then of the full size (the order the docstring states); the images of each size through the VAE
+                # in batches of their own; the CLIP embeddings above serve both passes
+                noise_lo = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width_lo, height_lo, *noise_args)
+                noise = self.prepare_latents(batch_size * num_images_per_prompt, self.denoising_unet.in_channels, width, height, *noise_args)
+                motion_lo = scene_motion_lowres_npy
+                if motion_lo is None:
+                    motion_lo = self.lowres_scene_motion(scene_motion_npy, height_lo // 8, width_lo // 8)
+                ref_latents_lo, _ = self._condition_latents(*images, None, motion_lo, height_lo, width_lo, video_length)
+                ref_latents, _ = self._condition_latents(*images, None, scene_motion_npy, height, width, video_length)
+                latents = self.denoise(noise_lo, ref_latents_lo, image_prompt_embeds, num_inference_steps, guidance_scale, *window_args, callback,
+                                       callback_steps, eta=eta, generator=generator, init_latents=None, **loop_kw)
+                latents = self.upscale_latents(latents, height, width, hires_mode)
+                callback_hi = None if callback is None else (lambda i, t, x: callback(num_inference_steps + i, t, x))
+                latents = self.denoise(noise, ref_latents, image_prompt_embeds, steps_hi, guidance_scale, *window_args, callback_hi,
+                                       callback_steps, eta=eta, generator=generator, init_latents=latents, **hi_kw)
+            if interpolation_factor > 0:
+                latents = self.interpolate_latents(latents, interpolation_factor, device)
+            images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)
+            if output_type == "tensor":
+                images = torch.from_numpy(images)
+            if not return_dict:
+                return images
+            return MikuDanceVideoPipelineOutput(videos=images)

@@ -9,8 +9,14 @@ same C-ABI kernels as the UNets: NHWC 3x3 convs (the encoder's downsampler pads 
 GEMMs.  The mid-block attention has ONE head of 512 channels -- too wide for the flash kernel's register tile -- so it runs
 per frame as QK^T GEMM -> row softmax (md_softmax_rows_f16) -> PV GEMM.
 
+Tiling and slicing (`enable_tiling` / `enable_slicing`, `tiled_encode` / `tiled_decode`; off by default): diffusers 0.24's names and rules, restated
+from the published algorithm -- overlapping tiles of `tile_sample_min_size` pixels / `tile_latent_min_size` latents, each through the whole
+encoder + quant_conv or post_quant_conv + decoder, the seams blended over `tile_overlap_factor` of a tile, vertical then horizontal, on the
+neighbour as blended.  One md_tile_blend_f16 launch per tile blends, crops and writes into the final NCHW tensor (`tile_grid` is the geometry).
+A tiled result DIFFERS from the untiled one by design: every tile's GroupNorm and attention see that tile only.
+
 Parity: the oracle's restatement (oracle/cpu_ref.py vae_*) follows the published diffusers semantics; diffusers is not in
-/root/reference, so this row is PARITY UNPINNED."""
+/root/reference, so this row -- tiling and slicing included -- is PARITY UNPINNED."""
 import json
 import os
 from types import SimpleNamespace
@@ -239,6 +245,10 @@ class AutoencoderKL(_Packed):
                                       latent_channels=latent_channels, layers_per_block=2, norm_num_groups=GROUPS, act_fn="silu",
                                       scaling_factor=scaling_factor, sample_size=sample_size)
         self.zc = latent_channels
+        self.use_tiling = self.use_slicing = False
+        self.tile_sample_min_size = sample_size
+        self.tile_latent_min_size = int(sample_size / 2 ** (len(chans) - 1))
+        self.tile_overlap_factor = 0.25
         self.encoder = Encoder(in_channels, latent_channels, chans)
         self.decoder = Decoder(latent_channels, out_channels, chans)
         self.quant_conv = Conv(2 * latent_channels, 2 * latent_channels, 1)
@@ -256,10 +266,8 @@ class AutoencoderKL(_Packed):
                     pq=pad_k(self.post_quant_conv.weight), pqb=packing.vec(self.post_quant_conv.bias, dev))
 
     # ---- reference-facing interface (NCHW tensors in / out, like diffusers)
-    @torch.no_grad()
-    def encode(self, x, return_dict=True):
-        if x.dim() != 4 or x.shape[2] % 8 or x.shape[3] % 8:
-            raise ValueError(f"AutoencoderKL.encode expects (B, C, H, W) with H, W multiples of 8, got {tuple(x.shape)}")
+    def _moments_nhwc(self, x):
+        """x (B, C, H, W), any strides (a tile is a view) -> encoder + quant_conv -> (B, H/f, W/f, 64) fp16 NHWC, 2z valid channels."""
         pk = self.packed()
         B, C, H, W = x.shape
         st = x.stride()
@@ -267,9 +275,46 @@ class AutoencoderKL(_Packed):
         h = self.encoder(x64)                                                            # (B, h, w, 64), 2z valid
         m64 = torch.zeros_like(h)
         ops.gemm(tokens(h), pk["q"], bias=pk["qb"], out=tokens(m64)[:, :2 * self.zc])
-        moments = torch.empty((B, 2 * self.zc, H // 8, W // 8), device=x.device, dtype=x.dtype if x.dtype != torch.float64 else torch.float32)
-        so = moments.stride()
-        ops.unpack_nhwc(m64, moments, B, 1, (so[0], 0, so[1], so[2], so[3]), 2 * self.zc, H // 8, W // 8)
+        return m64
+
+    def _image_nhwc(self, z):
+        """z (B, z, h, w), any strides -> post_quant_conv + decoder -> (B, f h, f w, out_channels) fp16 NHWC."""
+        pk = self.packed()
+        B, C, h, w = z.shape
+        st = z.stride()
+        z64 = ops.pack_nhwc(z, B, 1, (st[0], 0, st[1], st[2], st[3]), 0, C, 64, h, w)
+        p64 = torch.zeros_like(z64)
+        ops.gemm(tokens(z64), pk["pq"], bias=pk["pqb"], out=tokens(p64)[:, :self.zc])
+        return self.decoder(p64)                                                         # (B, 8h, 8w, 3)
+
+    @staticmethod
+    def _out_dtype(t):
+        return t.dtype if t.dtype != torch.float64 else torch.float32
+
+    def _run(self, x, out, encode, tiled):
+        """One untiled or tiled pass of x into `out` (a view of the final NCHW tensor), image by image under enable_slicing()."""
+        B = x.shape[0]
+        for sl in ([slice(b, b + 1) for b in range(B)] if self.use_slicing and B > 1 else [slice(0, B)]):
+            xs, os_ = x[sl], out[sl]
+            so = os_.stride()
+            n, strides, size = xs.shape[0], (so[0], 0, so[1], so[2], so[3]), tuple(out.shape[1:])
+            if tiled:
+                self._tiled(xs, os_, encode)
+            elif encode:
+                ops.unpack_nhwc(self._moments_nhwc(xs), os_, n, 1, strides, *size)          # 2z of 64 channels
+            else:
+                ops.unpack_nhwc(self._image_nhwc(xs), os_, n, 1, strides, *size)            # the image, pitch out_channels
+
+    @torch.no_grad()
+    def encode(self, x, return_dict=True):
+        if x.dim() != 4 or x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError(f"AutoencoderKL.encode expects (B, C, H, W) with H, W multiples of 8, got {tuple(x.shape)}")
+        B, C, H, W = x.shape
+        tiled = self.use_tiling and max(H, W) > self.tile_sample_min_size
+        if tiled:
+            self.tile_grid(H, W, encode=True)                                            # every refusal before the first launch
+        moments = torch.empty((B, 2 * self.zc, H // 8, W // 8), device=x.device, dtype=self._out_dtype(x))
+        self._run(x, moments, True, tiled)
         out = SimpleNamespace(latent_dist=DiagonalGaussian(moments))
         return out if return_dict else (out.latent_dist,)
 
@@ -277,16 +322,130 @@ class AutoencoderKL(_Packed):
     def decode(self, z, return_dict=True):
         if z.dim() != 4 or z.shape[1] != self.zc:
             raise ValueError(f"AutoencoderKL.decode expects (B, {self.zc}, h, w), got {tuple(z.shape)}")
-        pk = self.packed()
         B, C, h, w = z.shape
-        st = z.stride()
-        z64 = ops.pack_nhwc(z, B, 1, (st[0], 0, st[1], st[2], st[3]), 0, C, 64, h, w)
-        p64 = torch.zeros_like(z64)
-        ops.gemm(tokens(z64), pk["pq"], bias=pk["pqb"], out=tokens(p64)[:, :self.zc])
-        y = self.decoder(p64)                                                            # (B, 8h, 8w, 3)
-        img = torch.empty((B, y.shape[-1], 8 * h, 8 * w), device=z.device, dtype=z.dtype if z.dtype != torch.float64 else torch.float32)
-        so = img.stride()
-        ops.unpack_nhwc(y, img, B, 1, (so[0], 0, so[1], so[2], so[3]), y.shape[-1], 8 * h, 8 * w)
+        tiled = self.use_tiling and max(h, w) > self.tile_latent_min_size
+        if tiled:
+            self.tile_grid(h, w, encode=False)
+        img = torch.empty((B, self.config.out_channels, 8 * h, 8 * w), device=z.device, dtype=self._out_dtype(z))
+        self._run(z, img, False, tiled)
+        out = SimpleNamespace(sample=img)
+        return out if return_dict else (img,)
+
+    # ---- tiling and slicing (diffusers 0.24: enable_tiling / enable_slicing, tiled_encode / tiled_decode)
+    def enable_tiling(self, use_tiling=True):
+        """encode / decode of an input with a side above tile_sample_min_size pixels / tile_latent_min_size latents run tile by tile."""
+        self.use_tiling = bool(use_tiling)
+
+    def disable_tiling(self):
+        self.enable_tiling(False)
+
+    def enable_slicing(self):
+        """encode / decode of a batch run one image per encoder / decoder call (per-image arithmetic: the VAE never mixes samples)."""
+        self.use_slicing = True
+
+    def disable_slicing(self):
+        self.use_slicing = False
+
+    def set_tile_size(self, pixels):
+        """Both tile sizes from one number of image pixels: tile_sample_min_size = pixels, tile_latent_min_size = pixels / f.  A multiple of 4 f
+        (32 for the 8x VAE), so that the overlap and the blend extent are whole latents."""
+        f = 2 ** (len(self.config.block_out_channels) - 1)
+        if isinstance(pixels, bool) or not isinstance(pixels, int) or pixels < 4 * f or pixels % (4 * f):
+            raise ValueError(f"AutoencoderKL: the tile size must be a positive multiple of {4 * f} image pixels, got {pixels!r}")
+        self.tile_sample_min_size, self.tile_latent_min_size = pixels, pixels // f
+
+    def tile_grid(self, n_rows, n_cols, encode):
+        """The tile geometry of tiled_encode (an image of n_rows x n_cols pixels) or tiled_decode (latents): (rows, cols, extent), rows / cols
+        lists of (start, size, out_start, keep) per tile along the axis -- the tile reads input [start, start + size), its output is
+        blended over `extent` output elements with the tile before it and its first `keep` output elements land at out_start.
+        Tiles start every overlap = int(tile (1 - tile_overlap_factor)) inputs and are `tile` long, shorter at the far edge; extent =
+        int(out_tile tile_overlap_factor) and keep <= limit = out_tile - extent, out_tile the other space's tile size (diffusers 0.24).
+        ValueError for a grid the operators cannot run, naming the first such tile and input sizes that work: an image tile's sides must be
+        multiples of f = 8 and every tile's latent map h x w a multiple of 8 tokens (the mid-block attention's row softmax and GEMMs; the
+        convolutions and GroupNorms take any non-empty map, down to 1 x 1), and the kept parts must fill the output exactly."""
+        f = 2 ** (len(self.config.block_out_channels) - 1)
+        tile, out_tile = (self.tile_sample_min_size, self.tile_latent_min_size) if encode else (self.tile_latent_min_size, self.tile_sample_min_size)
+        what = "tiled_encode" if encode else "tiled_decode"
+        fac = self.tile_overlap_factor
+        if not (isinstance(tile, int) and isinstance(out_tile, int) and tile > 0 and out_tile > 0 and 0.0 <= fac < 1.0):
+            raise ValueError(f"AutoencoderKL.{what}: tile sizes must be positive integers and tile_overlap_factor in [0, 1), got "
+                             f"{self.tile_sample_min_size!r}, {self.tile_latent_min_size!r}, {fac!r}")
+        overlap, extent = int(tile * (1 - fac)), int(out_tile * fac)
+        limit = out_tile - extent
+        if overlap < 1 or (limit * f != overlap if encode else overlap * f != limit):
+            raise ValueError(f"AutoencoderKL.{what}: tile_sample_min_size {self.tile_sample_min_size}, tile_latent_min_size {self.tile_latent_min_size} and "
+                             f"tile_overlap_factor {fac} do not agree (a tile step of {overlap} against a kept part of {limit}, factor {f}); "
+                             f"set_tile_size(a multiple of {4 * f}) gives sizes that do")
+
+        def axis(n):
+            out, tiles = 0, []
+            for start in range(0, n, overlap):
+                size = min(tile, n - start)
+                keep = min(limit, size // f if encode else size * f)
+                tiles.append((start, size, out, keep))
+                out += keep
+            return tiles
+
+        def bad(rows, cols):
+            for i, (_, th, _, _) in enumerate(rows):
+                for j, (_, tw, _, _) in enumerate(cols):
+                    if encode and (th % f or tw % f):
+                        return i, j, th, tw, f"its sides must be multiples of {f}"
+                    lh, lw = (th // f, tw // f) if encode else (th, tw)
+                    if lh < 1 or lw < 1 or (lh * lw) % 8:
+                        return i, j, th, tw, f"its {lh} x {lw} latent map must be a multiple of 8 tokens"
+            return None
+
+        rows, cols = axis(n_rows), axis(n_cols)
+        first = bad(rows, cols)
+        if first is not None:
+            i, j, th, tw, why = first
+            step = f if encode else 1
+            near = lambda n, ok: [m for m in (next((m for m in range(n, 0, -step) if ok(m)), None),
+                                               next((m for m in range(n, n + 2 * tile + 1, step) if ok(m)), None)) if m is not None]
+            good_r = near(n_rows, lambda m: bad(axis(m), cols) is None)
+            good_c = near(n_cols, lambda m: bad(rows, axis(m)) is None)
+            unit = "pixels" if encode else "latents"
+            raise ValueError(f"AutoencoderKL.{what}: tile (row {i}, column {j}) of the {n_rows} x {n_cols} input is {th} x {tw} {unit}: {why}.  "
+                             f"With {n_cols} columns, {good_r or 'no nearby number of'} rows work; with {n_rows} rows, {good_c or 'no nearby number of'} "
+                             f"columns work (tiles of {tile} every {overlap} {unit}).")
+        return rows, cols, extent
+
+    def _tiled(self, x, out, encode):
+        """x -> out tile by tile.  Alive at any time: the row of blended tiles above (one entry per column, replaced as the row below is
+        made) -- its entry to the left of the current tile is the left neighbour."""
+        rows, cols, extent = self.tile_grid(x.shape[2], x.shape[3], encode)
+        c = out.shape[1]
+        line = [None] * len(cols)
+        for i, (y0, th, oy, kh) in enumerate(rows):
+            for j, (x0, tw, ox, kw) in enumerate(cols):
+                view = x[:, :, y0:y0 + th, x0:x0 + tw]
+                cur = self._moments_nhwc(view) if encode else self._image_nhwc(view)
+                ops.tile_blend(cur, out[:, :, oy:oy + kh, ox:ox + kw], c, above=line[j] if i else None, left=line[j - 1] if j else None,
+                               extent=(extent, extent))
+                line[j] = cur
+
+    @torch.no_grad()
+    def tiled_encode(self, x, return_dict=True):
+        """encode tile by tile, whatever the size of x (diffusers' tiled_encode): the blend runs on the 2z moments."""
+        if x.dim() != 4 or x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError(f"AutoencoderKL.tiled_encode expects (B, C, H, W) with H, W multiples of 8, got {tuple(x.shape)}")
+        B, C, H, W = x.shape
+        rows, cols, _ = self.tile_grid(H, W, encode=True)
+        moments = torch.empty((B, 2 * self.zc, rows[-1][2] + rows[-1][3], cols[-1][2] + cols[-1][3]), device=x.device, dtype=self._out_dtype(x))
+        self._run(x, moments, True, True)
+        out = SimpleNamespace(latent_dist=DiagonalGaussian(moments))
+        return out if return_dict else (out.latent_dist,)
+
+    @torch.no_grad()
+    def tiled_decode(self, z, return_dict=True):
+        """decode tile by tile, whatever the size of z (diffusers' tiled_decode)."""
+        if z.dim() != 4 or z.shape[1] != self.zc:
+            raise ValueError(f"AutoencoderKL.tiled_decode expects (B, {self.zc}, h, w), got {tuple(z.shape)}")
+        rows, cols, _ = self.tile_grid(z.shape[2], z.shape[3], encode=False)
+        img = torch.empty((z.shape[0], self.config.out_channels, rows[-1][2] + rows[-1][3], cols[-1][2] + cols[-1][3]), device=z.device,
+                          dtype=self._out_dtype(z))
+        self._run(z, img, False, True)
         out = SimpleNamespace(sample=img)
         return out if return_dict else (img,)
 
