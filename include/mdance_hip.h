@@ -481,6 +481,26 @@ int md_latent_resize_f16(const void* x, void* y, int F, int Hi, int Wi, int Ho, 
 int md_tile_blend_f16(void* cur, int ldc, const void* above, int Ah, const void* left, int Lw, void* dst, int dst_is_f32, int B, int Th,
                       int Tw, int C, int ev, int eh, int keep_h, int keep_w, long sB, long sC, long sY, long sX, void* stream);
 
+/* The pipeline's output boundary: decoded frames -> the uint8 H x W x C bytes every writer takes, one launch in the place of the reference's
+ * (video / 2 + 0.5).clamp(0, 1) (three elementwise passes), the permuted copy, the fp32 host array and the writer's (x * 255).astype(uint8).
+ * src: fp16, or fp32 with src_is_f32, element (b, c, y, x) at b sB + c sC + y sY + x sX in elements: the decoders' own NHWC result (sC = 1,
+ * sX = ldc >= C), a finished NCHW tensor (sX = 1), or any other strided view.  dst: bytes, (b, y, x, c) at b dB + y dY + x C + c: packed
+ * H x W x C frames whose row pitch dY and frame pitch dB are the caller's, so a frame can be written straight into a larger canvas.
+ * The arithmetic is the reference's chain operation by operation, not the single expression trunc(clamp(127.5 v + 127.5)):
+ *   f32_math = 0 (fp16 tensors):  a = fp16(v / 2);  s = fp16(a + 0.5), one round-to-nearest-even;  s clamped to [0, 1];  q = fp32(s) * 255
+ *                                 rounded to fp32;  the byte is q truncated toward zero
+ *   f32_math = 1 (an fp32 VAE boundary):  the same steps with every intermediate in fp32; an fp16 source converts exactly
+ * src_is_f32 = 1 requires f32_math = 1.  +Inf gives 255 and -Inf gives 0.  NaN gives 0: the float path's cast of a NaN to uint8 is undefined
+ * (C and numpy), so this value is a choice of this entry point.
+ * One thread per 4 pixels of a row; 8- / 16-byte loads where those are contiguous and aligned in src (sX = 1, or sC = 1 with sX = C), strided
+ * loads otherwise; 4-byte stores where the thread's 4 C bytes start on a 4-byte boundary, byte stores otherwise.  256 threads, at most 2048
+ * blocks, a grid-stride loop past that; no atomics: two calls give the same bits.  Nothing outside the B H rows of W C bytes of dst is
+ * written; the strides of src are the caller's word.
+ * src and dst not NULL; C in 1..4; B, H, W positive and B*H*W within int; src_is_f32 and f32_math 0 or 1; dY >= W C; dB >= (H - 1) dY + W C;
+ * src aligned to its element (dst needs no alignment); MD_ERR_ARG otherwise, with nothing launched and dst untouched. */
+int md_frames_u8(const void* src, int src_is_f32, int f32_math, void* dst, int B, int H, int W, int C, long sB, long sC, long sY, long sX,
+                 long dB, long dY, void* stream);
+
 /* Persistent launchers (gemm_sp_kernel behind md_gemm_f16 / md_conv*_f16) start one workgroup per CU of the device.  A caller that launches
  * on a stream created with a CU mask (hipExtStreamCreateWithCUMask: a partition of the chip shared with another stream) tells the
  * library how many CUs that stream owns: grids and the tile-choice model then use `ncu` (a multiple of 8: the same number of CUs on each

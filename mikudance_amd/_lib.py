@@ -88,6 +88,7 @@ SIGNATURES = {
     "md_latent_resize_f16": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "md_tile_blend_f16": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_long, c_long, c_long, c_long, P]),
+    "md_frames_u8": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_long, c_long, P]),
 }
 
 _lib = None

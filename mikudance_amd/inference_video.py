@@ -40,6 +40,8 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      the tail of the schedule at -W x -H; default 1 = off)
     pipe(..., vae_tiling=--vae_tiling, vae_tile_size=--vae_tile_size)
                      (an addition: tiled VAE encode / decode, diffusers' enable_vae_tiling; default off)
+    pipe(..., output_type="uint8") + save_frames_grid_u8 with --u8_output
+                     (an addition: frames quantised on the GPU and kept as bytes up to the writer; the same file; default off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
     pipe(ref_image, ref_skel, pose, face, hand, scene_motion, W, H, F, steps, cfg, generator)      (:211-224)
     save_videos_grid(cat([ref, pose, video]), ".../{skel}_{ref}_{H}x{W}_{cfg}_{time}.mp4", n_rows=3, fps)     (:228-234)
@@ -58,7 +60,8 @@ from PIL import Image
 from . import (AutoencoderKL, AutoencoderKLTemporalDecoder, CLIPVisionModelWithProjection, DDIMScheduler, DPMSolverMultistepScheduler,
                MikuDanceVideoPipeline, UNet2DConditionModel, UNet2DConditionModelPlain, UNet3DConditionModel, UniPCMultistepScheduler)
 from .free_init import FILTERS as FREE_INIT_FILTERS
-from .io_utils import frames_to_tensor, get_fps, load_config, read_frames, resize_depth, save_videos_grid, to_container
+from .io_utils import (frames_to_tensor, frames_to_u8, get_fps, load_config, read_frames, resize_depth, save_frames_grid_u8, save_videos_grid,
+                       to_container)
 from .scene_motion import camera_to_scene_motion
 
 
@@ -214,6 +217,9 @@ def parse_args(argv=None):
                              "tile is normalised on its own); image quality on real weights has not been assessed.  Not with --video_decoder")
     parser.add_argument("--vae_tile_size", type=int, default=None, metavar="PIXELS",
                         help="(addition) with --vae_tiling: the tile side in image pixels, a multiple of 32; default: the VAE's sample_size")
+    parser.add_argument("--u8_output", action="store_true",
+                        help="(addition) take the frames from the pipeline as uint8 (output_type='uint8': quantised on the GPU, a quarter of the "
+                             "bytes of the float32 clip on the host) and write the grid video from bytes; the file is byte-identical to the default's")
     args = parser.parse_args(argv)
     if args.vae_tile_size is not None and not args.vae_tiling:
         parser.error(f"--vae_tile_size {args.vae_tile_size} needs --vae_tiling")
@@ -315,10 +321,14 @@ def main(argv=None):
 
     skel_name = os.path.splitext(os.path.basename(config.tgt_pose_path))[0]
     ref_name = os.path.splitext(os.path.basename(config.ref_image_path))[0]
-    pose_tensor = frames_to_tensor(pose_pils, height, width)
     ref_image_pil = Image.open(config.ref_image_path).convert("RGB")
     ref_skel_pil = Image.open(config.ref_skel_path).convert("RGB")
-    ref_image_tensor = frames_to_tensor([ref_image_pil], height, width).repeat(1, 1, num_frames, 1, 1)
+    if args.u8_output:                                                     # (1, f, h, w, 3) bytes; the float clips are never made
+        pose_tensor = frames_to_u8(pose_pils, height, width)
+        ref_image_tensor = frames_to_u8([ref_image_pil], height, width).repeat(1, num_frames, 1, 1, 1)
+    else:
+        pose_tensor = frames_to_tensor(pose_pils, height, width)
+        ref_image_tensor = frames_to_tensor([ref_image_pil], height, width).repeat(1, 1, num_frames, 1, 1)
 
     out = pipe(ref_image_pil, ref_skel_pil, pose_pils, face_pils, hand_pils, scene_motion_npy, width, height, num_frames,
                args.steps, args.cfg, generator=generator, guidance_rescale=args.guidance_rescale,
@@ -334,10 +344,11 @@ def main(argv=None):
                deep_cache_interval=args.deep_cache_interval, deep_cache_depth=args.deep_cache_depth,
                guidance_interval=args.guidance_interval, uncond_cache_interval=args.uncond_cache_interval,
                hires_scale=args.hires_scale, hires_strength=args.hires_strength, hires_mode=args.hires_mode, hires_steps=args.hires_steps,
-               scene_motion_lowres_npy=scene_motion_lowres_npy, vae_tiling=args.vae_tiling, vae_tile_size=args.vae_tile_size)
+               scene_motion_lowres_npy=scene_motion_lowres_npy, vae_tiling=args.vae_tiling, vae_tile_size=args.vae_tile_size,
+               **(dict(output_type="uint8") if args.u8_output else {}))
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
-    save_videos_grid(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)
+    (save_frames_grid_u8 if args.u8_output else save_videos_grid)(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)
     return path
 
 

@@ -12,6 +12,8 @@ models, without the wheels this image lacks (omegaconf, PyAV, cv2, torchvision, 
   save_videos_grid       src/utils/util.py:90-111: b c t h w -> one grid image per frame -> .mp4 / .gif.  The .mp4 is a plain
                          ISO-BMFF file with a Motion-JPEG ('jpeg') video track written by the ~80-line muxer below (the reference
                          uses cv2's mp4v encoder; there is no video encoder in this image, PIL's JPEG codec is); .gif via PIL
+  frames_to_u8 / make_grid_u8 / save_frames_grid_u8   the uint8 twins of the three above for the pipeline's output_type="uint8" (an addition):
+                         channels-last bytes from the resize to the writer, the same files
   save_videos_from_pil   src/utils/util.py:50-87
   resize_depth           skimage.transform.resize(depth, (1, H/8, W/8)) as called at scripts/inference_video.py:184: order-1
                          interpolation, 'reflect' boundary, Gaussian anti-aliasing when shrinking, clipped to the input range
@@ -338,6 +340,41 @@ def save_videos_grid(videos, path, rescale=False, n_rows=6, fps=8):
         if rescale:
             x = (x + 1.0) / 2.0
         outputs.append(Image.fromarray((x * 255).numpy().astype(np.uint8)))
+    save_videos_from_pil(outputs, path, fps)
+
+
+def frames_to_u8(pils, height, width):
+    """The uint8 twin of frames_to_tensor: the same bilinear resize, no division -> (1, f, h, w, 3) torch.uint8.  frames_to_tensor's k / 255
+    comes back as k from save_videos_grid's cast (trunc(fp32(k) / 255 * 255) == k for all 256 bytes), so the two describe the same pixels."""
+    frames = [torch.from_numpy(np.array(im.convert("RGB").resize((width, height), Image.BILINEAR), dtype=np.uint8)) for im in pils]
+    return torch.stack(frames, 0)[None].contiguous()
+
+
+def make_grid_u8(frames, nrow=8, padding=2):
+    """make_grid for a (B, H, W, C) uint8 batch, channels last, pad bytes 0: the same layout rule -> (H', W', C)."""
+    if frames.dim() != 4 or frames.dtype != torch.uint8:
+        raise ValueError("make_grid_u8 expects a uint8 (B, H, W, C) tensor")
+    if frames.shape[3] == 1:
+        frames = frames.expand(-1, -1, -1, 3)
+    nmaps = frames.shape[0]
+    if nmaps == 1:
+        return frames[0]
+    xmaps = min(nrow, nmaps)
+    ymaps = int(math.ceil(nmaps / xmaps))
+    h, w = frames.shape[1] + padding, frames.shape[2] + padding
+    grid = frames.new_zeros((h * ymaps + padding, w * xmaps + padding, frames.shape[3]))
+    for k in range(nmaps):
+        y, x = divmod(k, xmaps)
+        grid[y * h + padding:(y + 1) * h, x * w + padding:(x + 1) * w] = frames[k]
+    return grid
+
+
+def save_frames_grid_u8(clips, path, n_rows=6, fps=8):
+    """save_videos_grid for uint8 clips (b, f, H, W, C) as the pipeline's output_type="uint8" returns them: one grid frame per f, no float
+    round trip.  Pixel for pixel the frames save_videos_grid builds from the float clips these bytes were cast from, so the same file."""
+    if clips.dim() != 5 or clips.dtype != torch.uint8:
+        raise ValueError("save_frames_grid_u8 expects a uint8 (b, f, H, W, C) tensor")
+    outputs = [Image.fromarray(np.ascontiguousarray(make_grid_u8(x, nrow=n_rows).numpy())) for x in clips.permute(1, 0, 2, 3, 4)]
     save_videos_from_pil(outputs, path, fps)
 
 

@@ -673,6 +673,39 @@ def tile_blend(cur, dst, c, above=None, left=None, extent=(0, 0)):
     return cur
 
 
+def frames_u8(src, out=None, *, f32_math=None):
+    """Decoded frames -> the bytes the writers take (md_frames_u8): src (B, C, H, W)-shaped fp16 / fp32 with ANY strides, C in 1..4 -- an NHWC
+    buffer is passed as its permuted view, the strides say what it is -- -> out (B, H, W, C) uint8, the reference's
+    ((x / 2 + 0.5).clamp(0, 1).float() * 255) truncated, operation by operation: in fp16 with f32_math=False, in fp32 with f32_math=True;
+    None: as the source dtype.  An fp32 source needs fp32 arithmetic.  NaN gives 0.  `out`: a uint8 (B, H, W, C) tensor or VIEW whose last two
+    dimensions are packed (stride C and 1); the row and frame pitches are free, so a frame can land inside a larger canvas.  Returns out."""
+    if not src.is_cuda or src.dtype not in (torch.float16, torch.float32):
+        raise _lib.MdanceHipError("frames_u8: src must be a CUDA fp16/fp32 tensor")
+    if src.dim() != 4 or not 1 <= src.shape[1] <= 4 or min(src.shape) < 1:
+        raise _lib.MdanceHipError(f"frames_u8: src must be (B, C, H, W)-shaped with C in 1..4 and no empty dimension, got {tuple(src.shape)}")
+    B, C, H, W = src.shape
+    if f32_math is None:
+        f32_math = src.dtype == torch.float32
+    if not isinstance(f32_math, bool):
+        raise _lib.MdanceHipError(f"frames_u8: f32_math must be True, False or None, got {f32_math!r}")
+    if src.dtype == torch.float32 and not f32_math:
+        raise _lib.MdanceHipError("frames_u8: an fp32 source needs f32_math=True")
+    if out is None:
+        out = torch.empty((B, H, W, C), device=src.device, dtype=torch.uint8)
+    if not out.is_cuda or out.dtype != torch.uint8 or out.device != src.device:
+        raise _lib.MdanceHipError("frames_u8: out must be a CUDA uint8 tensor on src's device")
+    if tuple(out.shape) != (B, H, W, C) or out.stride(3) != 1 or out.stride(2) != C:
+        raise _lib.MdanceHipError(f"frames_u8: out must be a (B, H, W, C) = ({B}, {H}, {W}, {C}) view with packed pixels (strides (*, *, {C}, 1)), got shape "
+                                  f"{tuple(out.shape)} strides {tuple(out.stride())}")
+    sB, sC, sY, sX = src.stride()
+    dY = out.stride(1) if H > 1 else max(out.stride(1), W * C)           # the stride of a dimension of size 1 says nothing
+    dB = out.stride(0) if B > 1 else max(out.stride(0), (H - 1) * dY + W * C)
+    n = B * H * W * C
+    _lib.call("md_frames_u8", src.data_ptr(), int(src.dtype == torch.float32), int(f32_math), out.data_ptr(), B, H, W, C, sB, sC, sY, sX, dB, dY, _st(),
+              meta=(f"frames_u8 B={B} {H}x{W} C={C} {'f32' if f32_math else 'f16'}", 0.0, float(src.element_size() * n + n)))
+    return out
+
+
 def blur_kernel_size(sigma, n):
     """Taps of SEG's Gaussian along a grid axis of n tokens: the official gaussian_blur_2d's ceil(6 sigma) + 1 - ceil(6 sigma) % 2, clamped to
     the largest odd number a reflect-padded axis of n allows (n if n is odd, else n + 1); 1 for n = 1."""

@@ -887,8 +887,34 @@ class MikuDanceVideoPipeline:
         lat = torch.cat([self._encode(u[i:i + self.vae_batch]) for i in range(0, u.shape[0], self.vae_batch)], dim=0)
         return lat if len(rep) == x.shape[0] else lat[torch.tensor(inverse, device=lat.device)]
 
-    def decode_latents(self, latents):
-        """reference :115-130 -- per-frame VAE decode, (x/2+0.5).clamp(0,1), float32 numpy (b,c,f,h,w)."""
+    def _decode_u8(self, latents, batch, temporal=False):
+        """The uint8 twin of decode_latents / decode_temporal: the same scaling, frame order and VAE batches, every batch through the VAE's
+        decode_u8 (md_frames_u8: quantised on the device, straight into its rows of one (b f, H, W, 3) buffer), ONE device-to-host copy of
+        bytes -> a CPU torch.uint8 (b, f, H, W, 3) tensor: bit for bit (the float path's array * 255) cast to uint8 and permuted."""
+        if not hasattr(self.vae, "decode_u8"):
+            raise ValueError(f"output_type 'uint8' / 'pil': {type(self.vae).__name__} has no decode_u8")
+        video_length = latents.shape[2]
+        latents = 1 / 0.18215 * latents
+        latents = latents.permute(0, 2, 1, 3, 4).reshape((-1,) + tuple(latents.shape[1:2]) + tuple(latents.shape[3:]))
+        video = None
+        for i in range(0, latents.shape[0], batch):
+            chunk = latents[i:i + batch].to(self.vae.dtype)
+            kw = dict(num_frames=chunk.shape[0]) if temporal else {}
+            if video is None:                                              # the first batch tells the frame size (the VAE's factor is its own)
+                first = self.vae.decode_u8(chunk, **kw)
+                video = torch.empty((latents.shape[0],) + tuple(first.shape[1:]), device=first.device, dtype=torch.uint8)
+                video[:first.shape[0]] = first
+            else:
+                self.vae.decode_u8(chunk, out=video[i:i + chunk.shape[0]], **kw)
+        return video.reshape((-1, video_length) + tuple(video.shape[1:])).cpu()
+
+    def decode_latents(self, latents, output_type=None):
+        """reference :115-130 -- per-frame VAE decode, (x/2+0.5).clamp(0,1), float32 numpy (b,c,f,h,w).  output_type "uint8": a CPU torch.uint8
+        (b, f, H, W, 3) tensor instead (_decode_u8); None: the reference's array."""
+        if output_type is not None:
+            if output_type != "uint8":
+                raise ValueError(f"decode_latents: output_type must be None or 'uint8', got {output_type!r}")
+            return self._decode_u8(latents, self.vae_batch)
         video_length = latents.shape[2]
         latents = 1 / 0.18215 * latents
         latents = latents.permute(0, 2, 1, 3, 4).reshape((-1,) + tuple(latents.shape[1:2]) + tuple(latents.shape[3:]))
@@ -898,9 +924,13 @@ class MikuDanceVideoPipeline:
         video = (video / 2 + 0.5).clamp(0, 1)
         return video.cpu().float().numpy()
 
-    def decode_temporal(self, latents, decode_chunk_size=None):
-        """reference :132-150 (AutoencoderKLTemporalDecoder in chunks of self.decode_chunk_size = 16 frames)."""
+    def decode_temporal(self, latents, decode_chunk_size=None, output_type=None):
+        """reference :132-150 (AutoencoderKLTemporalDecoder in chunks of self.decode_chunk_size = 16 frames).  output_type as decode_latents."""
         decode_chunk_size = decode_chunk_size or self.decode_chunk_size
+        if output_type is not None:
+            if output_type != "uint8":
+                raise ValueError(f"decode_temporal: output_type must be None or 'uint8', got {output_type!r}")
+            return self._decode_u8(latents, decode_chunk_size, temporal=True)
         video_length = latents.shape[2]
         latents = 1 / 0.18215 * latents
         latents = latents.permute(0, 2, 1, 3, 4).reshape((-1,) + tuple(latents.shape[1:2]) + tuple(latents.shape[3:]))
@@ -1045,6 +1075,12 @@ class MikuDanceVideoPipeline:
                  vae_tile_size=None, **kwargs):
         """The reference call (src/pipelines/pipeline_mikudance.py:362-704) with denoise()'s sampling keywords (see its docstring), and:
 
+        output_type         "tensor" (the default): `videos` is the reference's float32 (b, c, f, H, W) CPU tensor in [0, 1]; "uint8": a CPU
+                            torch.uint8 (b, f, H, W, 3) tensor, the frames quantised on the device (AutoencoderKL.decode_u8 / md_frames_u8) and
+                            copied to the host as bytes -- bit for bit (the "tensor" result * 255) cast to uint8 and permuted, what
+                            save_videos_grid's own cast makes of it; "pil": a list over b of lists of PIL.Image built from those bytes; any
+                            other value: the reference's float32 numpy array, as before.  vae_batch, decode_chunk_size, vae_tiling and
+                            interpolation_factor act as in the float path
         vae_tiling          True: the VAE encodes and decodes this call's images tile by tile (AutoencoderKL.enable_tiling(): diffusers' tiled
                             VAE, overlapping tiles with blended seams; memory and the mid-block attention then scale with the tile, not the
                             image).  A different result by design, each tile's GroupNorm and attention see that tile only; image quality on
@@ -1163,7 +1199,14 @@ class MikuDanceVideoPipeline:
                                        callback_steps, eta=eta, generator=generator, init_latents=latents, **hi_kw)
             if interpolation_factor > 0:
                 latents = self.interpolate_latents(latents, interpolation_factor, device)
-            images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)
+            if output_type in ("uint8", "pil"):
+                # frames quantised on the device (md_frames_u8), in the layout the writers take: half the bytes of the fp16 transfer, a quarter of the fp32 host array's
+                images = self.decode_temporal(latents, output_type="uint8") if self.video_decoder else self.decode_latents(latents, output_type="uint8")
+                if output_type == "pil":
+                    from PIL import Image
+                    images = [[Image.fromarray(frame.numpy()) for frame in clip] for clip in images]
+            else:
+                images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)
             if output_type == "tensor":
                 images = torch.from_numpy(images)
             if not return_dict:

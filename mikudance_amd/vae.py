@@ -331,6 +331,21 @@ class AutoencoderKL(_Packed):
         out = SimpleNamespace(sample=img)
         return out if return_dict else (img,)
 
+    @torch.no_grad()
+    def decode_u8(self, z, out=None):
+        """decode(z) as the bytes a writer takes: (B, 8h, 8w, out_channels) uint8 on the device, bit for bit
+        ((decode(z).sample / 2 + 0.5).clamp(0, 1).float() * 255) truncated, in the arithmetic of the dtype decode would have returned (fp16
+        chain for fp16 latents, fp32 chain for fp32).  Untiled, the decoder's NHWC image goes into ops.frames_u8 (md_frames_u8) directly: no
+        NCHW tensor, no elementwise pass.  With tiling or slicing on, decode runs as it stands and one frames_u8 reads its NCHW result.
+        `out`: a destination view as ops.frames_u8 takes it."""
+        if z.dim() != 4 or z.shape[1] != self.zc:
+            raise ValueError(f"AutoencoderKL.decode_u8 expects (B, {self.zc}, h, w), got {tuple(z.shape)}")
+        f32 = self._out_dtype(z) == torch.float32
+        tiled = self.use_tiling and max(z.shape[2:]) > self.tile_latent_min_size
+        if tiled or (self.use_slicing and z.shape[0] > 1):
+            return ops.frames_u8(self.decode(z).sample, out, f32_math=f32)
+        return ops.frames_u8(self._image_nhwc(z).permute(0, 3, 1, 2), out, f32_math=f32)
+
     # ---- tiling and slicing (diffusers 0.24: enable_tiling / enable_slicing, tiled_encode / tiled_decode)
     def enable_tiling(self, use_tiling=True):
         """encode / decode of an input with a side above tile_sample_min_size pixels / tile_latent_min_size latents run tile by tile."""

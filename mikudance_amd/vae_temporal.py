@@ -231,16 +231,21 @@ class AutoencoderKLTemporalDecoder(_Packed):
         out = SimpleNamespace(latent_dist=DiagonalGaussian(moments))
         return out if return_dict else (out.latent_dist,)
 
+    def _image_nhwc(self, z, num_frames):
+        """z (clips * num_frames, z, h, w), any strides -> the temporal decoder -> (B, 8h, 8w, 8) fp16 NHWC, out_channels valid channels."""
+        B, C, h, w = z.shape
+        st = z.stride()
+        z64 = ops.pack_nhwc(z, B, 1, (st[0], 0, st[1], st[2], st[3]), 0, C, 64, h, w)
+        return self.decoder(z64, num_frames)
+
     @torch.no_grad()
     def decode(self, z, num_frames=1, return_dict=True, image_only_indicator=None):
         """z: (clips * num_frames, latent, h, w).  `image_only_indicator` is accepted for signature compatibility; with the
         decoder's merge_strategy="learned" the blend does not depend on it (diffusers AlphaBlender.get_alpha)."""
         if z.dim() != 4 or z.shape[1] != self.zc or z.shape[0] % num_frames:
             raise ValueError(f"decode expects (clips * num_frames, {self.zc}, h, w), got {tuple(z.shape)} with num_frames={num_frames}")
-        B, C, h, w = z.shape
-        st = z.stride()
-        z64 = ops.pack_nhwc(z, B, 1, (st[0], 0, st[1], st[2], st[3]), 0, C, 64, h, w)
-        y = self.decoder(z64, num_frames)                                                # (B, 8h, 8w, 8): 3 valid channels
+        B = z.shape[0]
+        y = self._image_nhwc(z, num_frames)                                              # (B, 8h, 8w, 8): 3 valid channels
         oc = self.decoder.out_channels
         H, W = y.shape[1], y.shape[2]                                                    # 2^(levels-1) x the latent size
         img = torch.empty((B, oc, H, W), device=z.device, dtype=z.dtype if z.dtype != torch.float64 else torch.float32)
@@ -248,6 +253,16 @@ class AutoencoderKLTemporalDecoder(_Packed):
         ops.unpack_nhwc(y, img, B, 1, (so[0], 0, so[1], so[2], so[3]), oc, H, W)
         out = SimpleNamespace(sample=img)
         return out if return_dict else (img,)
+
+    @torch.no_grad()
+    def decode_u8(self, z, num_frames=1, image_only_indicator=None, out=None):
+        """decode(z, num_frames) as the bytes a writer takes: (B, H, W, out_channels) uint8 on the device, bit for bit
+        ((decode(...).sample / 2 + 0.5).clamp(0, 1).float() * 255) truncated, in the arithmetic of the dtype decode would have returned.  The
+        decoder's NHWC result (pixel pitch 8) goes into ops.frames_u8 (md_frames_u8) directly: no NCHW tensor, no elementwise pass."""
+        if z.dim() != 4 or z.shape[1] != self.zc or z.shape[0] % num_frames:
+            raise ValueError(f"decode_u8 expects (clips * num_frames, {self.zc}, h, w), got {tuple(z.shape)} with num_frames={num_frames}")
+        y = self._image_nhwc(z, num_frames)                                              # (B, 8h, 8w, 8): 3 valid channels
+        return ops.frames_u8(y[..., :self.decoder.out_channels].permute(0, 3, 1, 2), out, f32_math=z.dtype in (torch.float32, torch.float64))
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path, subfolder=None, **kw):
