@@ -220,31 +220,80 @@ int md_window_accumulate(const void* pred, void* noise_sum, void* counter, const
 int md_window_accumulate_weighted(const void* pred, void* noise_sum, void* counter, const int* window, const float* weights, int f,
                                   int Ftot, int HW, int halves, void* stream);
 
-/* (noise_pred / counter) -> classifier-free guidance -> DDIM v-prediction step (eta 0), latents updated in place.
- * src/pipelines/pipeline_mikudance.py:670-678 + diffusers DDIMScheduler.step.
- * Like every step entry below: latents / noise_sum (and counter when halves == 2) must not be NULL, Ftot > 0, HW > 0, halves 1 or 2,
- * guidance / alpha_t / alpha_prev finite; MD_ERR_ARG otherwise, with the latents untouched. */
+/* ---- The step family: md_cfg_<sampler>_step<guide>, 13 entries ---------------------------------------------------------------------
+ * (noise_pred / counter) -> guided v -> one step of the sampler, the fp16 latents [Ftot][HW][4] updated in place (fp32 arithmetic, one
+ * rounding).  src/pipelines/pipeline_mikudance.py:670-678 (CFG, then self.scheduler.step; :45-52 types the scheduler).
+ *
+ * Every entry takes latents, noise_sum (fp32 [halves][Ftot][HW][4], the window sums, planes [u, c] under CFG), counter (fp32 [Ftot]), Ftot, HW,
+ * halves and guidance.  halves == 2: inv = 1 / counter, u = sum_u inv, c = sum_c inv, v = u + guidance (c - u).  halves == 1: v is the window SUM
+ * and neither the counter nor a second plane is read.  latents / noise_sum (and counter when halves == 2) must not be NULL, Ftot > 0, HW > 0,
+ * halves 1 or 2, guidance and every coefficient finite; MD_ERR_ARG otherwise, with nothing launched and the latents untouched.
+ *
+ * What the sampler adds
+ *   ddim       alpha_t, alpha_prev (and eta, variance_noise in every entry but md_cfg_ddim_step, which is eta == 0): diffusers DDIMScheduler.step,
+ *              v-prediction.  sigma_t = eta sqrt((1 - a_prev) / (1 - a_t) (1 - a_t / a_prev)), x' = sqrt(a_prev) x0 + sqrt(1 - a_prev - sigma_t^2)
+ *              eps + sigma_t z, z = variance_noise, fp16, laid out like the latents: the caller draws it from ITS generator (`eta` of
+ *              MikuDanceVideoPipeline.__call__, pipeline_mikudance.py:152-171,375).  eta >= 0; variance_noise not NULL when eta != 0.
+ *              One element per access: the buffers need their natural alignment only (md_cfg_ddim_step_apg: as multistep).
+ *   multistep  history, variance_noise, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z: one DPM-Solver++ update (orders 1 / 2, ODE or SDE),
+ *              m0 = alpha_s x - sigma_s v, x' = c_x x + c_m0 m0 + c_m1 m1 + c_z z, with m1 = history (fp32 [Ftot][HW][4], the previous step's m0)
+ *              read only when c_m1 != 0 and then overwritten with m0.  The coefficients are DPMSolverMultistepScheduler.multistep_coefficients;
+ *              variance_noise may be NULL when c_z == 0.  One pixel per access: latents / variance_noise 8-byte, noise_sum / history 16-byte aligned.
+ *   unipc      state, row: the corrector of the step that produced these latents and the predictor to the next point in ONE pass per pixel (Zhao et
+ *              al., arXiv 2302.04867; diffusers UniPCMultistepScheduler, data prediction, orders 1 - 3; not among the reference's schedulers):
+ *                m_t = alpha_s x - sigma_s v
+ *                x^c = cc_x x_last + cc_m m_t + cc_0 H0 + cc_1 H1 + cc_2 H2       corrector on; off: x^c = x
+ *                x'  = pc_x x^c + pc_m m_t + pc_0 H0 + pc_1 H1                    -> latents
+ *                x_last <- x^c;  H0 <- m_t;  H1 <- H0;  H2 <- H1
+ *              state: fp32 [4][Ftot][HW][4], the planes x_last, H0, H1, H2, kept by the caller between steps.  A plane is read only where one of
+ *              its weights is non-zero (x_last only with the corrector on) and only a plane that was read moves down a slot: a first step
+ *              (corrector off, pc_0 = pc_1 = 0) may be given uninitialised memory.  row: 12 floats in HOST memory, read before the call returns:
+ *              alpha_s, sigma_s, cc_x, cc_m, cc_0, cc_1, cc_2, pc_x, pc_m, pc_0, pc_1 and the corrector flag (0 or 1), as
+ *              UniPCMultistepScheduler.unipc_coefficients gives them.  Latents 8-byte, noise_sum / state 16-byte, counter 4-byte aligned.
+ *
+ * What the guide adds
+ *   _scaled    vscale: v is multiplied by *vscale, the out_scale of md_cfg_guidance_rescale, read on the device (diffusers rescale_noise_cfg
+ *              followed by scheduler.step; arXiv 2305.08891 section 3.4).  halves must be 2; vscale 4-byte aligned.
+ *   _apg       momentum_buf, coef: v_g = c - (guidance - 1) (S m - K D_c) / s in place of v, D_c = a x - s c, (S, K) = coef[frame], m = momentum_buf
+ *              as md_cfg_apg_prepare left them for THIS step (a, s: sqrt(alpha_t), sqrt(1 - alpha_t) for ddim; alpha_s, sigma_s of multistep and
+ *              of unipc's row; history / state receive alpha_s x - sigma_s v_g).  With eta = 1, norm_threshold = 0, momentum = 0 at prepare this
+ *              is u + guidance (c - u) up to rounding.  halves must be 2, s > 0 (alpha_t in [0, 1)); momentum_buf 16-byte, coef 4-byte aligned.
+ *   _pag       perturbed_sum, pag_scale: perturbed-attention guidance (Ahn et al., arXiv 2403.17377; diffusers PAGMixin), v + pag_scale inv
+ *              (sum_c - sum_p), inv as above (1 without CFG: c + s (c - p) on the sums), sum_c the conditional plane of noise_sum (plane
+ *              halves - 1) and sum_p = perturbed_sum, fp32 [Ftot][HW][4], the prediction of the conditional evaluation whose selected self-attention
+ *              maps are the identity, accumulated over the windows like the other planes.  pag_scale == 0 gives the bits of the plain entry where
+ *              the planes are finite (0 * Inf is NaN).  halves 1 or 2; pag_scale finite and >= 0; perturbed_sum aligned like noise_sum
+ *              (ddim: 4-byte, and latents / variance_noise 2-byte, counter 4-byte). */
 int md_cfg_ddim_step(void* latents, const void* noise_sum, const void* counter, int Ftot, int HW, int halves,
                      float guidance, float alpha_t, float alpha_prev, void* stream);
-
-/* The same step for eta > 0 (DDIM's stochastic variant; `eta` of MikuDanceVideoPipeline.__call__,
- * src/pipelines/pipeline_mikudance.py:152-171,375 -> scheduler.step(..., eta=, generator=)): sigma_t = eta * sqrt((1 - a_prev) /
- * (1 - a_t) * (1 - a_t / a_prev)), prev = sqrt(a_prev) x0 + sqrt(1 - a_prev - sigma_t^2) eps + sigma_t z with z = variance_noise,
- * fp16, laid out like the latents (Ftot, HW, 4) -- the caller draws it from ITS generator (diffusers randn_tensor).
- * The refusals of md_cfg_ddim_step, and: eta finite and >= 0, variance_noise not NULL when eta != 0. */
 int md_cfg_ddim_step_eta(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, int Ftot, int HW,
                          int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
-
-/* (noise_pred / counter) -> classifier-free guidance -> one DPM-Solver++ multistep update (orders 1 / 2, ODE or SDE), latents updated
- * in place: m0 = alpha_s x - sigma_s v, x' = c_x x + c_m0 m0 + c_m1 m1 + c_z z, with m1 = history (fp32 [Ftot][HW][4], the previous
- * step's m0) read only when c_m1 != 0 and then overwritten with m0.  The coefficients come from the host
- * (DPMSolverMultistepScheduler.multistep_coefficients); variance_noise (fp16, laid out like the latents) may be NULL when c_z == 0.
- * noise_sum, counter, Ftot, HW, halves, guidance as md_cfg_ddim_step.  Latents / variance_noise 8-byte, noise_sum / history 16-byte aligned.
- * src/pipelines/pipeline_mikudance.py:45-52 (scheduler typed as one of six diffusers schedulers, DPMSolverMultistepScheduler among
- * them) and :670-678 (self.scheduler.step). */
+int md_cfg_ddim_step_scaled(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const float* vscale, int Ftot,
+                            int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
+int md_cfg_ddim_step_apg(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const void* momentum_buf,
+                         const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
+int md_cfg_ddim_step_pag(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const void* perturbed_sum, int Ftot,
+                         int HW, int halves, float guidance, float pag_scale, float alpha_t, float alpha_prev, float eta, void* stream);
 int md_cfg_multistep_step(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise, int Ftot,
                           int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
                           void* stream);
+int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                                 const float* vscale, int Ftot, int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x,
+                                 float c_m0, float c_m1, float c_z, void* stream);
+int md_cfg_multistep_step_apg(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                              const void* momentum_buf, const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_s,
+                              float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
+int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
+                              const void* perturbed_sum, int Ftot, int HW, int halves, float guidance, float pag_scale, float alpha_s,
+                              float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
+int md_cfg_unipc_step(void* latents, const void* noise_sum, const void* counter, void* state, int Ftot, int HW, int halves, float guidance,
+                      const float* row, void* stream);
+int md_cfg_unipc_step_scaled(void* latents, const void* noise_sum, const void* counter, void* state, const float* vscale, int Ftot, int HW,
+                             int halves, float guidance, const float* row, void* stream);
+int md_cfg_unipc_step_apg(void* latents, const void* noise_sum, const void* counter, void* state, const void* momentum_buf, const float* coef,
+                          int Ftot, int HW, int halves, float guidance, const float* row, void* stream);
+int md_cfg_unipc_step_pag(void* latents, const void* noise_sum, const void* counter, void* state, const void* perturbed_sum, int Ftot, int HW,
+                          int halves, float guidance, float pag_scale, const float* row, void* stream);
 
 /* Guidance rescale (rescaled classifier-free guidance, Lin et al. "Common Diffusion Noise Schedules and Sample Steps are Flawed",
  * arXiv 2305.08891 section 3.4; diffusers rescale_noise_cfg), applied to the window-averaged guided output between
@@ -258,16 +307,6 @@ int md_cfg_multistep_step(void* latents, const void* noise_sum, const void* coun
 size_t md_cfg_rescale_workspace_bytes(int Ftot, int HW);
 int md_cfg_guidance_rescale(const void* noise_sum, const void* counter, int Ftot, int HW, int halves, float guidance, float phi, void* workspace,
                             size_t workspace_bytes, void* out_scale, void* stream);
-
-/* md_cfg_ddim_step (eta == 0) / md_cfg_ddim_step_eta (eta > 0) and md_cfg_multistep_step with the guided v multiplied by *vscale (the
- * out_scale of md_cfg_guidance_rescale, read on the device) before the update: diffusers rescale_noise_cfg followed by scheduler.step
- * (src/pipelines/pipeline_mikudance.py:670-678, arXiv 2305.08891 section 3.4).  halves must be 2; other arguments and alignment as the
- * unscaled entries, vscale 4-byte aligned. */
-int md_cfg_ddim_step_scaled(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const float* vscale, int Ftot,
-                            int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
-int md_cfg_multistep_step_scaled(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
-                                 const float* vscale, int Ftot, int HW, int halves, float guidance, float alpha_s, float sigma_s, float c_x,
-                                 float c_m0, float c_m1, float c_z, void* stream);
 
 /* Adaptive projected guidance (APG; Sadat, Hilliges, Weber, "Eliminating Oversaturation and Artifacts of High Guidance Scales in Diffusion
  * Models", arXiv 2410.02416, Algorithm 1; diffusers AdaptiveProjectedGuidance), applied to the window-averaged halves between
@@ -287,61 +326,6 @@ size_t md_cfg_apg_workspace_bytes(int Ftot, int HW);
 int md_cfg_apg_prepare(const void* latents, const void* noise_sum, const void* counter, void* momentum_buf, int Ftot, int HW, int halves,
                        float alpha_s, float sigma_s, float momentum, float eta, float norm_threshold, void* workspace, size_t workspace_bytes,
                        void* coef, void* stream);
-
-/* md_cfg_ddim_step / md_cfg_ddim_step_eta and md_cfg_multistep_step with APG's guided output in place of u + guidance (c - u):
- *   v_g = c - (guidance - 1) (S m - K D_c) / s,   D_c = a x - s c,   (S, K) = coef[frame],   m = momentum_buf
- * as md_cfg_apg_prepare left them for THIS step (a, s: sqrt(alpha_t), sqrt(1 - alpha_t) of the DDIM entry; alpha_s, sigma_s of the
- * multistep entry, whose history receives alpha_s x - sigma_s v_g).  With eta = 1, norm_threshold = 0, momentum = 0 at prepare this is
- * u + guidance (c - u) up to rounding.  halves must be 2, momentum_buf and coef not NULL, s > 0 (alpha_t in [0, 1)); other arguments as
- * the plain entries; alignment for both as md_cfg_multistep_step, momentum_buf 16-byte, coef 4-byte.  MD_ERR_ARG otherwise, with nothing
- * launched. */
-int md_cfg_ddim_step_apg(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const void* momentum_buf,
-                         const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_t, float alpha_prev, float eta, void* stream);
-int md_cfg_multistep_step_apg(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
-                              const void* momentum_buf, const float* coef, int Ftot, int HW, int halves, float guidance, float alpha_s,
-                              float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
-
-/* md_cfg_ddim_step / md_cfg_ddim_step_eta and md_cfg_multistep_step with perturbed-attention guidance (PAG; Ahn et al., "Self-Rectifying
- * Diffusion Sampling with Perturbed-Attention Guidance", arXiv 2403.17377; diffusers PAGMixin / AnimateDiffPAGPipeline), applied to the
- * window-accumulated planes between src/pipelines/pipeline_mikudance.py:670-674 (CFG) and :678 (scheduler.step):
- *   v = v_plain + pag_scale inv (sum_c - sum_p)
- * v_plain and inv exactly as the plain entries form them (halves == 2: inv = 1 / counter, v_plain = u + guidance (c - u), so this is diffusers'
- * u + g (c - u) + s (c - p); halves == 1: inv = 1 and v_plain the window SUM, so it is c + s (c - p) on the sums), sum_c the conditional plane
- * of noise_sum (plane halves - 1) and sum_p = perturbed_sum [Ftot][HW][4] fp32, the prediction of the conditional evaluation whose selected
- * self-attention maps are the identity, accumulated over the windows like the other planes.  pag_scale == 0 gives the bits of the plain
- * entry where the planes are finite (0 * Inf is NaN).  halves 1 or 2; perturbed_sum not NULL, pag_scale finite and >= 0; other arguments as
- * the plain entries.  Alignment: the DDIM entry accesses single elements (latents / variance_noise 2-byte, noise_sum / counter /
- * perturbed_sum 4-byte); the multistep entry as md_cfg_multistep_step, perturbed_sum 16-byte.  MD_ERR_ARG otherwise, with nothing launched. */
-int md_cfg_ddim_step_pag(void* latents, const void* noise_sum, const void* counter, const void* variance_noise, const void* perturbed_sum, int Ftot,
-                         int HW, int halves, float guidance, float pag_scale, float alpha_t, float alpha_prev, float eta, void* stream);
-int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, const void* counter, void* history, const void* variance_noise,
-                              const void* perturbed_sum, int Ftot, int HW, int halves, float guidance, float pag_scale, float alpha_s,
-                              float sigma_s, float c_x, float c_m0, float c_m1, float c_z, void* stream);
-
-/* (noise_pred / counter) -> classifier-free guidance -> one UniPC step (Zhao et al., "UniPC: A Unified Predictor-Corrector Framework for Fast
- * Sampling of Diffusion Models", arXiv 2302.04867; diffusers UniPCMultistepScheduler, data prediction, orders 1 - 3), latents updated in
- * place.  The corrector of the step that produced these latents and the predictor to the next point are ONE pass per pixel:
- *   m_t = alpha_s x - sigma_s v                                      x: the fp16 latents, v: the guided output as md_cfg_ddim_step forms it
- *   x^c = cc_x x_last + cc_m m_t + cc_0 H0 + cc_1 H1 + cc_2 H2       corrector on; off: x^c = x
- *   x'  = pc_x x^c + pc_m m_t + pc_0 H0 + pc_1 H1                    -> latents (fp32 arithmetic, one rounding)
- *   x_last <- x^c;  H0 <- m_t;  H1 <- H0;  H2 <- H1
- * state: fp32 [4][Ftot][HW][4], the planes x_last, H0, H1, H2 (the corrected sample and the data predictions of the last three steps), kept by
- * the caller between steps.  A plane is read only where one of its weights is non-zero (x_last only with the corrector on), and only a plane
- * that was read moves down a slot: a first step (corrector off, pc_0 = pc_1 = 0) may be given uninitialised memory.
- * row: 12 floats in HOST memory, read before the call returns: alpha_s, sigma_s, cc_x, cc_m, cc_0, cc_1, cc_2, pc_x, pc_m, pc_0, pc_1 and the
- * corrector flag (0 or 1), as UniPCMultistepScheduler.unipc_coefficients gives them; all finite.
- * noise_sum, counter, Ftot, HW, halves, guidance as md_cfg_ddim_step; the _scaled / _apg / _pag entries add what the entries of the same name
- * of md_cfg_multistep_step add (md_cfg_apg_prepare is called with this row's alpha_s, sigma_s).  Latents 8-byte, noise_sum / state / momentum_buf /
- * perturbed_sum 16-byte, counter / vscale / coef 4-byte aligned.  MD_ERR_ARG otherwise, with nothing launched.
- * src/pipelines/pipeline_mikudance.py:45-52 (UniPCMultistepScheduler is not among the reference's schedulers: an addition) and :670-678. */
-int md_cfg_unipc_step(void* latents, const void* noise_sum, const void* counter, void* state, int Ftot, int HW, int halves, float guidance,
-                      const float* row, void* stream);
-int md_cfg_unipc_step_scaled(void* latents, const void* noise_sum, const void* counter, void* state, const float* vscale, int Ftot, int HW,
-                             int halves, float guidance, const float* row, void* stream);
-int md_cfg_unipc_step_apg(void* latents, const void* noise_sum, const void* counter, void* state, const void* momentum_buf, const float* coef,
-                          int Ftot, int HW, int halves, float guidance, const float* row, void* stream);
-int md_cfg_unipc_step_pag(void* latents, const void* noise_sum, const void* counter, void* state, const void* perturbed_sum, int Ftot, int HW,
-                          int halves, float guidance, float pag_scale, const float* row, void* stream);
 
 /* The unconditional plane of a sampling step that evaluated the conditional half only (guidance_interval= after Kynkaanniemi et al.,
  * "Applying Guidance in a Limited Interval", arXiv 2404.07724; uncond_cache_interval= after the CFG cache of FasterCache, arXiv 2410.19355,

@@ -164,8 +164,6 @@ extern "C" int md_window_accumulate_weighted(const void* pred, void* noise_sum, 
 // reference takes the window SUM as it is: its division by the counter sits inside `if do_classifier_free_guidance:`, so neither the
 // counter nor the second half is read.  T = float (one element at index i of `total`) or floatx4 (one pixel).  c_out, where given,
 // receives c (the rescale statistics; halves == 2 only).
-// SCALED in the step kernels (guidance rescale): they multiply this v by *vscale, the factor md_cfg_guidance_rescale left in device
-// memory; the unscaled instantiation has neither the load nor the multiply.
 template <typename T>
 __device__ __forceinline__ T guided_v(const T* __restrict__ ns, const float* __restrict__ counter, long i, long total, int fr, int halves,
                                       float guidance, T* c_out = nullptr) {
@@ -215,29 +213,71 @@ __device__ __forceinline__ T pag_v(const T* __restrict__ ns, const T* __restrict
   return v + (pag_scale * inv) * d;
 }
 
-// What a step entry adds to the plain one: nothing, the guidance-rescale factor (*_scaled), APG's momentum buffer and per-frame
-// coefficients (*_apg) or PAG's perturbed plane and scale (*_pag).
+// ---- the guide of a step: what an entry adds to the plain one -------------------------------------------------------------------
+//   guide          entries     aux0                           aux1                auxs
+//   GUIDE_PLAIN    (plain)     -                              -                   -
+//   GUIDE_SCALED   *_scaled    vscale, one fp32 (the factor   -                   -
+//                              md_cfg_guidance_rescale left)
+//   GUIDE_APG      *_apg       momentum buffer [Ftot][HW][4]  coef [Ftot][2]      gs = (guidance - 1) / sigma_s, formed by the launcher
+//   GUIDE_PAG      *_pag       perturbed plane [Ftot][HW][4]  -                   pag_scale
+// all fp32 in device memory, as md_cfg_guidance_rescale / md_cfg_apg_prepare / the window accumulation left them.
+enum { GUIDE_PLAIN = 0, GUIDE_SCALED, GUIDE_APG, GUIDE_PAG };
+
 struct StepExtra {
-  const float* vscale = nullptr;
-  const float* mom = nullptr;
-  const float* coef = nullptr;
-  const float* pag_sum = nullptr;
-  float pag_scale = 0.f;
-  bool scaled = false, apg = false, pag = false;
+  int guide = GUIDE_PLAIN;
+  const float* aux0 = nullptr;
+  const float* aux1 = nullptr;
+  float auxs = 0.f;
 };
 
+static StepExtra step_scaled(const float* vscale) { return {GUIDE_SCALED, vscale, nullptr, 0.f}; }
+static StepExtra step_apg(const void* momentum_buf, const float* coef) { return {GUIDE_APG, (const float*)momentum_buf, coef, 0.f}; }
+static StepExtra step_pag(const void* perturbed_sum, float pag_scale) { return {GUIDE_PAG, (const float*)perturbed_sum, nullptr, pag_scale}; }
+
+// The v a step kernel updates with, for the element or pixel i (T as in guided_v): the one place that chooses between guided_v, apg_v and
+// pag_v.  aux0 / aux1: the guide's buffers; sc: its scalar, which for GUIDE_SCALED is *vscale as the kernel read it once ahead of its loop
+// (the plain instantiation has neither the load nor the multiply).  a, s, x: the step's alpha_s / sigma_s and the latent, which APG reads.
+// The fence: under PAG v leaves as a finished value, opaque to the compiler.  pag_scale == 0 must give the plain entry's bits, and without
+// the fence the update that follows is free to fuse its products with other sums than in the plain instantiation (DDIM's did, while its
+// update was left to contraction: sb x + sa v instead of sa v + sb x).  It is unconditional: UniPC's PAG instantiation, written without
+// one, gives the same bits with it (50 of 50 cases on an MI355X, profiles/step_kernels_refactor.log), so no sampler needs to opt out.
+// The other guides promise no bits of another entry and have none.
+template <int GUIDE, typename T>
+__device__ __forceinline__ T step_v(const T* __restrict__ ns, const float* __restrict__ counter, const T* __restrict__ aux0,
+                                    const float* __restrict__ aux1, float sc, long i, long total, int fr, int halves, float guidance, float a,
+                                    float s, T x) {
+  T v;
+  if constexpr (GUIDE == GUIDE_APG)
+    v = apg_v(ns, counter, aux0, aux1, i, total, fr, guidance, a, s, sc, x);
+  else if constexpr (GUIDE == GUIDE_PAG)
+    v = pag_v(ns, aux0, counter, i, total, fr, halves, guidance, sc);
+  else
+    v = guided_v(ns, counter, i, total, fr, halves, guidance);
+  if constexpr (GUIDE == GUIDE_SCALED) v *= sc;
+  if constexpr (GUIDE == GUIDE_PAG) asm volatile("" : "+v"(v));
+  return v;
+}
+
+// Launches the instantiation of a step kernel that ex.guide names, one thread per element or pixel up to one grid round of 4096 x 256.
+// k: the four instantiations in the enum's order; args: the kernel's arguments up to the guide's three, which follow from ex.
+template <typename K, typename... Args>
+static void step_launch(K* const (&k)[4], const StepExtra& ex, float apg_gs, long threads, void* stream, Args... args) {
+  const int grid = (int)((threads + 255) / 256 < 4096 ? (threads + 255) / 256 : 4096);
+  hipLaunchKernelGGL(k[ex.guide], dim3(grid), dim3(256), 0, (hipStream_t)stream, args..., ex.aux0, ex.aux1,
+                     ex.guide == GUIDE_APG ? apg_gs : ex.auxs);
+}
+
 // The argument rules all step entry points share.  Alignment and a kernel's own buffers are its launcher's business.
-// noise_coeff: the factor of variance_noise (eta / c_z).  ex.scaled: the *_scaled entries, which need CFG and the factor; ex.apg: the
-// *_apg entries, which need CFG, the momentum buffer and the coefficients; ex.pag: the *_pag entries, which need the perturbed plane and a
-// finite scale >= 0, with or without CFG.
+// noise_coeff: the factor of variance_noise (eta / c_z).  The *_scaled entries need CFG and the factor; the *_apg entries CFG, the momentum
+// buffer and the coefficients; the *_pag entries the perturbed plane and a finite scale >= 0, with or without CFG.
 static int cfg_step_check(const char* who, const void* latents, const void* noise_sum, const void* counter, const void* variance_noise,
                           const StepExtra& ex, int Ftot, int HW, int halves, float noise_coeff, std::initializer_list<float> coeffs) {
   MD_CHECK_ARG(Ftot > 0 && HW > 0 && (halves == 1 || halves == 2), "%s: bad arguments", who);
   MD_CHECK_ARG(latents && noise_sum && (halves == 1 || counter), "%s: null pointer", who);
-  MD_CHECK_ARG(!ex.scaled || (halves == 2 && ex.vscale && ((uintptr_t)ex.vscale % 4) == 0),
+  MD_CHECK_ARG(ex.guide != GUIDE_SCALED || (halves == 2 && ex.aux0 && ((uintptr_t)ex.aux0 % 4) == 0),
                "%s: guidance rescale needs halves == 2 and a 4-byte aligned vscale", who);
-  MD_CHECK_ARG(!ex.apg || (halves == 2 && ex.mom && ex.coef), "%s: APG needs halves == 2, the momentum buffer and coef", who);
-  MD_CHECK_ARG(!ex.pag || (ex.pag_sum && __builtin_isfinite(ex.pag_scale) && ex.pag_scale >= 0.f),
+  MD_CHECK_ARG(ex.guide != GUIDE_APG || (halves == 2 && ex.aux0 && ex.aux1), "%s: APG needs halves == 2, the momentum buffer and coef", who);
+  MD_CHECK_ARG(ex.guide != GUIDE_PAG || (ex.aux0 && __builtin_isfinite(ex.auxs) && ex.auxs >= 0.f),
                "%s: PAG needs the perturbed plane and a finite pag_scale >= 0", who);
   for (const float c : coeffs) MD_CHECK_ARG(__builtin_isfinite(c), "%s: non-finite coefficient", who);
   MD_CHECK_ARG(noise_coeff == 0.f || variance_noise, "%s: a non-zero noise coefficient needs variance_noise", who);
@@ -250,63 +290,42 @@ static int cfg_pixel_alignment_check(const char* who, const void* latents, const
   MD_CHECK_ARG(((uintptr_t)latents % 8) == 0 && ((uintptr_t)noise_sum % 16) == 0 && ((uintptr_t)history % 16) == 0 &&
                    ((uintptr_t)variance_noise % 8) == 0,
                "%s: latents / variance_noise need 8-byte, noise_sum / history 16-byte alignment", who);
-  MD_CHECK_ARG(!ex.apg || (((uintptr_t)ex.mom % 16) == 0 && ((uintptr_t)ex.coef % 4) == 0),
+  MD_CHECK_ARG(ex.guide != GUIDE_APG || (((uintptr_t)ex.aux0 % 16) == 0 && ((uintptr_t)ex.aux1 % 4) == 0),
                "%s: the momentum buffer needs 16-byte, coef 4-byte alignment", who);
-  MD_CHECK_ARG(!ex.pag || ((uintptr_t)ex.pag_sum % 16) == 0, "%s: the perturbed plane needs 16-byte alignment", who);
+  MD_CHECK_ARG(ex.guide != GUIDE_PAG || ((uintptr_t)ex.aux0 % 16) == 0, "%s: the perturbed plane needs 16-byte alignment", who);
   return MD_OK;
 }
 
 // ---- CFG combine + DDIM v-prediction step -------------------------------------------------------------------------------
-//   v   = guided_v                                                                   (the *_apg entry: apg_v; *_pag: pag_v)
+//   v   = step_v                                                                     the guided v under the entry's guide
 //   x0  = sqrt(a_t) x - sqrt(1-a_t) v ;  eps = sqrt(a_t) v + sqrt(1-a_t) x
 //   x'  = sqrt(a_prev) x0 + sqrt(1-a_prev) eps                                      DDIMScheduler.step
 // latents: [Ftot][HW][4] fp16, updated in place (fp32 arithmetic, one rounding).
-// ddim_update is the update every flavour of the kernel shares, from v on.
+// ddim_update is the update every guide of the kernel shares, from v on.  x0 and eps are spelled out as one rounded product and one fma
+// each: left to contraction, which product is rounded follows from where the kernel happens to load x, and the entries' bits with it.
+// x0 under APG rounds sa x, the product its D_c already holds, and under every other guide sb v; both are the bits each entry has always
+// given, so both stay.
+template <int GUIDE>
 __device__ __forceinline__ void ddim_update(half_t* __restrict__ lat, const half_t* __restrict__ variance_noise, long idx, float x, float v, float sa,
                                             float sb, float sap, float sdir, float sigma) {
-  const float x0 = sa * x - sb * v;
-  const float ep = sa * v + sb * x;
+  const float x0 = GUIDE == GUIDE_APG ? __builtin_fmaf(-sb, v, sa * x) : __builtin_fmaf(sa, x, -(sb * v));
+  const float ep = __builtin_fmaf(sa, v, sb * x);
   float out = sap * x0 + sdir * ep;                              // sdir = sqrt(1 - alpha_prev - sigma^2)
   if (variance_noise) out += sigma * (float)variance_noise[idx];  // eta > 0: + sigma_t * z
   lat[idx] = (half_t)out;
 }
 
-template <bool SCALED>
+// One element per thread.  APG's mom / coef are md_cfg_apg_prepare's at THIS step's (sa, sb).
+template <int GUIDE>
 __global__ void cfg_ddim_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
                                 const half_t* __restrict__ variance_noise, int Ftot, int HW4, int halves, float guidance, float sa, float sb, float sap,
-                                float sdir, float sigma, const float* __restrict__ vscale) {
+                                float sdir, float sigma, const float* __restrict__ aux0, const float* __restrict__ aux1, float auxs) {
   const long total = (long)Ftot * HW4;
-  const float vs = SCALED ? *vscale : 1.f;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    float v = guided_v(noise_sum, counter, idx, total, (int)(idx / HW4), halves, guidance);
-    if constexpr (SCALED) v *= vs;
-    ddim_update(lat, variance_noise, idx, (float)lat[idx], v, sa, sb, sap, sdir, sigma);
-  }
-}
-
-// The APG flavour: mom [Ftot][HW][4] fp32 and coef [Ftot][2] fp32 of md_cfg_apg_prepare at THIS step's (sa, sb); gs = (guidance - 1) / sb.
-__global__ void cfg_ddim_apg_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
-                                    const half_t* __restrict__ variance_noise, int Ftot, int HW4, float guidance, float sa, float sb, float sap,
-                                    float sdir, float sigma, const float* __restrict__ mom, const float* __restrict__ coef, float gs) {
-  const long total = (long)Ftot * HW4;
+  const float sc = GUIDE == GUIDE_SCALED ? *aux0 : auxs;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const float x = (float)lat[idx];
-    const float v = apg_v(noise_sum, counter, mom, coef, idx, total, (int)(idx / HW4), guidance, sa, sb, gs, x);
-    ddim_update(lat, variance_noise, idx, x, v, sa, sb, sap, sdir, sigma);
-  }
-}
-
-// The PAG flavour: pag_sum [Ftot][HW][4] fp32, the perturbed plane; halves 1 or 2.
-__global__ void cfg_ddim_pag_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
-                                    const half_t* __restrict__ variance_noise, int Ftot, int HW4, int halves, float guidance, float sa, float sb,
-                                    float sap, float sdir, float sigma, const float* __restrict__ pag_sum, float pag_scale) {
-  const long total = (long)Ftot * HW4;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    float v = pag_v(noise_sum, pag_sum, counter, idx, total, (int)(idx / HW4), halves, guidance, pag_scale);
-    // v goes into the update as a finished value: without this the compiler is free to fuse ddim_update's products with other sums than in
-    // cfg_ddim_kernel (it did: sb x + sa v instead of sa v + sb x), and pag_scale == 0 would not be the plain kernel's bits
-    asm volatile("" : "+v"(v));
-    ddim_update(lat, variance_noise, idx, (float)lat[idx], v, sa, sb, sap, sdir, sigma);
+    const float v = step_v<GUIDE>(noise_sum, counter, aux0, aux1, sc, idx, total, (int)(idx / HW4), halves, guidance, sa, sb, x);
+    ddim_update<GUIDE>(lat, variance_noise, idx, x, v, sa, sb, sap, sdir, sigma);
   }
 }
 
@@ -315,57 +334,27 @@ static int cfg_ddim_launch(void* latents, const void* noise_sum, const void* cou
   if (cfg_step_check(who, latents, noise_sum, counter, variance_noise, ex, Ftot, HW, halves, eta, {guidance, alpha_t, alpha_prev, eta}))
     return MD_ERR_ARG;
   MD_CHECK_ARG(eta >= 0.f, "%s: eta must be >= 0", who);
-  if (ex.apg) {
+  // single-element accesses under every guide: the *_pag entry asks for natural alignment only, like the plain one, and the *_apg entry
+  // keeps the contract it was published with, md_cfg_multistep_step's
+  if (ex.guide == GUIDE_APG) {
     if (cfg_pixel_alignment_check(who, latents, noise_sum, nullptr, variance_noise, ex)) return MD_ERR_ARG;
     MD_CHECK_ARG(alpha_t >= 0.f && alpha_t < 1.f, "%s: APG divides by sqrt(1 - alpha_t): alpha_t must be in [0, 1)", who);
   }
-  // the PAG kernel accesses single elements, like the plain one: natural alignment is all it needs
-  MD_CHECK_ARG(!ex.pag || (((uintptr_t)latents % 2) == 0 && ((uintptr_t)variance_noise % 2) == 0 && ((uintptr_t)noise_sum % 4) == 0 &&
-                           ((uintptr_t)counter % 4) == 0 && ((uintptr_t)ex.pag_sum % 4) == 0),
+  MD_CHECK_ARG(ex.guide != GUIDE_PAG || (((uintptr_t)latents % 2) == 0 && ((uintptr_t)variance_noise % 2) == 0 &&
+                                         ((uintptr_t)noise_sum % 4) == 0 && ((uintptr_t)counter % 4) == 0 && ((uintptr_t)ex.aux0 % 4) == 0),
                "%s: latents / variance_noise need 2-byte, noise_sum / counter / the perturbed plane 4-byte alignment", who);
   // diffusers DDIMScheduler._get_variance: sigma_t^2 = eta^2 (1 - a_prev) / (1 - a_t) (1 - a_t / a_prev); a_t == 1 never occurs (t >= 0 of a
   // zero-terminal-SNR table has a_t < 1)
   const float var = eta > 0.f ? (1.f - alpha_prev) / (1.f - alpha_t) * (1.f - alpha_t / alpha_prev) : 0.f;
   const float sigma = eta * sqrtf(var > 0.f ? var : 0.f);
   const float dir2 = 1.f - alpha_prev - sigma * sigma;
-  const long total = (long)Ftot * HW * 4;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   const half_t* z = eta > 0.f ? (const half_t*)variance_noise : nullptr;
   const float sa = sqrtf(alpha_t), sb = sqrtf(1.f - alpha_t), sap = sqrtf(alpha_prev), sdir = sqrtf(dir2 > 0.f ? dir2 : 0.f);
-  if (ex.apg)
-    hipLaunchKernelGGL(cfg_ddim_apg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
-                       (const float*)counter, z, Ftot, HW * 4, guidance, sa, sb, sap, sdir, sigma, ex.mom, ex.coef, (guidance - 1.f) / sb);
-  else if (ex.pag)
-    hipLaunchKernelGGL(cfg_ddim_pag_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
-                       (const float*)counter, z, Ftot, HW * 4, halves, guidance, sa, sb, sap, sdir, sigma, ex.pag_sum, ex.pag_scale);
-  else
-    hipLaunchKernelGGL(ex.scaled ? cfg_ddim_kernel<true> : cfg_ddim_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents,
-                       (const float*)noise_sum, (const float*)counter, z, Ftot, HW * 4, halves, guidance, sa, sb, sap, sdir, sigma, ex.vscale);
+  step_launch({cfg_ddim_kernel<GUIDE_PLAIN>, cfg_ddim_kernel<GUIDE_SCALED>, cfg_ddim_kernel<GUIDE_APG>, cfg_ddim_kernel<GUIDE_PAG>}, ex,
+              (guidance - 1.f) / sb, (long)Ftot * HW * 4, stream, (half_t*)latents, (const float*)noise_sum, (const float*)counter, z, Ftot, HW * 4,
+              halves, guidance, sa, sb, sap, sdir, sigma);
   MD_CHECK_LAUNCH(who);
   return MD_OK;
-}
-
-static StepExtra step_scaled(const float* vscale) {
-  StepExtra ex;
-  ex.scaled = true;
-  ex.vscale = vscale;
-  return ex;
-}
-
-static StepExtra step_apg(const void* momentum_buf, const float* coef) {
-  StepExtra ex;
-  ex.apg = true;
-  ex.mom = (const float*)momentum_buf;
-  ex.coef = coef;
-  return ex;
-}
-
-static StepExtra step_pag(const void* perturbed_sum, float pag_scale) {
-  StepExtra ex;
-  ex.pag = true;
-  ex.pag_sum = (const float*)perturbed_sum;
-  ex.pag_scale = pag_scale;
-  return ex;
 }
 
 extern "C" int md_cfg_ddim_step(void* latents, const void* noise_sum, const void* counter, int Ftot, int HW, int halves, float guidance, float alpha_t,
@@ -401,7 +390,7 @@ extern "C" int md_cfg_ddim_step_pag(void* latents, const void* noise_sum, const 
 }
 
 // ---- CFG combine + DPM-Solver++ multistep step (orders 1 / 2, ODE or SDE; Lu et al., arXiv 2211.01095) ------------------
-//   v   = guided_v                                 (the *_apg entry: apg_v; *_pag: pag_v)
+//   v   = step_v                                   the guided v under the entry's guide
 //   m0  = alpha_s x - sigma_s v                    data prediction (x0) of this step
 //   x'  = c_x x + c_m0 m0 + c_m1 m1 + c_z z        m1 = the previous step's m0 (history), z = variance noise
 // The coefficients are host scalars (DPMSolverMultistepScheduler.multistep_coefficients): every solver variant is this one update.
@@ -419,54 +408,22 @@ __device__ __forceinline__ void multistep_update(half4_t* __restrict__ lat4, flo
   lat4[p] = __builtin_convertvector(out, half4_t);
 }
 
-template <bool SCALED>
+// APG's mom / coef are md_cfg_apg_prepare's at THIS step's (alpha_s, sigma_s).
+template <int GUIDE>
 __global__ void cfg_multistep_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
                                      float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, int halves,
                                      float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
-                                     const float* __restrict__ vscale) {
+                                     const float* __restrict__ aux0, const float* __restrict__ aux1, float auxs) {
   const long total = (long)Ftot * HW;  // pixels
   const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
+  const floatx4* a4 = reinterpret_cast<const floatx4*>(aux0);
   floatx4* hist = reinterpret_cast<floatx4*>(history);
   half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
-  const float vs = SCALED ? *vscale : 1.f;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-    floatx4 v = guided_v(ns, counter, p, total, (int)(p / HW), halves, guidance);
-    if constexpr (SCALED) v *= vs;
-    multistep_update(lat4, hist, variance_noise, p, __builtin_convertvector(lat4[p], floatx4), v, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z);
-  }
-}
-
-// The APG flavour: mom / coef of md_cfg_apg_prepare at THIS step's (alpha_s, sigma_s); gs = (guidance - 1) / sigma_s.
-__global__ void cfg_multistep_apg_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
-                                         float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, float guidance,
-                                         float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z, const float* __restrict__ mom,
-                                         const float* __restrict__ coef, float gs) {
-  const long total = (long)Ftot * HW;  // pixels
-  const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
-  const floatx4* mom4 = reinterpret_cast<const floatx4*>(mom);
-  floatx4* hist = reinterpret_cast<floatx4*>(history);
-  half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
+  const float sc = GUIDE == GUIDE_SCALED ? *aux0 : auxs;
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const floatx4 x = __builtin_convertvector(lat4[p], floatx4);
-    const floatx4 v = apg_v(ns, counter, mom4, coef, p, total, (int)(p / HW), guidance, alpha_s, sigma_s, gs, x);
+    const floatx4 v = step_v<GUIDE>(ns, counter, a4, aux1, sc, p, total, (int)(p / HW), halves, guidance, alpha_s, sigma_s, x);
     multistep_update(lat4, hist, variance_noise, p, x, v, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z);
-  }
-}
-
-// The PAG flavour: pag_sum [Ftot][HW][4] fp32, the perturbed plane; halves 1 or 2.
-__global__ void cfg_multistep_pag_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum, const float* __restrict__ counter,
-                                         float* __restrict__ history, const half_t* __restrict__ variance_noise, int Ftot, int HW, int halves,
-                                         float guidance, float alpha_s, float sigma_s, float c_x, float c_m0, float c_m1, float c_z,
-                                         const float* __restrict__ pag_sum, float pag_scale) {
-  const long total = (long)Ftot * HW;  // pixels
-  const floatx4* ns = reinterpret_cast<const floatx4*>(noise_sum);
-  const floatx4* pp = reinterpret_cast<const floatx4*>(pag_sum);
-  floatx4* hist = reinterpret_cast<floatx4*>(history);
-  half4_t* lat4 = reinterpret_cast<half4_t*>(lat);
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-    floatx4 v = pag_v(ns, pp, counter, p, total, (int)(p / HW), halves, guidance, pag_scale);
-    asm volatile("" : "+v"(v));  // as in cfg_ddim_pag_kernel: the update sees a finished v, like the plain kernel's
-    multistep_update(lat4, hist, variance_noise, p, __builtin_convertvector(lat4[p], floatx4), v, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z);
   }
 }
 
@@ -478,22 +435,12 @@ static int cfg_multistep_launch(void* latents, const void* noise_sum, const void
     return MD_ERR_ARG;
   MD_CHECK_ARG(history, "%s: null history", who);
   if (cfg_pixel_alignment_check(who, latents, noise_sum, history, variance_noise, ex)) return MD_ERR_ARG;
-  MD_CHECK_ARG(!ex.apg || sigma_s > 0.f, "%s: APG divides by sigma_s: it must be > 0", who);
-  const long total = (long)Ftot * HW;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  MD_CHECK_ARG(ex.guide != GUIDE_APG || sigma_s > 0.f, "%s: APG divides by sigma_s: it must be > 0", who);
   const half_t* z = c_z != 0.f ? (const half_t*)variance_noise : nullptr;
-  if (ex.apg)
-    hipLaunchKernelGGL(cfg_multistep_apg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
-                       (const float*)counter, (float*)history, z, Ftot, HW, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, ex.mom, ex.coef,
-                       (guidance - 1.f) / sigma_s);
-  else if (ex.pag)
-    hipLaunchKernelGGL(cfg_multistep_pag_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (half_t*)latents, (const float*)noise_sum,
-                       (const float*)counter, (float*)history, z, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, ex.pag_sum,
-                       ex.pag_scale);
-  else
-    hipLaunchKernelGGL(ex.scaled ? cfg_multistep_kernel<true> : cfg_multistep_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (half_t*)latents, (const float*)noise_sum, (const float*)counter, (float*)history, z, Ftot, HW, halves, guidance, alpha_s,
-                       sigma_s, c_x, c_m0, c_m1, c_z, ex.vscale);
+  step_launch({cfg_multistep_kernel<GUIDE_PLAIN>, cfg_multistep_kernel<GUIDE_SCALED>, cfg_multistep_kernel<GUIDE_APG>,
+               cfg_multistep_kernel<GUIDE_PAG>},
+              ex, (guidance - 1.f) / sigma_s, (long)Ftot * HW, stream, (half_t*)latents, (const float*)noise_sum, (const float*)counter,
+              (float*)history, z, Ftot, HW, halves, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z);
   MD_CHECK_LAUNCH(who);
   return MD_OK;
 }
@@ -527,7 +474,7 @@ extern "C" int md_cfg_multistep_step_pag(void* latents, const void* noise_sum, c
 }
 
 // ---- CFG combine + UniPC correct-then-predict step (orders 1 - 3; Zhao et al., arXiv 2302.04867, data-prediction form) -----------------
-//   v    = guided_v                                          (the *_scaled entry: times *vscale; *_apg: apg_v; *_pag: pag_v)
+//   v    = step_v                                            the guided v under the entry's guide
 //   m_t  = alpha_s x - sigma_s v                             data prediction at this step's point, x the fp16 latent the UNet saw
 //   x^c  = cc_x x_last + cc_m m_t + cc_0 H0 + cc_1 H1 + cc_2 H2      UniC from the previous point to this one; corrector off: x^c = x
 //   x'   = pc_x x^c + pc_m m_t + pc_0 H0 + pc_1 H1                   UniP from this point to the next, stored as the fp16 latent
@@ -544,10 +491,7 @@ struct UniPCRow {
   int correct;
 };
 
-enum { UNIPC_PLAIN = 0, UNIPC_SCALED, UNIPC_APG, UNIPC_PAG };
-
-// aux0 / aux1 / auxs: SCALED (vscale, -, -), APG (mom, coef, gs = (guidance - 1) / sigma_s), PAG (pag_sum, -, pag_scale)
-template <int FLAVOUR>
+template <int GUIDE>
 __global__ __launch_bounds__(256) void cfg_unipc_kernel(half_t* __restrict__ lat, const float* __restrict__ noise_sum,
                                                         const float* __restrict__ counter, float* __restrict__ state, int Ftot, int HW, int halves,
                                                         float guidance, UniPCRow r, const float* __restrict__ aux0, const float* __restrict__ aux1,
@@ -559,18 +503,10 @@ __global__ __launch_bounds__(256) void cfg_unipc_kernel(half_t* __restrict__ lat
   floatx4* xl = reinterpret_cast<floatx4*>(state);
   floatx4 *H0 = xl + total, *H1 = H0 + total, *H2 = H1 + total;
   const bool rd0 = r.cc_0 != 0.f || r.pc_0 != 0.f, rd1 = r.cc_1 != 0.f || r.pc_1 != 0.f, rd2 = r.cc_2 != 0.f;
-  const float vs = FLAVOUR == UNIPC_SCALED ? *aux0 : 1.f;
+  const float sc = GUIDE == GUIDE_SCALED ? *aux0 : auxs;
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
     const floatx4 x = __builtin_convertvector(lat4[p], floatx4);
-    const int fr = (int)(p / HW);
-    floatx4 v;
-    if constexpr (FLAVOUR == UNIPC_APG)
-      v = apg_v(ns, counter, a4, aux1, p, total, fr, guidance, r.alpha_s, r.sigma_s, auxs, x);
-    else if constexpr (FLAVOUR == UNIPC_PAG)
-      v = pag_v(ns, a4, counter, p, total, fr, halves, guidance, auxs);
-    else
-      v = guided_v(ns, counter, p, total, fr, halves, guidance);
-    if constexpr (FLAVOUR == UNIPC_SCALED) v *= vs;
+    const floatx4 v = step_v<GUIDE>(ns, counter, a4, aux1, sc, p, total, (int)(p / HW), halves, guidance, r.alpha_s, r.sigma_s, x);
     const floatx4 mt = r.alpha_s * x - r.sigma_s * v;
     floatx4 h0, h1, h2;
     if (rd0) h0 = H0[p];
@@ -605,24 +541,11 @@ static int cfg_unipc_launch(void* latents, const void* noise_sum, const void* co
   MD_CHECK_ARG(state, "%s: null state", who);
   if (cfg_pixel_alignment_check(who, latents, noise_sum, state, nullptr, ex)) return MD_ERR_ARG;
   MD_CHECK_ARG(((uintptr_t)counter % 4) == 0, "%s: counter needs 4-byte alignment", who);
-  MD_CHECK_ARG(!ex.apg || row[1] > 0.f, "%s: APG divides by sigma_s: it must be > 0", who);
+  MD_CHECK_ARG(ex.guide != GUIDE_APG || row[1] > 0.f, "%s: APG divides by sigma_s: it must be > 0", who);
   const UniPCRow r = {row[0], row[1], row[2], row[3], row[4], row[5], row[6], row[7], row[8], row[9], row[10], row[11] != 0.f};
-  const long total = (long)Ftot * HW;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  const dim3 g(grid), b(256);
-  half_t* lat = (half_t*)latents;
-  const float *ns = (const float*)noise_sum, *cnt = (const float*)counter;
-  float* st = (float*)state;
-  hipStream_t s = (hipStream_t)stream;
-  if (ex.apg)
-    hipLaunchKernelGGL(cfg_unipc_kernel<UNIPC_APG>, g, b, 0, s, lat, ns, cnt, st, Ftot, HW, halves, guidance, r, ex.mom, ex.coef,
-                       (guidance - 1.f) / r.sigma_s);
-  else if (ex.pag)
-    hipLaunchKernelGGL(cfg_unipc_kernel<UNIPC_PAG>, g, b, 0, s, lat, ns, cnt, st, Ftot, HW, halves, guidance, r, ex.pag_sum, nullptr, ex.pag_scale);
-  else if (ex.scaled)
-    hipLaunchKernelGGL(cfg_unipc_kernel<UNIPC_SCALED>, g, b, 0, s, lat, ns, cnt, st, Ftot, HW, halves, guidance, r, ex.vscale, nullptr, 0.f);
-  else
-    hipLaunchKernelGGL(cfg_unipc_kernel<UNIPC_PLAIN>, g, b, 0, s, lat, ns, cnt, st, Ftot, HW, halves, guidance, r, nullptr, nullptr, 0.f);
+  step_launch({cfg_unipc_kernel<GUIDE_PLAIN>, cfg_unipc_kernel<GUIDE_SCALED>, cfg_unipc_kernel<GUIDE_APG>, cfg_unipc_kernel<GUIDE_PAG>}, ex,
+              (guidance - 1.f) / r.sigma_s, (long)Ftot * HW, stream, (half_t*)latents, (const float*)noise_sum, (const float*)counter,
+              (float*)state, Ftot, HW, halves, guidance, r);
   MD_CHECK_LAUNCH(who);
   return MD_OK;
 }

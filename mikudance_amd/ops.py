@@ -377,31 +377,72 @@ def add_noise(latents, x0, a, b):
     return latents
 
 
-def _step_buffers(latents, noise_sum, counter, ftot, hw, halves, noise_coeff, variance_noise, vscale):
-    """The checks cfg_ddim_step and cfg_multistep_step share -> (the three buffer pointers, the variance_noise pointer or 0)."""
+def _fp32_buffer(t, name, numel):
+    """A contiguous fp32 device buffer of `numel` elements -> its pointer."""
+    _chk(t, name, torch.float32)
+    assert t.is_contiguous() and t.numel() == numel
+    return t.data_ptr()
+
+
+def _step_buffers(latents, noise_sum, counter, ftot, hw, halves):
+    """The buffers every entry of the step tail takes -> their three pointers."""
     _chk(latents, "latents"); _chk(noise_sum, "noise_sum", torch.float32); _chk(counter, "counter", torch.float32)
     n = ftot * hw * 4
     assert halves in (1, 2) and latents.is_contiguous() and latents.numel() == n
     assert noise_sum.is_contiguous() and noise_sum.numel() == halves * n and counter.numel() >= ftot
+    return latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr()
+
+
+def _unipc_state_row(state, row, ftot, hw):
+    """The checks the cfg_unipc_step* wrappers share -> (state pointer, the row as 12 C floats in host memory)."""
+    assert len(row) == 12
+    return _fp32_buffer(state, "state", 4 * ftot * hw * 4), (ctypes.c_float * 12)(*(float(v) for v in row))
+
+
+def _cfg_step(sampler, latents, noise_sum, counter, ftot, hw, halves, guidance, coeffs, *, history=None, state=None, noise_coeff=0.0,
+              variance_noise=None, vscale=None, apg=None, pag=None, meta=None):
+    """The one call behind the cfg_*_step* wrappers:
+        md_cfg_<sampler>_step<guide>(latents, noise_sum, counter, <the sampler's buffers>, <the guide's buffers>, ftot, hw, halves, guidance,
+                                     <the guide's scalar>, <the sampler's coefficients>, stream)
+    sampler  "ddim": no buffer of its own; coeffs (alpha_t, alpha_prev), noise_coeff = eta, which follows them.  The plain entry at
+             eta == 0 (md_cfg_ddim_step) takes neither variance_noise nor eta; at eta != 0 it is md_cfg_ddim_step_eta.
+             "multistep": history, variance_noise; the six coeffs, noise_coeff = c_z, the last of them.
+             "unipc": state; coeffs is the row of 12, handed over as host floats.
+    guide    at most one of vscale (_scaled: the fp32 device factor), apg = (momentum_buf, coef) (_apg) and
+             pag = (perturbed_sum, pag_scale) (_pag)."""
+    n = ftot * hw * 4
+    bufs = _step_buffers(latents, noise_sum, counter, ftot, hw, halves)
+    z = 0
     if noise_coeff:
         _chk(variance_noise, "variance_noise")
         assert variance_noise is not None and variance_noise.is_contiguous() and variance_noise.numel() == n
+        z = variance_noise.data_ptr()
+    if sampler == "unipc":
+        sp, rp = _unipc_state_row(state, coeffs, ftot, hw)
+        mid, tail = (sp,), (rp,)
+    else:
+        mid, tail = (_fp32_buffer(history, "history", n), z) if sampler == "multistep" else (z,), tuple(float(c) for c in coeffs)
+    guide, ptrs, scalar = "", (), ()
     if vscale is not None:
         _chk(vscale, "vscale", torch.float32)
-    return (latents.data_ptr(), noise_sum.data_ptr(), counter.data_ptr()), _p(variance_noise) if noise_coeff else 0
+        guide, ptrs = "_scaled", (vscale.data_ptr(),)
+    elif apg is not None:
+        guide, ptrs = "_apg", (_fp32_buffer(apg[0], "momentum_buf", n), _fp32_buffer(apg[1], "coef", ftot * 2))
+    elif pag is not None:
+        guide, ptrs, scalar = "_pag", (_fp32_buffer(pag[0], "perturbed_sum", n),), (float(pag[1]),)
+    if sampler == "ddim":
+        if guide or noise_coeff:
+            guide, tail = guide or "_eta", tail + (float(noise_coeff),)
+        else:
+            mid = ()
+    _lib.call(f"md_cfg_{sampler}_step{guide}", *bufs, *mid, *ptrs, ftot, hw, halves, float(guidance), *scalar, *tail, _st(), meta=meta)
 
 
 def cfg_ddim_step(latents, noise_sum, counter, ftot, hw, guidance, alpha_t, alpha_prev, halves=2, eta=0.0, variance_noise=None, vscale=None):
     """eta > 0: `variance_noise` is the caller's N(0, 1) draw, fp16, laid out like `latents` (ftot, hw, 4).
     vscale: the fp32 device factor of cfg_guidance_rescale (md_cfg_ddim_step_scaled, any eta); None: the unscaled entry points."""
-    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, eta, variance_noise, vscale)
-    if vscale is not None:
-        name, ptrs, tail = "md_cfg_ddim_step_scaled", (z, vscale.data_ptr()), (float(eta),)
-    elif eta:
-        name, ptrs, tail = "md_cfg_ddim_step_eta", (z,), (float(eta),)
-    else:
-        name, ptrs, tail = "md_cfg_ddim_step", (), ()
-    _lib.call(name, *bufs, *ptrs, ftot, hw, halves, float(guidance), float(alpha_t), float(alpha_prev), *tail, _st())
+    _cfg_step("ddim", latents, noise_sum, counter, ftot, hw, halves, guidance, (alpha_t, alpha_prev), noise_coeff=eta,
+              variance_noise=variance_noise, vscale=vscale)
 
 
 def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z, halves=2,
@@ -409,18 +450,8 @@ def cfg_multistep_step(latents, noise_sum, counter, history, ftot, hw, guidance,
     """DPM-Solver++ multistep update (md_cfg_multistep_step): `history` is the fp32 (ftot, hw, 4) data-prediction buffer the caller keeps
     between steps; the coefficients are DPMSolverMultistepScheduler.multistep_coefficients(step_index).  c_z != 0: `variance_noise` is
     the caller's N(0, 1) draw, fp16, laid out like `latents`.  vscale: as in cfg_ddim_step (md_cfg_multistep_step_scaled)."""
-    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, c_z, variance_noise, vscale)
-    _chk(history, "history", torch.float32)
-    assert history.is_contiguous() and history.numel() == ftot * hw * 4
-    _lib.call("md_cfg_multistep_step" if vscale is None else "md_cfg_multistep_step_scaled", *bufs, history.data_ptr(), z,
-              *(() if vscale is None else (vscale.data_ptr(),)), ftot, hw, halves, float(guidance), float(alpha_s), float(sigma_s), float(c_x),
-              float(c_m0), float(c_m1), float(c_z), _st())
-
-
-def _apg_buffers(momentum_buf, coef, ftot, hw):
-    _chk(momentum_buf, "momentum_buf", torch.float32); _chk(coef, "coef", torch.float32)
-    assert momentum_buf.is_contiguous() and momentum_buf.numel() == ftot * hw * 4 and coef.is_contiguous() and coef.numel() == ftot * 2
-    return momentum_buf.data_ptr(), coef.data_ptr()
+    _cfg_step("multistep", latents, noise_sum, counter, ftot, hw, halves, guidance, (alpha_s, sigma_s, c_x, c_m0, c_m1, c_z), history=history,
+              noise_coeff=c_z, variance_noise=variance_noise, vscale=vscale)
 
 
 def cfg_apg_prepare(latents, noise_sum, counter, momentum_buf, coef, ftot, hw, alpha_s, sigma_s, momentum, eta, norm_threshold):
@@ -428,10 +459,10 @@ def cfg_apg_prepare(latents, noise_sum, counter, momentum_buf, coef, ftot, hw, a
     PER FRAME): updates the fp32 (ftot, hw, 4) `momentum_buf` in place, m = sigma_s (u - c) + momentum m (momentum == 0 never reads it), and
     writes the fp32 (ftot, 2) `coef` = (S, (1 - eta) S proj) per frame.  Both stay on the device: hand them to cfg_ddim_step_apg /
     cfg_multistep_step_apg with the same alpha / sigma.  The workspace is kept per (device, stream) and reused."""
-    bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, 0.0, None, None)
-    mp, cp = _apg_buffers(momentum_buf, coef, ftot, hw)
-    ws = _workspace("cfg_apg_prepare", noise_sum.device, _lib.load().md_cfg_apg_workspace_bytes(ftot, hw), torch.float64, 1 << 14)
     n = ftot * hw * 4
+    bufs = _step_buffers(latents, noise_sum, counter, ftot, hw, 2)
+    mp, cp = _fp32_buffer(momentum_buf, "momentum_buf", n), _fp32_buffer(coef, "coef", ftot * 2)
+    ws = _workspace("cfg_apg_prepare", noise_sum.device, _lib.load().md_cfg_apg_workspace_bytes(ftot, hw), torch.float64, 1 << 14)
     _lib.call("md_cfg_apg_prepare", *bufs, mp, ftot, hw, 2, float(alpha_s), float(sigma_s), float(momentum), float(eta), float(norm_threshold),
               ws.data_ptr(), ws.numel() * 8, cp, _st(), meta=(f"cfg_apg_prepare F={ftot} HW={hw}", 0.0, (2.0 + 8.0 + 8.0) * n))
     return coef
@@ -440,26 +471,16 @@ def cfg_apg_prepare(latents, noise_sum, counter, momentum_buf, coef, ftot, hw, a
 def cfg_ddim_step_apg(latents, noise_sum, counter, momentum_buf, coef, ftot, hw, guidance, alpha_t, alpha_prev, eta=0.0, variance_noise=None):
     """cfg_ddim_step under CFG with APG's guided output (md_cfg_ddim_step_apg): `momentum_buf` and `coef` as cfg_apg_prepare left them for this
     step at alpha_s = sqrt(alpha_t), sigma_s = sqrt(1 - alpha_t).  eta / variance_noise as in cfg_ddim_step."""
-    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, eta, variance_noise, None)
-    _lib.call("md_cfg_ddim_step_apg", *bufs, z, *_apg_buffers(momentum_buf, coef, ftot, hw), ftot, hw, 2, float(guidance), float(alpha_t),
-              float(alpha_prev), float(eta), _st())
+    _cfg_step("ddim", latents, noise_sum, counter, ftot, hw, 2, guidance, (alpha_t, alpha_prev), noise_coeff=eta, variance_noise=variance_noise,
+              apg=(momentum_buf, coef))
 
 
 def cfg_multistep_step_apg(latents, noise_sum, counter, history, momentum_buf, coef, ftot, hw, guidance, alpha_s, sigma_s, c_x, c_m0, c_m1, c_z,
                            variance_noise=None):
     """cfg_multistep_step under CFG with APG's guided output (md_cfg_multistep_step_apg): `momentum_buf` and `coef` as cfg_apg_prepare left them
     for this step at the same alpha_s, sigma_s; `history` receives alpha_s x - sigma_s v_g.  The rest as in cfg_multistep_step."""
-    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, c_z, variance_noise, None)
-    _chk(history, "history", torch.float32)
-    assert history.is_contiguous() and history.numel() == ftot * hw * 4
-    _lib.call("md_cfg_multistep_step_apg", *bufs, history.data_ptr(), z, *_apg_buffers(momentum_buf, coef, ftot, hw), ftot, hw, 2, float(guidance),
-              float(alpha_s), float(sigma_s), float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
-
-
-def _pag_plane(perturbed_sum, ftot, hw):
-    _chk(perturbed_sum, "perturbed_sum", torch.float32)
-    assert perturbed_sum.is_contiguous() and perturbed_sum.numel() == ftot * hw * 4
-    return perturbed_sum.data_ptr()
+    _cfg_step("multistep", latents, noise_sum, counter, ftot, hw, 2, guidance, (alpha_s, sigma_s, c_x, c_m0, c_m1, c_z), history=history,
+              noise_coeff=c_z, variance_noise=variance_noise, apg=(momentum_buf, coef))
 
 
 def cfg_ddim_step_pag(latents, noise_sum, counter, perturbed_sum, ftot, hw, guidance, pag_scale, alpha_t, alpha_prev, halves=2, eta=0.0,
@@ -467,54 +488,35 @@ def cfg_ddim_step_pag(latents, noise_sum, counter, perturbed_sum, ftot, hw, guid
     """cfg_ddim_step with perturbed-attention guidance (md_cfg_ddim_step_pag; arXiv 2403.17377): v + pag_scale inv (sum_c - perturbed_sum) in place
     of the guided v, with or without CFG.  `perturbed_sum`: fp32 (ftot, hw, 4), the perturbed evaluation accumulated over the windows like one
     plane of `noise_sum` (halves planes).  eta / variance_noise as in cfg_ddim_step."""
-    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, eta, variance_noise, None)
-    _lib.call("md_cfg_ddim_step_pag", *bufs, z, _pag_plane(perturbed_sum, ftot, hw), ftot, hw, halves, float(guidance), float(pag_scale),
-              float(alpha_t), float(alpha_prev), float(eta), _st())
+    _cfg_step("ddim", latents, noise_sum, counter, ftot, hw, halves, guidance, (alpha_t, alpha_prev), noise_coeff=eta,
+              variance_noise=variance_noise, pag=(perturbed_sum, pag_scale))
 
 
 def cfg_multistep_step_pag(latents, noise_sum, counter, history, perturbed_sum, ftot, hw, guidance, pag_scale, alpha_s, sigma_s, c_x, c_m0, c_m1,
                            c_z, halves=2, variance_noise=None):
     """cfg_multistep_step with perturbed-attention guidance (md_cfg_multistep_step_pag): `perturbed_sum` and pag_scale as in cfg_ddim_step_pag;
     `history` receives alpha_s x - sigma_s v of the PAG-guided v.  The rest as in cfg_multistep_step."""
-    bufs, z = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, c_z, variance_noise, None)
-    _chk(history, "history", torch.float32)
-    assert history.is_contiguous() and history.numel() == ftot * hw * 4
-    _lib.call("md_cfg_multistep_step_pag", *bufs, history.data_ptr(), z, _pag_plane(perturbed_sum, ftot, hw), ftot, hw, halves, float(guidance),
-              float(pag_scale), float(alpha_s), float(sigma_s), float(c_x), float(c_m0), float(c_m1), float(c_z), _st())
-
-
-def _unipc_state_row(state, row, ftot, hw):
-    """The checks the cfg_unipc_step* wrappers share -> (state pointer, the row as 12 C floats in host memory)."""
-    _chk(state, "state", torch.float32)
-    assert state.is_contiguous() and state.numel() == 4 * ftot * hw * 4
-    assert len(row) == 12
-    return state.data_ptr(), (ctypes.c_float * 12)(*(float(v) for v in row))
+    _cfg_step("multistep", latents, noise_sum, counter, ftot, hw, halves, guidance, (alpha_s, sigma_s, c_x, c_m0, c_m1, c_z), history=history,
+              noise_coeff=c_z, variance_noise=variance_noise, pag=(perturbed_sum, pag_scale))
 
 
 def cfg_unipc_step(latents, noise_sum, counter, state, ftot, hw, guidance, row, halves=2, vscale=None):
     """UniPC correct-then-predict update (md_cfg_unipc_step): `state` is the fp32 (4, ftot, hw, 4) buffer (x_last and the data predictions of
     the last three steps) the caller keeps between steps, uninitialised before the first; `row` is
     UniPCMultistepScheduler.unipc_coefficients(step_index).  vscale: as in cfg_ddim_step (md_cfg_unipc_step_scaled)."""
-    bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, 0.0, None, vscale)
-    sp, rp = _unipc_state_row(state, row, ftot, hw)
-    _lib.call("md_cfg_unipc_step" if vscale is None else "md_cfg_unipc_step_scaled", *bufs, sp, *(() if vscale is None else (vscale.data_ptr(),)),
-              ftot, hw, halves, float(guidance), rp, _st(), meta=(f"cfg_unipc_step F={ftot} HW={hw}", 0.0, (4.0 + 4.0 * halves + 32.0) * ftot * hw * 4))
+    _cfg_step("unipc", latents, noise_sum, counter, ftot, hw, halves, guidance, row, state=state, vscale=vscale,
+              meta=(f"cfg_unipc_step F={ftot} HW={hw}", 0.0, (4.0 + 4.0 * halves + 32.0) * ftot * hw * 4))
 
 
 def cfg_unipc_step_apg(latents, noise_sum, counter, state, momentum_buf, coef, ftot, hw, guidance, row):
     """cfg_unipc_step under CFG with APG's guided output (md_cfg_unipc_step_apg): `momentum_buf` and `coef` as cfg_apg_prepare left them for
     this step at the row's alpha_s, sigma_s; the data prediction kept in `state` is alpha_s x - sigma_s v_g."""
-    bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, 2, 0.0, None, None)
-    sp, rp = _unipc_state_row(state, row, ftot, hw)
-    _lib.call("md_cfg_unipc_step_apg", *bufs, sp, *_apg_buffers(momentum_buf, coef, ftot, hw), ftot, hw, 2, float(guidance), rp, _st())
+    _cfg_step("unipc", latents, noise_sum, counter, ftot, hw, 2, guidance, row, state=state, apg=(momentum_buf, coef))
 
 
 def cfg_unipc_step_pag(latents, noise_sum, counter, state, perturbed_sum, ftot, hw, guidance, pag_scale, row, halves=2):
     """cfg_unipc_step with perturbed-attention guidance (md_cfg_unipc_step_pag): `perturbed_sum` and pag_scale as in cfg_ddim_step_pag."""
-    bufs, _ = _step_buffers(latents, noise_sum, counter, ftot, hw, halves, 0.0, None, None)
-    sp, rp = _unipc_state_row(state, row, ftot, hw)
-    _lib.call("md_cfg_unipc_step_pag", *bufs, sp, _pag_plane(perturbed_sum, ftot, hw), ftot, hw, halves, float(guidance), float(pag_scale), rp,
-              _st())
+    _cfg_step("unipc", latents, noise_sum, counter, ftot, hw, halves, guidance, row, state=state, pag=(perturbed_sum, pag_scale))
 
 
 def cfg_uncond_cache(noise_sum, counter, delta, ftot, hw, mode, scale=1.0):

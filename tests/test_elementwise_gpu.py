@@ -1,9 +1,10 @@
 """GPU: the kernels of mikudance_amd/csrc/elementwise.hip in every form the package calls them and past one grid round, on the MI355X.
 pack / unpack / concat / window_accumulate are held to EXACT equality with tests/elementwise_ref.py (and with tests/fake_ops.py, whose
-emulations the CPU suite runs the pipeline on); the eight step kernels to float64 under the project's step error model,
+emulations the CPU suite runs the pipeline on); the DDIM and DPM-Solver++ step kernels under their four guides to float64 under the project's step error model,
 |got - want| <= U16 |want| + 2e-6 scale + 2^-24 (tests/test_apg_gpu.py section 2), at small sizes through the plain entries and at
 1 048 820 elements / 1 048 815 pixels, where every thread of the first 244 / 239 runs its grid-stride loop twice, with the elements of the
-second round asserted on their own.  tests/test_elementwise_ref_cpu.py shows that a correct fp32 evaluation passes the same bound on the same
+second round asserted on their own.  Section 6 takes UniPC's four past the round as well and holds all three samplers to the plain entry's
+bits at pag_scale == 0.  tests/test_elementwise_ref_cpu.py shows that a correct fp32 evaluation passes the same bound on the same
 inputs.  profiles/elementwise_tests.log holds every printed figure of a run on an MI355X."""
 import pytest
 import torch
@@ -14,6 +15,7 @@ from mikudance_amd import _lib, ops  # noqa: E402
 
 import elementwise_ref as E  # noqa: E402
 import fake_ops  # noqa: E402
+import test_unipc_gpu as U  # noqa: E402  (the float64 statement and bounds of the UniPC entries: _case, _row, _kernel, _check)
 
 DEV = torch.device("cuda:0")
 put = lambda t: t.to(DEV)
@@ -222,3 +224,59 @@ def test_step_past_one_grid_round_matches_float64(kind, ftot, h, w, flavour, hal
 def test_plain_ddim_at_the_exact_round_boundary(ftot, h, w):
     total = ftot * h * w * 4
     _step("ELEMENTWISE_STEP_BOUNDARY", "plain", "ddim-eta", ftot, h * w, 2, second_round_from=E.ROUND if total > E.ROUND else None)
+
+
+# ---- 6. what one step_v behind the three samplers makes natural
+@pytest.mark.parametrize("flavour,halves", E.LARGE_FLAVOURS)
+def test_unipc_past_one_grid_round_matches_float64(flavour, halves):
+    """The four cfg_unipc_kernel instantiations at the pixel count of LARGE_STEP_CASES (5 x 459 x 457 = 1 048 815: 239 pixels loop twice, the
+    round boundary inside frame 4), corrector on so that every plane is read: the float64 statement and the bounds of
+    test_unipc_gpu.test_every_entry_matches_float64, the latents' bound asserted once more over the pixels of the second round."""
+    _, ftot, h, w = E.LARGE_STEP_CASES[1]
+    assert ftot * h * w > E.ROUND
+    case, row = U._case(ftot, h * w, halves), U._row("on")
+    got, st, extra = U._kernel(flavour, case, row, case.state)
+    U._check("ELEMENTWISE_UNIPC_ROUND2", flavour, case, row, case.state, got, st, extra, second_round_from=E.ROUND)
+
+
+def _pag_or_plain(kind, case, state, s):
+    """One step on the case's inputs through the *_pag entry at pag_scale s, or through the plain entry (s None) -> (latents, history or state
+    or None) on the host."""
+    ftot, hw, halves, g = case.ftot, case.hw, case.halves, E.G_PAG
+    ld, nd, cd, pd = put(case.lat), put(case.ns), put(case.cnt), put(case.pp)
+    if kind.startswith("unipc"):
+        row, kept = U._row(kind[6:]), put(state)
+        if s is None:
+            ops.cfg_unipc_step(ld, nd, cd, kept, ftot, hw, g, row, halves=halves)
+        else:
+            ops.cfg_unipc_step_pag(ld, nd, cd, kept, pd, ftot, hw, g, s, row, halves=halves)
+    elif kind.startswith("ddim"):
+        a_t, a_p, eta = E._coefficients(kind)
+        kept, kw = None, dict(halves=halves, eta=eta, variance_noise=put(case.z) if eta else None)
+        if s is None:
+            ops.cfg_ddim_step(ld, nd, cd, ftot, hw, g, a_t, a_p, **kw)
+        else:
+            ops.cfg_ddim_step_pag(ld, nd, cd, pd, ftot, hw, g, s, a_t, a_p, **kw)
+    else:
+        co = E._coefficients(kind)
+        kept, kw = put(case.hist), dict(halves=halves, variance_noise=put(case.z) if co[5] else None)
+        if s is None:
+            ops.cfg_multistep_step(ld, nd, cd, kept, ftot, hw, g, *co, **kw)
+        else:
+            ops.cfg_multistep_step_pag(ld, nd, cd, kept, pd, ftot, hw, g, s, *co, **kw)
+    return ld.cpu(), None if kept is None else kept.cpu()
+
+
+@pytest.mark.parametrize("ftot,h,w", E.SMALL_STEP_CASES[:2])
+@pytest.mark.parametrize("kind", E.KINDS + ["unipc-on", "unipc-off"])
+def test_pag_scale_zero_is_the_plain_entry_bitwise(kind, ftot, h, w):
+    """pag_scale == 0 adds a zero to the guided v, and the update that follows must round as the plain entry's does: the same bits in the
+    latents and in the history / state, for every sampler, with and without CFG, on finite planes.  At PAG_S the result differs (the term is
+    there).  test_pag_gpu holds DDIM and multistep to this at (3, 13, 11) and (16, 16, 16); here also one pixel, and UniPC."""
+    for halves in (1, 2):
+        case = E.step_case("pag", ftot, h * w, halves, E.step_seed("pag", ftot, h * w, halves))
+        state = torch.randn((4, ftot, h * w, 4), generator=torch.Generator().manual_seed(ftot + h * w + halves))
+        zero, plain, live = (_pag_or_plain(kind, case, state, s) for s in (0.0, None, E.PAG_S))
+        assert torch.equal(E.bits(zero[0]), E.bits(plain[0])), (kind, halves)
+        assert zero[1] is None or torch.equal(zero[1].view(torch.int32), plain[1].view(torch.int32)), (kind, halves)
+        assert torch.isfinite(zero[0]).all() and not torch.equal(live[0], plain[0])
