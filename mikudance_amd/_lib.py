@@ -90,6 +90,14 @@ SIGNATURES = {
                                   c_long, c_long, c_long, c_long, P]),
     "md_frames_u8": (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_long, c_long, P]),
 }
+# Entry points declared beside their source instead of in include/mdance_hip.h: {header under csrc/: {symbol: signature}}.  Exported from the
+# same library and typed by load() like the table above.
+EXTENSION_SIGNATURES = {
+    "rel_l1.h": {
+        "md_rel_l1_workspace_bytes": (c_size_t, [c_int, c_int]),
+        "md_rel_l1_f16": (c_int, [P, c_int, P, c_int, c_int, c_int, P, c_size_t, P, P]),
+    },
+}
 
 _lib = None
 
@@ -107,7 +115,7 @@ def load():
                 f"{LIB_PATH} is missing: the HIP extension has not been built (run __graft_entry__.build()). "
                 "mikudance_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + [kv for table in EXTENSION_SIGNATURES.values() for kv in table.items()]:
             fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -29,7 +29,7 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      (an addition: smoothed-energy guidance, arXiv 2408.00760; default 0.0 = off)
     pipe(..., tile_attention=--tile_attention, tile_attention_shift=--tile_attention_shift)
                      (an addition: shifted-tile spatial self-attention, arXiv 2311.17528; default 1 = off)
-    pipe(..., deep_cache_interval=--deep_cache_interval, deep_cache_depth=--deep_cache_depth)
+    pipe(..., deep_cache_interval=--deep_cache_interval, deep_cache_depth=--deep_cache_depth, deep_cache_threshold=--deep_cache_threshold)
                      (an addition: DeepCache, arXiv 2312.00858: the deep part of the denoising UNet every N-th step only; default 1 = off)
     pipe(..., guidance_interval=--guidance_interval, uncond_cache_interval=--uncond_cache_interval)
                      (an addition: guidance on a stretch of the schedule only, arXiv 2404.07724, and the unconditional half on every N-th guided
@@ -191,6 +191,11 @@ def parse_args(argv=None):
     parser.add_argument("--deep_cache_depth", type=int, default=3, metavar="D",
                         help="(addition) DeepCache: how many skip connections, counted from conv_in, the steps between still evaluate "
                              "(this project's own index); 3 = the whole highest-resolution level on both sides")
+    parser.add_argument("--deep_cache_threshold", type=float, default=None, metavar="R",
+                        help="(addition) adaptive DeepCache (the accumulated relative-L1 rule of TeaCache, arXiv 2411.19108): a step evaluates "
+                             "the whole UNet when the relative change of its first skipped feature map, summed since the last full step, reaches "
+                             "R (> 0); --deep_cache_interval N (>= 2) then caps the shallow steps in a row at N - 1.  One host synchronisation "
+                             "per UNet call.  Default: the fixed every-N-th rule")
     parser.add_argument("--guidance_interval", type=_interval, default=(0.0, 1.0), metavar="LO,HI",
                         help="(addition) guidance in a limited interval (arXiv 2404.07724), an approximation that saves the unconditional half "
                              "of the denoising UNet: classifier-free guidance is applied at step k of --steps N only where LO N <= k < HI N, the "
@@ -342,7 +347,7 @@ def main(argv=None):
                seg_scale=args.seg_scale, seg_blur_sigma=args.seg_blur_sigma, seg_applied_layers=_layer_names(args.seg_layers),
                tile_attention=args.tile_attention, tile_attention_shift=args.tile_attention_shift,
                deep_cache_interval=args.deep_cache_interval, deep_cache_depth=args.deep_cache_depth,
-               guidance_interval=args.guidance_interval, uncond_cache_interval=args.uncond_cache_interval,
+               deep_cache_threshold=args.deep_cache_threshold, guidance_interval=args.guidance_interval, uncond_cache_interval=args.uncond_cache_interval,
                hires_scale=args.hires_scale, hires_strength=args.hires_strength, hires_mode=args.hires_mode, hires_steps=args.hires_steps,
                scene_motion_lowres_npy=scene_motion_lowres_npy, vae_tiling=args.vae_tiling, vae_tile_size=args.vae_tile_size,
                **(dict(output_type="uint8") if args.u8_output else {}))

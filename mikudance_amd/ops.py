@@ -761,3 +761,26 @@ def token_blur(x, B, Hh, Ww, sigma, out=None):
     _lib.call("md_token_blur_f16", x.data_ptr(), out.data_ptr(), B, Hh, Ww, C, wy.data_ptr(), wy.numel(), wx.data_ptr(), wx.numel(), ws.data_ptr(),
               _st(), meta=(f"token_blur B={B} {Hh}x{Ww} C={C} k={wy.numel()}x{wx.numel()}", 2.0 * n * (wy.numel() + wx.numel()), 12.0 * n))
     return out
+
+
+def rel_l1(a, b, out=None):
+    """The distance of adaptive DeepCache (md_rel_l1_f16): a, b fp16 of one shape (..., C), each contiguous or a channel slice of a wider
+    contiguous tensor (one uniform row pitch each, see _pixel_pitch; the two pitches may differ) -> 2 fp32 on the device,
+    (sum |a - b|, sum |b|), fp32 terms and sums in a fixed order: the same inputs give the same bits.  Nothing is read back: the caller does.
+    `out`: a contiguous fp32 destination of 2 elements.  The 16 KiB workspace is kept per (device, stream)."""
+    lda, ldb = _pixel_pitch(a, "a", align=1), _pixel_pitch(b, "b", align=1)
+    if a.shape != b.shape or a.numel() == 0 or a.device != b.device:
+        raise _lib.MdanceHipError(f"rel_l1: a and b must be non-empty, of one shape and on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    C = a.shape[-1]
+    rows = a.numel() // C
+    if rows >= 1 << 31 or max(lda, ldb) >= 1 << 31:
+        raise _lib.MdanceHipError(f"rel_l1: {rows} rows of pitch {lda} / {ldb} exceed the entry point's int arguments")
+    if out is None:
+        out = torch.empty((2,), device=a.device, dtype=torch.float32)
+    _chk(out, "out", torch.float32)
+    if out.shape != (2,) or not out.is_contiguous() or out.device != a.device:
+        raise _lib.MdanceHipError(f"rel_l1: out must be 2 contiguous fp32 on a's device, got {tuple(out.shape)}")
+    ws = _workspace("rel_l1", a.device, _lib.load().md_rel_l1_workspace_bytes(rows, C), floor=1 << 14)
+    _lib.call("md_rel_l1_f16", a.data_ptr(), lda, b.data_ptr(), ldb, rows, C, ws.data_ptr(), ws.numel() * 4, out.data_ptr(), _st(),
+              meta=(f"rel_l1 rows={rows} C={C}", 2.0 * rows * C, 4.0 * rows * C))
+    return out

@@ -87,6 +87,7 @@ class SamplingPlan:
     tile: Union[None, tuple] = None                # None: no tiled self-attention; (factors, shift), resolved: (UNet3DConditionModel.tile_attention_plan, shift)
     deep: Union[None, tuple] = None                # None: deep_cache_interval == 1, no DeepCache; (interval N, depth d), d checked against the UNet by _resolve_plan
     uncond: Union[None, tuple] = None              # None: guidance on every step from a full evaluation (the defaults, or no CFG); (lo, hi, n) of guidance_interval / uncond_cache_interval
+    deep_threshold: Optional[float] = None         # None: DeepCache's fixed rule (a key step every N-th step); a float > 0: the adaptive rule, N the cap
     sampler: str = "ddim"                          # which step the loop calls: "ddim" (md_cfg_ddim_step*), "dpm" (md_cfg_multistep_step*) or "unipc" (md_cfg_unipc_step*)
 
 
@@ -215,7 +216,7 @@ class MikuDanceVideoPipeline:
                 free_init_fast=False, apg=False, apg_eta=0.0, apg_norm_threshold=0.0, apg_momentum=0.0, pag_scale=0.0, pag_adaptive_scale=0.0,
                 pag_applied_layers=("mid",), kv_downsample=1, kv_downsample_mode="nearest", seg_scale=0.0, seg_blur_sigma=100.0,
                 seg_applied_layers=("mid",), tile_attention=1, tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3,
-                guidance_interval=(0.0, 1.0), uncond_cache_interval=1):
+                guidance_interval=(0.0, 1.0), uncond_cache_interval=1, deep_cache_threshold=None):
         """The loop of reference src/pipelines/pipeline_mikudance.py:573-686.
 
         latents             (1, 4, F, h, w)  initial noise (any float dtype, on the GPU)
@@ -391,6 +392,25 @@ class MikuDanceVideoPipeline:
                             list of a whole cache period is therefore the key step's.  This loop calls the window scheduler once, with index 0,
                             for every step (as the oracle does), so that holds by construction; a loop that moved its windows per step
                             would have to hold them still over each period
+        deep_cache_threshold  None (the default): DeepCache's fixed rule above, bitwise what it is without the keyword: the same operator calls,
+                            nothing allocated.  A number > 0: ADAPTIVE DeepCache, the accumulated relative-L1 rule of TeaCache (arXiv 2411.19108)
+                            on the "first block output" of first-block cache, which here is skip deep_cache_depth - 1: a shallow step computes
+                            it from the current latents anyway.  Needs deep_cache_interval >= 2, which becomes the CAP: at most N - 1 shallow
+                            steps in a row.  Every evaluation behind the first of a pass is an auto call (unet_3d_mix.DeepCacheSlot.auto): it
+                            runs the shallow part of the down path into a fresh buffer, ops.rel_l1 (md_rel_l1_f16, deterministic) gives
+                            r = sum |skip - skip of the step before| / sum |skip of the step before|, the host reads it -- ONE host
+                            synchronisation per UNet call, which the fixed rule does not have -- and adds it to the slot's accumulator; the
+                            call goes on as a key step iff the accumulator has reached the threshold, N calls have been made since the last
+                            key step, r is not finite or its denominator is 0, and resets the accumulator then; otherwise as a shallow step,
+                            after one copy of one channel slice.  math.inf: the cap alone decides, bitwise deep_cache_interval's fixed rule.
+                            The first step of every pass (FreeInit, each pass of hires_scale) is a key step.  One accumulator per (window,
+                            plane) slot: PAG's / SEG's plane decides on its own, and so does every window -- decisions are local, so
+                            window_parallel needs no new collective.  Composes with what deep_cache_interval > 1 composes with, two_queues
+                            included (one distance per clip-half queue, summed before the division).  ValueError, before anything runs, for
+                            zero, a negative number, NaN, a value that is no number, deep_cache_interval < 2, and together with
+                            guidance_interval / uncond_cache_interval.  self.last_deep_cache_trace lists what every evaluation of the last
+                            denoise() did, (step_i, window, plane, "key" | "shallow", r), step_i counting from 0 in every pass, on this rank;
+                            under the fixed rule r is None; None when DeepCache is off.  Image quality on real weights has not been assessed
         guidance_interval   (lo, hi), two finite numbers with 0 <= lo <= hi <= 1 (Kynkaanniemi et al., "Applying Guidance in a Limited Interval",
                             arXiv 2404.07724; the start / stop of diffusers' ClassifierFreeGuidance guider), an opt-in APPROXIMATION that trades
                             accuracy for time: classifier-free guidance is applied at schedule index k = t_start + step_i (video-to-video keeps the
@@ -432,7 +452,7 @@ class MikuDanceVideoPipeline:
             pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode, seg_scale=seg_scale,
             seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
             tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth,
-            guidance_interval=guidance_interval, uncond_cache_interval=uncond_cache_interval)
+            guidance_interval=guidance_interval, uncond_cache_interval=uncond_cache_interval, deep_cache_threshold=deep_cache_threshold)
         if init_latents is not None and tuple(init_latents.shape) != tuple(latents.shape):
             raise ValueError(f"init_latents of shape {tuple(init_latents.shape)} do not match latents of shape {tuple(latents.shape)}")
         ops.require_gpu(latents, "MikuDanceVideoPipeline.denoise")
@@ -494,15 +514,30 @@ class MikuDanceVideoPipeline:
             from .unet_3d_mix import DeepCacheSlot
             dc_slots = {}
 
+        self.last_deep_cache_trace = None if dc_slots is None else []       # what every evaluation of this call did: traced() below
+
         def deep_kw(wi, plane, key):
-            """forward_nhwc's deep_cache keyword for window wi: a key step fills the window's slot, a shallow step reuses it."""
+            """forward_nhwc's deep_cache keyword for window wi: a key step fills the window's slot, a shallow step reuses it.  Under
+            deep_cache_threshold the call decides (DeepCacheSlot.auto, one accumulator per slot; an empty slot, as at the first step of every
+            pass, makes it a fill) and `key` is not read."""
             if dc_slots is None:
                 return {}
             slot = dc_slots.get((wi, plane))
             if slot is None:
-                assert key, f"DeepCache: no slot for window {wi}, plane {plane} at a shallow step"
+                assert key or plan.deep_threshold is not None, f"DeepCache: no slot for window {wi}, plane {plane} at a shallow step"
                 slot = dc_slots[(wi, plane)] = DeepCacheSlot(plan.deep[1])
+            if plan.deep_threshold is not None:
+                return dict(deep_cache=slot.auto(plan.deep_threshold, plan.deep[0]))
             return dict(deep_cache=slot.fill() if key else slot.reuse())
+
+        def traced(step_i, wi, plane, key, kw):
+            """kw, the keyword of deep_kw, once its evaluation has been made: one more row (step_i, window, plane, "key" | "shallow", r) of
+            self.last_deep_cache_trace; r: the distance an adaptive call measured (None: the fixed rule, or a fill of an empty slot)."""
+            if kw:
+                slot = kw["deep_cache"]
+                fixed = plan.deep_threshold is None
+                self.last_deep_cache_trace.append((step_i, wi, plane, ("key" if key else "shallow") if fixed else slot.last,
+                                                   None if fixed else slot.last_distance))
         # guidance interval / cached unconditional half: d = c - u of the last full step, kept only when some step reuses it; no plan: no buffer,
         # no new call.  Under window_parallel every rank keeps its own identical copy (written after the all_reduce)
         uc_delta = None
@@ -622,8 +657,10 @@ class MikuDanceVideoPipeline:
                         # both clip-halves are packed from the SAME latents (batch stride 0 above): the layers in front of the first attention
                         # run once (self.share_first_layers = False: the literal evaluation of both halves, bit-identical)
                         if kind == "full":
+                            dkw = deep_kw(wi, 0, dc_key)
                             pred = den.forward_nhwc(x, nb, f, torch.full((nb,), float(t)), cross, halves_identical=self.share_first_layers,
-                                                    two_queues=self.two_queues, **sa_kw, **deep_kw(wi, 0, dc_key))
+                                                    two_queues=self.two_queues, **sa_kw, **dkw)
+                            traced(step_i, wi, 0, dc_key, dkw)
                             accumulate(pred, ns_main, counter, wi, nb)
                         else:
                             # ---- the conditional frames only (PAG's call below without its perturbation), into the c plane with the real counter;
@@ -633,8 +670,10 @@ class MikuDanceVideoPipeline:
                         if s_t > 0.0:
                             # ---- PAG / SEG: the conditional frames once more (the banks are still in place), the selected self-attention maps
                             # = identity / from blurred queries
+                            dkw = deep_kw(wi, 1, dc_key)
                             pred = den.forward_nhwc(x[(nb - 1) * f:], 1, f, torch.full((1,), float(t)), cross.rows(f, 2 * f) if do_cfg else cross,
-                                                    **pert_kw, **sa_kw, **deep_kw(wi, 1, dc_key))
+                                                    **pert_kw, **sa_kw, **dkw)
+                            traced(step_i, wi, 1, dc_key, dkw)
                             accumulate(pred, ns_pert, pert_counter, wi, 1)
                         reader.clear()
                         writer.clear()
@@ -665,7 +704,7 @@ class MikuDanceVideoPipeline:
                       free_init_iters, free_init_filter, free_init_order, free_init_spatial_stop, free_init_temporal_stop, free_init_fast, apg, apg_eta,
                       apg_norm_threshold, apg_momentum, pag_scale, pag_adaptive_scale, pag_applied_layers, kv_downsample, kv_downsample_mode,
                       seg_scale, seg_blur_sigma, seg_applied_layers, tile_attention=1, tile_attention_shift="cycle", deep_cache_interval=1,
-                      deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1, sampler="ddim", eta=0.0):
+                      deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1, sampler="ddim", eta=0.0, deep_cache_threshold=None):
         """Every refusal of denoise()'s sampling keywords (see its docstring) that needs no model -- every value is checked whether or not its
         feature is on, and neither UNet is called -- then what they resolve to -> SamplingPlan, still holding the layer names and the
         (factors, mode) that _resolve_plan hands to the denoising UNet.  has_init: there is a clip to start from (init_latents / video);
@@ -752,6 +791,17 @@ class MikuDanceVideoPipeline:
             raise ValueError("guidance_interval / uncond_cache_interval cannot be combined with deep_cache_interval > 1: a DeepCache slot is shaped by "
                              "the batch of the evaluation that filled it (both clip-halves), and a conditional-only step would meet a slot of the "
                              "other shape")
+        deep_thr = None
+        if deep_cache_threshold is not None:
+            from .unet_3d_mix import check_deep_cache_threshold
+            deep_thr = check_deep_cache_threshold(deep_cache_threshold)
+            if skips_uncond:
+                raise ValueError("guidance_interval / uncond_cache_interval cannot be combined with deep_cache_threshold: a DeepCache slot is shaped "
+                                 "by the batch of the evaluation that filled it (both clip-halves), and a conditional-only step would meet a slot "
+                                 "of the other shape")
+            if deep_cache_interval < 2:
+                raise ValueError(f"deep_cache_threshold={deep_cache_threshold!r} needs deep_cache_interval >= 2: the interval is the cap, at most "
+                                 f"deep_cache_interval - 1 shallow steps in a row, got deep_cache_interval={deep_cache_interval}")
         if sampler not in ("ddim", "dpm", "unipc"):
             raise ValueError(f"sampler must be 'ddim', 'dpm' or 'unipc', got {sampler!r}")
         if sampler == "unipc" and eta != 0:
@@ -770,7 +820,7 @@ class MikuDanceVideoPipeline:
                                            free_init_fast), strength, (kv_factors, kv_mode) if any(f > 1 for f in kv_factors) else None, guide,
                             (tile_factors, tile_shift) if any(f > 1 for f in tile_factors) else None,
                             (int(deep_cache_interval), int(deep_cache_depth)) if deep_cache_interval > 1 else None,
-                            (gi_lo, gi_hi, int(uncond_cache_interval)) if skips_uncond and guidance_scale > 1.0 else None, sampler)
+                            (gi_lo, gi_hi, int(uncond_cache_interval)) if skips_uncond and guidance_scale > 1.0 else None, deep_thr, sampler)
 
     def _sampler(self):
         """The sampling plan's name for what self.scheduler selects; any other scheduler counts as "ddim" until denoise() refuses it."""
@@ -1072,7 +1122,7 @@ class MikuDanceVideoPipeline:
                  kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), tile_attention=1,
                  tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1,
                  hires_scale=1, hires_strength=0.5, hires_mode="bicubic", hires_steps=None, scene_motion_lowres_npy=None, vae_tiling=False,
-                 vae_tile_size=None, **kwargs):
+                 vae_tile_size=None, deep_cache_threshold=None, **kwargs):
         """The reference call (src/pipelines/pipeline_mikudance.py:362-704) with denoise()'s sampling keywords (see its docstring), and:
 
         output_type         "tensor" (the default): `videos` is the reference's float32 (b, c, f, H, W) CPU tensor in [0, 1]; "uint8": a CPU
@@ -1136,7 +1186,7 @@ class MikuDanceVideoPipeline:
                        pag_applied_layers=pag_applied_layers, kv_downsample=kv_downsample, kv_downsample_mode=kv_downsample_mode,
                        seg_scale=seg_scale, seg_blur_sigma=seg_blur_sigma, seg_applied_layers=seg_applied_layers, tile_attention=tile_attention,
                        tile_attention_shift=tile_attention_shift, deep_cache_interval=deep_cache_interval, deep_cache_depth=deep_cache_depth,
-                       guidance_interval=guidance_interval, uncond_cache_interval=uncond_cache_interval)
+                       guidance_interval=guidance_interval, uncond_cache_interval=uncond_cache_interval, deep_cache_threshold=deep_cache_threshold)
         hires =self.hires_plan(height or 768, width or 768, num_inference_steps, hires_scale, hires_strength, hires_mode, hires_steps)
         if hires is None:
             self._resolve_plan(self.sampling_plan(num_inference_steps, guidance_scale, video is not None,

@@ -98,17 +98,30 @@ class DeepCacheSlot:
     Memory: one (nb f, H, W, C1 + Cs) fp16 buffer of skip d - 1 per slot (two of (f, ...) under two_queues), alive until the slot is dropped or
     filled again.  A reuse call uses the CURRENT time rows, context and banks for the layers it runs and reads nothing of a layer it skips.
     `store` is shared by the slots made with reuse() / fill(): {"sig": (nb, f, two_queues, halves_identical), "bufs": {half: buffer},
-    "written": halves whose hidden slice the fill call's up path has produced in place}."""
+    "written": halves whose hidden slice the fill call's up path has produced in place}.
+    mode "auto" (auto(threshold, max_run): adaptive DeepCache, the accumulated relative-L1 rule of TeaCache, arXiv 2411.19108, on the "first
+      block output" of first-block cache -- here skip d - 1, which a shallow step computes anyway): the CALL decides.  On an empty slot it is a
+      fill.  Otherwise it runs conv_in and the first d - 1 down operators as a reuse call does, except that the producer of skip d - 1 writes
+      into a FRESH concat buffer; ops.rel_l1(new skip slice, kept skip slice) gives (sum |new - kept|, sum |kept|) on the device, once per
+      clip-half queue, and the call reads them: its one host synchronisation.  r = sum of the first / sum of the second over the queues (inf
+      for a zero denominator); store["acc"] += r, store["run"] += 1.  The call goes on as a KEY step iff the denominator is 0, r is not finite,
+      acc >= threshold or run >= max_run: the rest of the down path, the mid block and the whole up path run, the fresh buffer becomes the
+      kept one as in a fill, acc = run = 0.  Otherwise it goes on as a SHALLOW step: ONE device copy of one channel slice per queue brings the
+      kept hidden state and the new skip into one buffer -- the new skip into the kept buffer, or, where the hidden slice is the narrower
+      one, the kept hidden state into the fresh buffer, which then becomes the kept one -- and the up path runs as in a reuse call.  Either
+      way the kept buffer holds THIS step's skip afterwards: the next comparison is against the step before, key or shallow.
+      The slot reports what the call did: `last` ("key" / "shallow") and `last_distance` (r; None for the fill on an empty slot)."""
 
-    MODES = ("fill", "reuse")
+    MODES = ("fill", "reuse", "auto")
 
-    def __init__(self, depth, mode="fill", store=None):
+    def __init__(self, depth, mode="fill", store=None, threshold=None, max_run=None):
         import numbers
         if not isinstance(depth, numbers.Integral) or isinstance(depth, bool) or depth < 1:
             raise ValueError(f"deep_cache_depth must be an integer >= 1, got {depth!r}")
         if mode not in self.MODES:
             raise ValueError(f"DeepCacheSlot: mode must be one of {self.MODES}, got {mode!r}")
         self.depth, self.mode, self.store = int(depth), mode, {} if store is None else store
+        self.threshold, self.max_run = threshold, max_run
 
     def fill(self):
         return DeepCacheSlot(self.depth, "fill", self.store)
@@ -116,12 +129,45 @@ class DeepCacheSlot:
     def reuse(self):
         return DeepCacheSlot(self.depth, "reuse", self.store)
 
+    def auto(self, threshold, max_run):
+        """The slot for an adaptive call: threshold a number > 0 (math.inf: only max_run forces a key step), max_run an integer >= 1 (a key
+        step at the latest when this many calls have been made since the last one, the key step counted: max_run - 1 shallow steps in a row)."""
+        import numbers
+        return DeepCacheSlot(self.depth, "auto", self.store, check_deep_cache_threshold(threshold, "DeepCacheSlot.auto: threshold"),
+                             _check_max_run(max_run, numbers))
+
     @property
     def filled(self):
         return bool(self.store.get("bufs"))
 
+    @property
+    def last(self):
+        """What the last auto call on this slot's store did: "key" or "shallow" (None: no auto call yet)."""
+        return self.store.get("last")
+
+    @property
+    def last_distance(self):
+        """r of the last auto call (None for a fill on an empty slot)."""
+        return self.store.get("last_distance")
+
     def drop(self):
         self.store.clear()
+
+
+def check_deep_cache_threshold(threshold, what="deep_cache_threshold"):
+    """The threshold of adaptive DeepCache as a float: a number > 0, math.inf included (then the cap alone decides); ValueError for zero, a
+    negative number, NaN and anything that is no number."""
+    import math
+    import numbers
+    if isinstance(threshold, bool) or not isinstance(threshold, numbers.Real) or math.isnan(threshold) or not threshold > 0:
+        raise ValueError(f"{what} must be a number > 0 (math.inf: the cap alone decides), got {threshold!r}")
+    return float(threshold)
+
+
+def _check_max_run(max_run, numbers):
+    if not isinstance(max_run, numbers.Integral) or isinstance(max_run, bool) or max_run < 1:
+        raise ValueError(f"DeepCacheSlot.auto: max_run must be an integer >= 1, got {max_run!r}")
+    return int(max_run)
 
 
 class _Skips:
@@ -145,10 +191,33 @@ class _Skips:
                                  f"{(B, H, W, c1 + cs)} on {device}")
         else:
             buf = torch.empty((B, H, W, c1 + cs), device=device, dtype=torch.float16)
-            if kept:
+            if kept and self.deep.mode == "fill":                        # (an undecided auto call: the fresh buffer waits in the stack for hand_over)
                 self.deep.store["bufs"][self.half] = buf
         self.stack.append((buf, c1))
         return buf[..., c1:]
+
+    def skip_pair(self):
+        """An undecided auto call behind its first depth - 1 down operators: (the new skip d - 1, the kept one), both channel slices."""
+        buf, c1 = self.stack[-1]
+        assert self.deep.mode == "auto" and len(self.stack) == self.deep.depth, "the down path did not stop at skip depth - 1"
+        return buf[..., c1:], self.deep.store["bufs"][self.half][..., c1:]
+
+    def hand_over(self, key):
+        """The decision of an auto call, for this clip-half (the caller then sets the call's mode to "fill" / "reuse").  key: the fresh buffer
+        becomes the kept one.  Shallow: one copy of the narrower channel slice -- the new skip into the kept buffer, which takes the fresh
+        one's place in the stack, or the kept hidden state into the fresh buffer, which becomes the kept one."""
+        fresh, c1 = self.stack[-1]
+        bufs = self.deep.store["bufs"]
+        if key:
+            bufs[self.half] = fresh
+            return
+        kept = bufs[self.half]
+        if fresh.shape[-1] - c1 <= c1:
+            kept[..., c1:].copy_(fresh[..., c1:])
+            self.stack[-1] = (kept, c1)
+        else:
+            fresh[..., :c1].copy_(kept[..., :c1])
+            bufs[self.half] = fresh
 
     def hidden_slot(self):
         """Where the up path writes the hidden state that meets the top skip: the left-hand slice of that skip's buffer."""
@@ -611,7 +680,10 @@ class UNet3DConditionModel(_UNetBase):
         reuse call for depth >= 2 (depth 1 shares conv_in only).  A reuse call never reads the bank, the cross-attention K / V or the time rows
         of a layer it skips, and projects a new context for the blocks it runs only.  ValueError, before any launch: a depth out of range; reuse
         with an empty slot or with a kept buffer whose shape, dtype or device does not fit this call; a reuse call whose (nb, f, two_queues,
-        halves_identical) differs from the fill call's.
+        halves_identical) differs from the fill call's.  A slot from DeepCacheSlot.auto(threshold, max_run) makes the CALL decide between the two
+        (adaptive DeepCache; DeepCacheSlot states the rule): a fill on an empty slot; otherwise a reuse call's refusals, the shallow part of
+        the down path into a fresh buffer, ops.rel_l1 against the kept skip, ONE host synchronisation to read it, and then the rest of a fill
+        or -- after one copy of one channel slice -- of a reuse call.  The slot reports the outcome (last, last_distance).
         halves_identical: the caller GUARANTEES that the two clip-halves of x hold the same latents (classifier-free guidance: the loop of
         src/pipelines/pipeline_mikudance.py:626-633 feeds `torch.cat([latents] * 2)`) -- with equal timesteps, conv_in and the first resnet
         (no attention in front of them: nothing has seen the context or the bank yet) then produce the same tensor for both halves, so
@@ -637,8 +709,9 @@ class UNet3DConditionModel(_UNetBase):
         b0 = self.down_blocks[0]
         queues = bool(share and two_queues and x.is_cuda and (b0.has_cross_attention or b0.motion_modules[0] is not None))
         if deep_cache is not None:                                       # every refusal before the first launch
-            self._deep_cache_begin(deep_cache, x, nb, f, (nb, f, bool(two_queues), bool(halves_identical)), queues)
+            deep_cache = self._deep_cache_begin(deep_cache, x, nb, f, (nb, f, bool(two_queues), bool(halves_identical)), queues)
         reuse = deep_cache is not None and deep_cache.mode == "reuse"
+        auto = deep_cache is not None and deep_cache.mode == "auto"      # undecided until the first depth - 1 down operators have run
         trows = self._time_rows(pk, timesteps, dev)                         # [nb, sumC]
         gf = 1 if self.use_inflated_groupnorm else f                        # plain nn.GroupNorm on 5-D: stats across frames
         B = x.shape[0]
@@ -654,27 +727,73 @@ class UNet3DConditionModel(_UNetBase):
             x = slot
             # the first resnet on one half (time rows of group 0 = those of group 1), then both halves from the copy
             r = b0.resnets[0]
-            if reuse and deep_cache.depth == 1:                          # DeepCache reuse at depth 1 runs no down layer: only conv_in is shared
-                pass
-            elif b0.has_cross_attention or b0.motion_modules[0] is not None:
-                first = r(x[:f], self._temb(pk, trows, r), f * hh * ww, gf).repeat(2, 1, 1, 1)
-            else:                                                        # the resnet is its layer's last operator: it writes the skip in place
-                dst = skips.slot(B, hh, ww, r.cout, dev)
-                r(x[:f], self._temb(pk, trows, r), f * hh * ww, gf, out=dst[:f])
+
+            def shared_first():
+                if b0.has_cross_attention or b0.motion_modules[0] is not None:
+                    return r(slot[:f], self._temb(pk, trows, r), f * hh * ww, gf).repeat(2, 1, 1, 1)
+                dst = skips.slot(B, hh, ww, r.cout, dev)                 # the resnet is its layer's last operator: it writes the skip in place
+                r(slot[:f], self._temb(pk, trows, r), f * hh * ww, gf, out=dst[:f])
                 dst[f:].copy_(dst[:f])
-                first = dst
+                return dst
+
+            if (reuse or auto) and deep_cache.depth == 1:                # DeepCache reuse at depth 1 runs no down layer: only conv_in is shared
+                pass                                                     # (an auto call that turns out a key step evaluates it behind its decision)
+            else:
+                first = shared_first()
         else:
             x = ops.conv3x3(x, pk["cin"], c0, bias=pk["cinb"], out=skips.slot(B, hh, ww, c0, dev))
-        return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first, deep=deep_cache))
+        if not auto:
+            return tokens(self._body(x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first, deep=deep_cache))
+        # ---- an auto call: the shallow part of the down path, the distance, the decision, then the rest of a key or of a shallow step
+        d = deep_cache.depth
+        down_ops = list(self._down_ops())
+        x = self._down(x, skips, down_ops[:d - 1], nb, f, trows, cross, pk, gf, sa, first)
+        key = self._deep_cache_decide(deep_cache, ops.rel_l1(*skips.skip_pair()).tolist())      # the call's one host synchronisation
+        skips.hand_over(key)
+        if key:
+            if share and d == 1:
+                first = shared_first()
+            x = self._down(x, skips, down_ops[d - 1:], nb, f, trows, cross, pk, gf, sa, first if d == 1 else None)
+        return tokens(self._tail(x, skips, nb, f, trows, cross, pk, gf, force_size, sa, deep=deep_cache))
+
+    @staticmethod
+    def _deep_cache_decide(deep, sums):
+        """The decision of an auto call (DeepCacheSlot states the rule) from `sums`, the (sum |new - kept|, sum |kept|) of every clip-half
+        queue as host floats, one pair after the other; it is recorded in the store, and `deep` -- the call's own slot object -- becomes a
+        fill or a reuse slot for the rest of the call.  True: a key step.  The caller then hands the buffers over (_Skips.hand_over), once
+        per queue."""
+        import math
+        num, den = math.fsum(sums[0::2]), math.fsum(sums[1::2])
+        r = num / den if den != 0 else (math.nan if math.isnan(num) else math.inf)
+        st = deep.store
+        st["acc"], st["run"] = st.get("acc", 0.0) + r, st.get("run", 0) + 1
+        key = bool(den == 0 or not math.isfinite(r) or st["acc"] >= deep.threshold or st["run"] >= deep.max_run)
+        if key:
+            st.update(written=set(), acc=0.0, run=0)
+        st.update(last="key" if key else "shallow", last_distance=r)
+        deep.mode = "fill" if key else "reuse"
+        return key
 
     def _deep_cache_begin(self, deep, x, nb, f, sig, queues):
         """The refusals of forward_nhwc(deep_cache=) and the start of a fill: a fill call empties the store and records its call signature; a
-        reuse call must find the fill call's signature and one kept buffer per clip-half queue that fits this call."""
+        reuse call must find the fill call's signature and one kept buffer per clip-half queue that fits this call.  An auto call on an empty
+        slot is a fill; on a filled one it is checked like a reuse call.  Returns the slot the call works with: the caller's, or for an auto
+        call one of its own (its mode changes when the call has decided; the store is shared)."""
         d = self.check_deep_cache_depth(deep.depth)
+        if deep.mode == "auto":
+            if deep.threshold is None or deep.max_run is None:
+                raise ValueError("deep_cache: an auto slot comes from DeepCacheSlot.auto(threshold, max_run)")
+            own = DeepCacheSlot(deep.depth, "auto" if deep.filled else "fill", deep.store, deep.threshold, deep.max_run)
+            if own.mode == "fill":
+                self._deep_cache_begin(own, x, nb, f, sig, queues)
+                deep.store.update(acc=0.0, run=0, last="key", last_distance=None)
+                return own
+            self._deep_cache_begin(DeepCacheSlot(deep.depth, "reuse", deep.store), x, nb, f, sig, queues)
+            return own
         if deep.mode == "fill":
             deep.store.clear()
             deep.store.update(sig=sig, bufs={}, written=set())
-            return
+            return deep
         if not deep.filled:
             raise ValueError(f"deep_cache: reuse with an empty slot (depth {d}): no fill call has kept a hidden state")
         if deep.store["sig"] != sig:
@@ -694,6 +813,7 @@ class UNet3DConditionModel(_UNetBase):
             if tuple(bufs[k].shape) != want or bufs[k].dtype != torch.float16 or bufs[k].device != x.device:
                 raise ValueError(f"deep_cache: the kept buffer {tuple(bufs[k].shape)} {bufs[k].dtype} on {bufs[k].device} does not fit this call, "
                                  f"which needs {want} torch.float16 on {x.device}")
+        return deep
 
     def _body(self, x, skips, nb, f, trows, cross, pk, gf, force_size, sa, first=None, out=None, deep=None):
         """Everything behind conv_in.  x: conv_in's output (nb*f, h, w, C0), already in its skip slot; `sa`: the call's blocks.SelfAttnCall;
@@ -701,12 +821,17 @@ class UNet3DConditionModel(_UNetBase):
         (nb*f, h, w, 4); `deep`: the call's DeepCacheSlot (the one `skips` was made with).  In mode "reuse" the down path stops behind its first
         depth - 1 operators, the mid block and the first len(_skip_plan()) - depth up layers do not run, and the up path starts from the hidden
         state in the kept buffer; otherwise everything runs, operator for operator as without the slot."""
+        reuse = deep is not None and deep.mode == "reuse"
+        down_ops = list(self._down_ops())
+        x = self._down(x, skips, down_ops[:deep.depth - 1] if reuse else down_ops, nb, f, trows, cross, pk, gf, sa, first)
+        return self._tail(x, skips, nb, f, trows, cross, pk, gf, force_size, sa, out, deep)
+
+    def _down(self, x, skips, down_ops, nb, f, trows, cross, pk, gf, sa, first=None):
+        """The skip-producing operators `down_ops` (entries of _down_ops(), a run of them in order) on x, every one writing its skip through
+        skips.slot(); `first` as in _body, for down_blocks.0 layer 0 where the run holds it.  Returns the last operator's output."""
         dev = x.device
         B = x.shape[0]
-        reuse = deep is not None and deep.mode == "reuse"
-        n_up = sum(len(blk.resnets) for blk in self.up_blocks)
-        down_ops = list(self._down_ops())
-        for bi, blk, j in down_ops[:deep.depth - 1] if reuse else down_ops:
+        for bi, blk, j in down_ops:
             if j is None:
                 x = blk.downsamplers[0](x, out=skips.slot(B, (x.shape[1] + 1) // 2, (x.shape[2] + 1) // 2, blk.downsamplers[0].c, dev))
                 continue
@@ -725,6 +850,13 @@ class UNet3DConditionModel(_UNetBase):
                 x = blk.attentions[j](x, cross, out=None if mm is not None else dst, sa=sa)
             if mm is not None:
                 x = mm(x, nb, f, out=dst)
+        return x
+
+    def _tail(self, x, skips, nb, f, trows, cross, pk, gf, force_size, sa, out=None, deep=None):
+        """Everything behind the down path: the mid block and the up path from x, the down path's output -- or, in mode "reuse", the last
+        `depth` up layers from the hidden state in the kept buffer -- then conv_norm_out and conv_out (`out`: as in _body)."""
+        reuse = deep is not None and deep.mode == "reuse"
+        n_up = sum(len(blk.resnets) for blk in self.up_blocks)
         if reuse:
             x = skips.kept_hidden()                                      # what the fill call's up path wrote in front of skip depth - 1
         else:
@@ -794,19 +926,76 @@ class UNet3DConditionModel(_UNetBase):
         qs = _side_streams(dev)
         plan = self._skip_plan()
         reuse = deep is not None and deep.mode == "reuse"
+        auto = deep is not None and deep.mode == "auto"
         sk = [_Skips(plan, deep, 0), _Skips(plan, deep, 1)]
         slot0 = sk[0].slot(f, hh, ww, c0, dev)
         ops.conv3x3(x[:f], pk["cin"], c0, bias=pk["cinb"], out=slot0)
         r = self.down_blocks[0].resnets[0]
-        first = None if reuse and deep.depth == 1 else r(slot0, self._temb(pk, trows[0:1], r), f * hh * ww, gf)
-        for tb in self.deep_cache_layers(deep.depth)[2] if reuse else self.transformer_blocks_in_order():
+        first = None if (reuse or auto) and deep.depth == 1 else r(slot0, self._temb(pk, trows[0:1], r), f * hh * ww, gf)
+        for tb in self.deep_cache_layers(deep.depth)[2] if reuse or auto else self.transformer_blocks_in_order():
             tb.context_kv(cross)                                          # (a reuse call: of the blocks it runs only)
         pred = torch.empty((2 * f, hh, ww, 4), device=dev, dtype=torch.float16)
         primed = pk.setdefault("_two_queue_shapes", set())
         serial = (f, hh, ww) not in primed or getattr(self, "serialize_queues", False)     # serialize_queues: bench.py's per-launch timing pass
         fork = torch.cuda.Event()
-        fork.record(main)
         done = []
+        if auto:
+            # An auto call has two phases with the decision between them.  Phase 1, on each queue: the first depth - 1 down operators and
+            # ops.rel_l1 into that queue's row of `dist` (allocated here, on the calling stream, before the fork, like `pred`).  The calling
+            # stream waits for both queues and reads the four floats: the call's one host synchronisation.  Phase 2, on each queue behind a
+            # second fork event: the hand-over (its copy runs on the stream that owns the kept buffer) and the rest of a key or of a shallow
+            # step.  A key step's first resnet at depth 1 and the context K / V of the blocks a shallow step skips are evaluated on the calling
+            # stream between the phases, where a fill call evaluates them before its fork.
+            d = deep.depth
+            down_ops = list(self._down_ops())
+            dist = torch.empty((2, 2), device=dev, dtype=torch.float32)
+            fork.record(main)
+            xs = [slot0, None]
+            for c in (0, 1):
+                with torch.cuda.stream(qs[c]):
+                    qs[c].wait_event(fork)
+                    if c == 1:
+                        if serial:
+                            qs[1].wait_event(done[0])
+                        xs[1] = sk[1].slot(f, hh, ww, c0, dev)
+                        xs[1].copy_(slot0)
+                    xs[c] = self._down(xs[c], sk[c], down_ops[:d - 1], 1, f, trows[c:c + 1], cross.rows(c * f, (c + 1) * f), pk, gf,
+                                       replace(sa, half=c), first)
+                    ops.rel_l1(*sk[c].skip_pair(), out=dist[c])
+                    ev = torch.cuda.Event()
+                    ev.record(qs[c])
+                    done.append(ev)
+            for ev in done:
+                main.wait_event(ev)
+            key = self._deep_cache_decide(deep, dist.flatten().tolist())
+            if key:
+                if d == 1:
+                    first = r(slot0, self._temb(pk, trows[0:1], r), f * hh * ww, gf)
+                for tb in self.transformer_blocks_in_order():
+                    tb.context_kv(cross)
+            fork = torch.cuda.Event()
+            fork.record(main)
+            done = []
+            for c in (0, 1):
+                with torch.cuda.stream(qs[c]):
+                    qs[c].wait_event(fork)
+                    if c == 1 and serial:
+                        qs[1].wait_event(done[0])
+                    sk[c].hand_over(key)
+                    if key:
+                        xs[c] = self._down(xs[c], sk[c], down_ops[d - 1:], 1, f, trows[c:c + 1], cross.rows(c * f, (c + 1) * f), pk, gf,
+                                           replace(sa, half=c), first if d == 1 else None)
+                    self._tail(xs[c], sk[c], 1, f, trows[c:c + 1], cross.rows(c * f, (c + 1) * f), pk, gf, force_size, replace(sa, half=c),
+                               out=pred[c * f:(c + 1) * f], deep=deep)
+                    ev = torch.cuda.Event()
+                    ev.record(qs[c])
+                    done.append(ev)
+            for ev in done:
+                main.wait_event(ev)
+            primed.add((f, hh, ww))
+            del first, slot0, xs, dist
+            return tokens(pred)
+        fork.record(main)
         for c in (0, 1):
             with torch.cuda.stream(qs[c]):
                 qs[c].wait_event(fork)
