@@ -97,6 +97,11 @@ EXTENSION_SIGNATURES = {
         "md_rel_l1_workspace_bytes": (c_size_t, [c_int, c_int]),
         "md_rel_l1_f16": (c_int, [P, c_int, P, c_int, c_int, c_int, P, c_size_t, P, P]),
     },
+    "color_match.h": {
+        "md_color_moments_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+        "md_color_moments": (c_int, [P, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, P, c_size_t, P, P]),
+        "md_color_apply": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_long, c_long, c_long, c_long, P]),
+    },
 }
 
 _lib = None

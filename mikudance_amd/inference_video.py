@@ -40,6 +40,9 @@ has (no omegaconf / diffusers / PyAV / cv2 / torchvision / scikit-image): see mi
                      the tail of the schedule at -W x -H; default 1 = off)
     pipe(..., vae_tiling=--vae_tiling, vae_tile_size=--vae_tile_size)
                      (an addition: tiled VAE encode / decode, diffusers' enable_vae_tiling; default off)
+    pipe(..., color_match=--color_match, color_match_strength=--color_match_strength, color_match_scope=--color_match_scope,
+         color_match_target=Image.open(--color_match_image) | "first_frame")
+                     (an addition: colour matching of the output frames on the GPU toward the reference image; default off)
     pipe(..., output_type="uint8") + save_frames_grid_u8 with --u8_output
                      (an addition: frames quantised on the GPU and kept as bytes up to the writer; the same file; default off)
     *.load_state_dict(torch.load(...))                                                             (:111-117)
@@ -225,7 +228,22 @@ def parse_args(argv=None):
     parser.add_argument("--u8_output", action="store_true",
                         help="(addition) take the frames from the pipeline as uint8 (output_type='uint8': quantised on the GPU, a quarter of the "
                              "bytes of the float32 clip on the host) and write the grid video from bytes; the file is byte-identical to the default's")
+    parser.add_argument("--color_match", choices=["mean_std", "mkl"], default=None,
+                        help="(addition) colour matching of the output frames on the GPU (ComfyUI's ColorMatch, A1111's 'apply color correction'): "
+                             "every frame gets an affine colour transfer toward the reference image (or --color_match_image) before it is "
+                             "quantised; mean_std matches each channel's mean and standard deviation, mkl the whole colour covariance "
+                             "(Monge-Kantorovich).  Image quality on real weights has not been assessed; default off")
+    parser.add_argument("--color_match_strength", type=float, default=1.0, metavar="A",
+                        help="(addition) with --color_match: blend between the frames as they are (0) and the full transfer (1)")
+    parser.add_argument("--color_match_scope", choices=["frame", "clip"], default="frame",
+                        help="(addition) with --color_match: one transform per frame, or one for the whole clip from the frames' summed "
+                             "statistics (removes the global drift, keeps the clip's own variation over time)")
+    parser.add_argument("--color_match_image", type=str, default=None, metavar="PATH",
+                        help="(addition) with --color_match: the target image, or 'first_frame' for the clip's own first frame (Deforum's "
+                             "colour coherence); default: the reference image")
     args = parser.parse_args(argv)
+    if args.color_match is None and (args.color_match_strength != 1.0 or args.color_match_scope != "frame" or args.color_match_image is not None):
+        parser.error("--color_match_strength / --color_match_scope / --color_match_image need --color_match")
     if args.vae_tile_size is not None and not args.vae_tiling:
         parser.error(f"--vae_tile_size {args.vae_tile_size} needs --vae_tiling")
     if args.vae_tiling and args.video_decoder:
@@ -334,6 +352,13 @@ def main(argv=None):
     else:
         pose_tensor = frames_to_tensor(pose_pils, height, width)
         ref_image_tensor = frames_to_tensor([ref_image_pil], height, width).repeat(1, 1, num_frames, 1, 1)
+    color_kw = {}
+    if args.color_match is not None:                                       # passed only when asked for: the default call keeps its keywords
+        target = args.color_match_image
+        if target is not None and target != "first_frame":
+            target = Image.open(target).convert("RGB")
+        color_kw = dict(color_match=args.color_match, color_match_strength=args.color_match_strength, color_match_scope=args.color_match_scope,
+                        color_match_target=target)
 
     out = pipe(ref_image_pil, ref_skel_pil, pose_pils, face_pils, hand_pils, scene_motion_npy, width, height, num_frames,
                args.steps, args.cfg, generator=generator, guidance_rescale=args.guidance_rescale,
@@ -350,7 +375,7 @@ def main(argv=None):
                deep_cache_threshold=args.deep_cache_threshold, guidance_interval=args.guidance_interval, uncond_cache_interval=args.uncond_cache_interval,
                hires_scale=args.hires_scale, hires_strength=args.hires_strength, hires_mode=args.hires_mode, hires_steps=args.hires_steps,
                scene_motion_lowres_npy=scene_motion_lowres_npy, vae_tiling=args.vae_tiling, vae_tile_size=args.vae_tile_size,
-               **(dict(output_type="uint8") if args.u8_output else {}))
+               **(dict(output_type="uint8") if args.u8_output else {}), **color_kw)
     video = torch.cat([ref_image_tensor, pose_tensor, out.videos], dim=0)
     path = f"{save_dir}/{skel_name}_{ref_name}_{args.H}x{args.W}_{int(args.cfg)}_{time_str}.mp4"
     (save_frames_grid_u8 if args.u8_output else save_videos_grid)(video, path, n_rows=3, fps=src_fps if args.fps is None else args.fps)

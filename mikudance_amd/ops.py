@@ -784,3 +784,75 @@ def rel_l1(a, b, out=None):
     _lib.call("md_rel_l1_f16", a.data_ptr(), lda, b.data_ptr(), ldb, rows, C, ws.data_ptr(), ws.numel() * 4, out.data_ptr(), _st(),
               meta=(f"rel_l1 rows={rows} C={C}", 2.0 * rows * C, 4.0 * rows * C))
     return out
+
+
+def _color_src(who, src):
+    """The refusals both colour-matching operators share with frames_u8, for 3 channels -> (B, H, W)."""
+    if not src.is_cuda or src.dtype not in (torch.float16, torch.float32):
+        raise _lib.MdanceHipError(f"{who}: src must be a CUDA fp16/fp32 tensor")
+    if src.dim() != 4 or src.shape[1] != 3 or min(src.shape) < 1:
+        raise _lib.MdanceHipError(f"{who}: src must be (B, 3, H, W)-shaped with no empty dimension, got {tuple(src.shape)}")
+    B, _, H, W = src.shape
+    if B * H * W >= 1 << 31:
+        raise _lib.MdanceHipError(f"{who}: B*H*W = {B * H * W} exceeds the entry point's int arguments")
+    return B, H, W
+
+
+def color_moments(src, out=None):
+    """The colour moments of decoded frames (md_color_moments): src (B, 3, H, W)-shaped fp16 / fp32 with ANY strides, as frames_u8 takes it ->
+    (B, 9) float64 on the device, per frame the sums over its pixels of s0, s1, s2, s0^2, s1^2, s2^2, s0 s1, s0 s2, s1 s2 with
+    s = clamp(0.5 v + 0.5, 0, 1) in fp32 (NaN kept): fp32 terms, fp32 sums per workgroup, fp64 across workgroups, all in a fixed order
+    (csrc/color_match.hip), so the same input gives the same bits.  Nothing is read back: the caller does.  `out`: a contiguous float64
+    (B, 9) destination.  The workspace (36 bytes per 8192 pixels) is kept per (device, stream)."""
+    B, H, W = _color_src("color_moments", src)
+    if out is None:
+        out = torch.empty((B, 9), device=src.device, dtype=torch.float64)
+    _chk(out, "out", torch.float64)
+    if tuple(out.shape) != (B, 9) or not out.is_contiguous() or out.device != src.device:
+        raise _lib.MdanceHipError(f"color_moments: out must be ({B}, 9) contiguous float64 on src's device, got {tuple(out.shape)}")
+    ws = _workspace("color_moments", src.device, _lib.load().md_color_moments_workspace_bytes(B, H, W), floor=1 << 16)
+    sB, sC, sY, sX = src.stride()
+    n = B * H * W * 3
+    _lib.call("md_color_moments", src.data_ptr(), int(src.dtype == torch.float32), B, H, W, sB, sC, sY, sX, ws.data_ptr(), ws.numel() * 4,
+              out.data_ptr(), _st(), meta=(f"color_moments B={B} {H}x{W}", 5.0 * n, float(src.element_size() * n + 72 * B)))
+    return out
+
+
+def color_apply(src, coef, out=None, *, dtype=torch.uint8):
+    """The affine colour map in front of the output quantisation (md_color_apply): src as color_moments takes it, coef (B, 12) contiguous
+    fp32 on the device, frame b's row-major 3 x 3 matrix M then its offset t -> y = clamp(M s + t, 0, 1), every operation rounded in fp32.
+    dtype torch.uint8: out (B, H, W, 3) bytes, fp32(y * 255) truncated, NaN -> 0, `out` as frames_u8 takes it (packed pixels, free row and
+    frame pitches); dtype torch.float32: out (B, 3, H, W) fp32 with any positive strides, y itself, NaN kept.  Returns out."""
+    B, H, W = _color_src("color_apply", src)
+    _chk(coef, "coef", torch.float32)
+    if tuple(coef.shape) != (B, 12) or not coef.is_contiguous() or coef.device != src.device:
+        raise _lib.MdanceHipError(f"color_apply: coef must be ({B}, 12) contiguous fp32 on src's device, got {tuple(coef.shape)}")
+    if dtype not in (torch.uint8, torch.float32):
+        raise _lib.MdanceHipError(f"color_apply: dtype must be torch.uint8 or torch.float32, got {dtype!r}")
+    sB, sC, sY, sX = src.stride()
+    n = B * H * W * 3
+    if dtype == torch.uint8:
+        if out is None:
+            out = torch.empty((B, H, W, 3), device=src.device, dtype=torch.uint8)
+        if not out.is_cuda or out.dtype != torch.uint8 or out.device != src.device:
+            raise _lib.MdanceHipError("color_apply: out must be a CUDA uint8 tensor on src's device")
+        if tuple(out.shape) != (B, H, W, 3) or out.stride(3) != 1 or out.stride(2) != 3:
+            raise _lib.MdanceHipError(f"color_apply: out must be a (B, H, W, 3) = ({B}, {H}, {W}, 3) view with packed pixels (strides (*, *, 3, 1)), got "
+                                      f"shape {tuple(out.shape)} strides {tuple(out.stride())}")
+        dY = out.stride(1) if H > 1 else max(out.stride(1), W * 3)          # the stride of a dimension of size 1 says nothing
+        dB = out.stride(0) if B > 1 else max(out.stride(0), (H - 1) * dY + W * 3)
+        dst = (dB, 1, dY, 3)
+    else:
+        if out is None:
+            out = torch.empty((B, 3, H, W), device=src.device, dtype=torch.float32)
+        if not out.is_cuda or out.dtype != torch.float32 or out.device != src.device:
+            raise _lib.MdanceHipError("color_apply: out must be a CUDA float32 tensor on src's device")
+        if tuple(out.shape) != (B, 3, H, W):
+            raise _lib.MdanceHipError(f"color_apply: out must be (B, 3, H, W) = ({B}, 3, {H}, {W}), got {tuple(out.shape)}")
+        dst = tuple(max(s, 1) if d == 1 else s for s, d in zip(out.stride(), out.shape))     # (dB, dC, dY, dX)
+        if min(dst) < 1:
+            raise _lib.MdanceHipError(f"color_apply: out must not be an expanded view, got strides {tuple(out.stride())}")
+    _lib.call("md_color_apply", src.data_ptr(), int(src.dtype == torch.float32), coef.data_ptr(), out.data_ptr(), int(dtype == torch.float32), B, H, W,
+              sB, sC, sY, sX, *dst, _st(),
+              meta=(f"color_apply B={B} {H}x{W} {'f32' if dtype == torch.float32 else 'u8'}", 7.0 * n, float((src.element_size() + out.element_size()) * n + 48 * B)))
+    return out

@@ -958,6 +958,98 @@ class MikuDanceVideoPipeline:
                 self.vae.decode_u8(chunk, out=video[i:i + chunk.shape[0]], **kw)
         return video.reshape((-1, video_length) + tuple(video.shape[1:])).cpu()
 
+    def color_match_plan(self, color_match, color_match_strength, color_match_target, color_match_scope, ref_image, height, width, clips):
+        """__call__'s color_match keywords, checked before anything runs -> None (off) or the plan _decode_color_matched takes:
+        dict(mode, strength, scope, targets), targets one entry per clip, "first_frame" or the (sums, n) of a target image
+        (color_match.moments_of_image of the image resized to height x width like the reference image).  ValueError for a bad value, for a
+        keyword given without color_match, for a VAE without decode_image_view and for one whose images do not have 3 channels."""
+        from . import color_match as CM
+        if color_match is None:
+            if color_match_strength != 1.0 or color_match_target is not None or color_match_scope != "frame":
+                raise ValueError("color_match_strength / color_match_target / color_match_scope need color_match='mean_std' or 'mkl'")
+            return None
+        if color_match not in CM.MODES:
+            raise ValueError(f"color_match must be None or one of {CM.MODES}, got {color_match!r}")
+        a = color_match_strength
+        if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a) or not 0.0 <= a <= 1.0:
+            raise ValueError(f"color_match_strength must be a finite number in [0, 1], got {a!r}")
+        if color_match_scope not in CM.SCOPES:
+            raise ValueError(f"color_match_scope must be one of {CM.SCOPES}, got {color_match_scope!r}")
+        targets = list(color_match_target) if isinstance(color_match_target, (list, tuple)) else [color_match_target] * clips
+        if len(targets) != clips:
+            raise ValueError(f"color_match_target lists {len(targets)} targets for {clips} clips: one per clip")
+        is_image = lambda t: hasattr(t, "convert") and hasattr(t, "resize")
+        if not all(t is None or (t == "first_frame" if isinstance(t, str) else is_image(t)) for t in targets):
+            raise ValueError(f"color_match_target must be None (the reference image), a PIL image or 'first_frame' (or a list of them, one per clip), "
+                             f"got {color_match_target!r}")
+        if not hasattr(self.vae, "decode_image_view"):
+            raise ValueError(f"color_match: {type(self.vae).__name__} has no decode_image_view")
+        channels = getattr(getattr(self.vae, "config", None), "out_channels", 3)
+        if channels != 3:
+            raise ValueError(f"color_match: the VAE decodes images of {channels} channels, colour matching needs 3")
+        known = {}
+
+        def sums_of(img):
+            if id(img) not in known:
+                known[id(img)] = CM.moments_of_image(_pil_to_tensor(img, height, width, normalize=False)[0].permute(1, 2, 0).numpy())
+            return known[id(img)]
+        return dict(mode=color_match, strength=float(a), scope=color_match_scope,
+                    targets=[t if t == "first_frame" else sums_of(ref_image if t is None else t) for t in targets])
+
+    def _decode_color_matched(self, latents, batch, plan, temporal=False, as_bytes=False):
+        """decode_latents / decode_temporal / _decode_u8 with colour matching (plan: color_match_plan's): the same scaling, frame order and VAE
+        batches; per batch the VAE's decode_image_view (the image where the decoder left it), ops.color_moments, ONE host read of B x 9
+        doubles, color_match.transform per frame, ops.color_apply straight into the output buffer -- bytes (as_bytes: the CPU uint8
+        (b, f, H, W, 3) tensor of _decode_u8) or fp32 (the float32 (b, c, f, H, W) numpy array of decode_latents).  scope "clip": the decoded
+        views of every batch stay on the device until the last batch's sums are in, the frames' sums of a clip are added into ONE transform,
+        then every batch is applied.  Target "first_frame": the sums of the clip's own frame 0.  self.last_color_match: (M', t', fallback)
+        per frame, in frame order, float64."""
+        from . import color_match as CM
+        video_length = latents.shape[2]
+        latents = 1 / 0.18215 * latents
+        latents = latents.permute(0, 2, 1, 3, 4).reshape((-1,) + tuple(latents.shape[1:2]) + tuple(latents.shape[3:]))
+        total = latents.shape[0]
+        mode, strength, per_clip, targets = plan["mode"], plan["strength"], plan["scope"] == "clip", plan["targets"]
+        video, held, sums, pixels = None, [], np.empty((total, 9), dtype=np.float64), 0
+
+        def target_of(clip):
+            t = targets[clip]
+            return (sums[clip * video_length], pixels) if t == "first_frame" else t
+
+        def apply(i, view, maps):
+            coef = torch.from_numpy(CM.coefficients(maps)).to(view.device)
+            if as_bytes:
+                ops.color_apply(view, coef, out=video[i:i + view.shape[0]], dtype=torch.uint8)
+            else:
+                ops.color_apply(view, coef, out=video[i:i + view.shape[0]], dtype=torch.float32)
+
+        maps = []
+        for i in range(0, total, batch):
+            chunk = latents[i:i + batch].to(self.vae.dtype)
+            view = self.vae.decode_image_view(chunk, **(dict(num_frames=chunk.shape[0]) if temporal else {}))
+            n, _, H, W = view.shape
+            if video is None:                                              # the first batch tells the frame size (the VAE's factor is its own)
+                pixels = H * W
+                video = torch.empty((total, H, W, 3) if as_bytes else (total, 3, H, W), device=view.device, dtype=torch.uint8 if as_bytes else torch.float32)
+            sums[i:i + n] = ops.color_moments(view).cpu().numpy()          # the one host read of this batch
+            if per_clip:
+                held.append((i, view))
+                continue
+            batch_maps = [CM.transform(sums[j], pixels, *target_of(j // video_length), mode, strength) for j in range(i, i + n)]
+            apply(i, view, batch_maps)
+            maps += batch_maps
+        if per_clip:
+            clip_maps = [CM.transform(sums[c * video_length:(c + 1) * video_length].sum(0), pixels * video_length, *target_of(c), mode, strength)
+                         for c in range(total // video_length)]
+            maps = [clip_maps[j // video_length] for j in range(total)]
+            for i, view in held:
+                apply(i, view, maps[i:i + view.shape[0]])
+            del held[:]
+        self.last_color_match = maps
+        if as_bytes:
+            return video.reshape((-1, video_length) + tuple(video.shape[1:])).cpu()
+        return video.reshape((-1, video_length) + tuple(video.shape[1:])).permute(0, 2, 1, 3, 4).cpu().numpy()
+
     def decode_latents(self, latents, output_type=None):
         """reference :115-130 -- per-frame VAE decode, (x/2+0.5).clamp(0,1), float32 numpy (b,c,f,h,w).  output_type "uint8": a CPU torch.uint8
         (b, f, H, W, 3) tensor instead (_decode_u8); None: the reference's array."""
@@ -1122,7 +1214,8 @@ class MikuDanceVideoPipeline:
                  kv_downsample_mode="nearest", seg_scale: float = 0.0, seg_blur_sigma: float = 100.0, seg_applied_layers=("mid",), tile_attention=1,
                  tile_attention_shift="cycle", deep_cache_interval=1, deep_cache_depth=3, guidance_interval=(0.0, 1.0), uncond_cache_interval=1,
                  hires_scale=1, hires_strength=0.5, hires_mode="bicubic", hires_steps=None, scene_motion_lowres_npy=None, vae_tiling=False,
-                 vae_tile_size=None, deep_cache_threshold=None, **kwargs):
+                 vae_tile_size=None, deep_cache_threshold=None, color_match=None, color_match_strength=1.0, color_match_target=None,
+                 color_match_scope="frame", **kwargs):
         """The reference call (src/pipelines/pipeline_mikudance.py:362-704) with denoise()'s sampling keywords (see its docstring), and:
 
         output_type         "tensor" (the default): `videos` is the reference's float32 (b, c, f, H, W) CPU tensor in [0, 1]; "uint8": a CPU
@@ -1138,6 +1231,26 @@ class MikuDanceVideoPipeline:
                             afterwards.  False (the default): the VAE is left as it is, and the call is bitwise what it was.  ValueError,
                             before the CLIP tower or the VAE runs, for a tile grid the VAE cannot run at this call's sizes (both of them under
                             hires_scale) and for a VAE without tiling (video_decoder)
+        color_match         "mean_std" or "mkl": every decoded frame gets an affine colour transfer y = M s + t toward a target image before it is
+                            quantised, the stock post-process of the SD-1.5 front ends (A1111 "apply color correction", Deforum "color
+                            coherence", ComfyUI ColorMatch) against the colour drift of windows, hires pass 2, video-to-video and the opt-in
+                            approximations.  On the device: per VAE batch the decoder's image is read where it lies (decode_image_view) by
+                            ops.color_moments (nine sums per frame, deterministic), ONE host read of B x 9 doubles, a 3 x 3 solve in float64
+                            (color_match.transform: "mean_std" scales every channel to the target's mean and standard deviation, "mkl" is the
+                            Monge-Kantorovich linear map of Pitie & Kokaram 2007, which matches the whole covariance), and ops.color_apply
+                            writes the result: bytes for output_type "uint8" / "pil" (bit for bit the "tensor" result * 255 cast), the
+                            float32 tensor otherwise.  A frame that is flat in a channel (variance < color_match.COLOR_MATCH_EPS) or holds
+                            a NaN gets the mean shift alone.  pipe.last_color_match lists (M', t', fallback) per frame.  Composes with
+                            interpolation_factor, vae_tiling, hires_scale and both decoders.  Image quality on real weights has not been
+                            assessed.  None (the default): bitwise the call without the keywords, the same operator calls, nothing allocated.
+                            ValueError, before the CLIP tower or the VAE runs, for a bad value of any of the four keywords, for one of the
+                            other three without color_match, and for a VAE without decode_image_view or with other than 3 image channels
+        color_match_strength  a finite number in [0, 1]: M' = (1 - a) I + a M, t' = a t; 0 leaves the frames as they are
+        color_match_target  None: ref_image, resized to width x height like the reference image itself (LANCZOS); a PIL image: that image, the
+                            same way; "first_frame": the clip's own decoded frame 0 (Deforum's colour coherence); a list: one of these per clip
+        color_match_scope   "frame": one transform per frame; "clip": the sums of a clip's frames are added into ONE transform for the clip,
+                            which removes the global drift and keeps the clip's own variation over time (the decoded images of every VAE
+                            batch then stay on the device until the last batch's sums are in)
         vae_tile_size       the tile side in image pixels, a positive multiple of 32 (sets tile_sample_min_size and tile_latent_min_size
                             together); None: the VAE's own (config.sample_size).  Needs tiling on
 
@@ -1206,6 +1319,8 @@ class MikuDanceVideoPipeline:
             if scene_motion_lowres_npy is not None and tuple(np.shape(scene_motion_lowres_npy)) != (video_length, 2, height_lo // 8, width_lo // 8):
                 raise ValueError(f"scene_motion_lowres_npy has shape {tuple(np.shape(scene_motion_lowres_npy))}, pass 1 needs "
                                  f"{(video_length, 2, height_lo // 8, width_lo // 8)}")
+        color_plan = self.color_match_plan(color_match, color_match_strength, color_match_target, color_match_scope, ref_image, height or 768,
+                                           width or 768, num_images_per_prompt)
         if context_batch_size > 1 and not getattr(self, "_warned_context_batch", False):
             import warnings
             warnings.warn("context_batch_size > 1: the windows of a context batch are evaluated one at a time (the reference itself "
@@ -1249,7 +1364,14 @@ class MikuDanceVideoPipeline:
                                        callback_steps, eta=eta, generator=generator, init_latents=latents, **hi_kw)
             if interpolation_factor > 0:
                 latents = self.interpolate_latents(latents, interpolation_factor, device)
-            if output_type in ("uint8", "pil"):
+            if color_plan is not None:
+                # colour matched on the device between the decode and the quantisation (md_color_moments / md_color_apply)
+                images = self._decode_color_matched(latents, self.decode_chunk_size if self.video_decoder else self.vae_batch, color_plan,
+                                                    temporal=bool(self.video_decoder), as_bytes=output_type in ("uint8", "pil"))
+                if output_type == "pil":
+                    from PIL import Image
+                    images = [[Image.fromarray(frame.numpy()) for frame in clip] for clip in images]
+            elif output_type in ("uint8", "pil"):
                 # frames quantised on the device (md_frames_u8), in the layout the writers take: half the bytes of the fp16 transfer, a quarter of the fp32 host array's
                 images = self.decode_temporal(latents, output_type="uint8") if self.video_decoder else self.decode_latents(latents, output_type="uint8")
                 if output_type == "pil":

@@ -346,6 +346,19 @@ class AutoencoderKL(_Packed):
             return ops.frames_u8(self.decode(z).sample, out, f32_math=f32)
         return ops.frames_u8(self._image_nhwc(z).permute(0, 3, 1, 2), out, f32_math=f32)
 
+    @torch.no_grad()
+    def decode_image_view(self, z):
+        """decode(z)'s image where the decoder left it, as the strided (B, out_channels, 8h, 8w) view decode_u8 hands to ops.frames_u8: the
+        decoder's own NHWC buffer, permuted (fp16, no NCHW tensor, no elementwise pass), or decode's NCHW result with tiling or slicing on.
+        The values are decode(z).sample's.  For the operators that read an image once at the output boundary (ops.color_moments /
+        ops.color_apply)."""
+        if z.dim() != 4 or z.shape[1] != self.zc:
+            raise ValueError(f"AutoencoderKL.decode_image_view expects (B, {self.zc}, h, w), got {tuple(z.shape)}")
+        tiled = self.use_tiling and max(z.shape[2:]) > self.tile_latent_min_size
+        if tiled or (self.use_slicing and z.shape[0] > 1):
+            return self.decode(z).sample
+        return self._image_nhwc(z).permute(0, 3, 1, 2)
+
     # ---- tiling and slicing (diffusers 0.24: enable_tiling / enable_slicing, tiled_encode / tiled_decode)
     def enable_tiling(self, use_tiling=True):
         """encode / decode of an input with a side above tile_sample_min_size pixels / tile_latent_min_size latents run tile by tile."""

@@ -264,6 +264,14 @@ class AutoencoderKLTemporalDecoder(_Packed):
         y = self._image_nhwc(z, num_frames)                                              # (B, 8h, 8w, 8): 3 valid channels
         return ops.frames_u8(y[..., :self.decoder.out_channels].permute(0, 3, 1, 2), out, f32_math=z.dtype in (torch.float32, torch.float64))
 
+    @torch.no_grad()
+    def decode_image_view(self, z, num_frames=1):
+        """decode(z, num_frames)'s image where the decoder left it: the NHWC result (pixel pitch 8) as the strided (B, out_channels, H, W)
+        view decode_u8 hands to ops.frames_u8 -- no NCHW tensor.  The values are decode(...).sample's."""
+        if z.dim() != 4 or z.shape[1] != self.zc or z.shape[0] % num_frames:
+            raise ValueError(f"decode_image_view expects (clips * num_frames, {self.zc}, h, w), got {tuple(z.shape)} with num_frames={num_frames}")
+        return self._image_nhwc(z, num_frames)[..., :self.decoder.out_channels].permute(0, 3, 1, 2)
+
     @classmethod
     def from_pretrained(cls, pretrained_model_path, subfolder=None, **kw):
         path = os.path.join(pretrained_model_path, subfolder) if subfolder else str(pretrained_model_path)
