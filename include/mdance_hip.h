@@ -476,8 +476,8 @@ int md_tile_blend_f16(void* cur, int ldc, const void* above, int Ah, const void*
  *   f32_math = 1 (an fp32 VAE boundary):  the same steps with every intermediate in fp32; an fp16 source converts exactly
  * src_is_f32 = 1 requires f32_math = 1.  +Inf gives 255 and -Inf gives 0.  NaN gives 0: the float path's cast of a NaN to uint8 is undefined
  * (C and numpy), so this value is a choice of this entry point.
- * One thread per 4 pixels of a row; 8- / 16-byte loads where those are contiguous and aligned in src (sX = 1, or sC = 1 with sX = C), strided
- * loads otherwise; 4-byte stores where the thread's 4 C bytes start on a 4-byte boundary, byte stores otherwise.  256 threads, at most 2048
+ * One thread per 4 pixels of a row; the loads and the byte writer are csrc/frame_io.h's, stated there (vector loads where a whole unit is
+ * contiguous and aligned in src, nothing outside the view's span read; 4-byte stores where the 4 C bytes are aligned).  256 threads, at most 2048
  * blocks, a grid-stride loop past that; no atomics: two calls give the same bits.  Nothing outside the B H rows of W C bytes of dst is
  * written; the strides of src are the caller's word.
  * src and dst not NULL; C in 1..4; B, H, W positive and B*H*W within int; src_is_f32 and f32_math 0 or 1; dY >= W C; dB >= (H - 1) dY + W C;

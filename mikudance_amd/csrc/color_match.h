@@ -28,9 +28,8 @@ extern "C" {
  * term (s_i, s_j, their product) and every term >= 0, a sum is within (d + 3) 2^-24 of the exact one, relatively, to first order.  The second launch: one workgroup
  * per frame, thread t adds partials t, t + 256, ... in ascending order, then the same butterfly and the same 4-wave sum, all in fp64.
  * Deterministic: the grid (B P workgroups) depends on the shape alone, no atomics, every workspace word that is read has been written by the
- * same call, two calls give the same bits.  A NaN in the source reaches every sum it is a term of.  16-byte loads where a unit's 8 pixels
- * are contiguous in the source (pitch 3, 4, 8 with sC = 1: all of them; sX = 1: 8 elements per channel) and start on a 16-byte boundary,
- * element loads otherwise (a row's tail, odd offsets, other strides).
+ * same call, two calls give the same bits.  A NaN in the source reaches every sum it is a term of.  Loads: csrc/frame_io.h's rule
+ * with 16-byte vectors.
  * B, H, W positive with B H W <= INT_MAX; src aligned to its element, workspace to 4 and out to 8 bytes; workspace_bytes >=
  * md_color_moments_workspace_bytes(B, H, W) = 36 B P (0 for a shape that is refused); MD_ERR_ARG otherwise, with nothing launched. */
 size_t md_color_moments_workspace_bytes(int B, int H, int W);
@@ -43,8 +42,7 @@ int md_color_moments(const void* src, int src_is_f32, int B, int H, int W, long 
  * dst_is_f32 = 0: dst is bytes, (b, y, x, c) at b dB + y dY + 3 x + c with dC = 1 and dX = 3 -- md_frames_u8's destination, its rules for
  *     dB and dY, no alignment asked; the byte is fp32(y * 255) truncated toward zero, 0 for a NaN (md_frames_u8's choice)
  * dst_is_f32 = 1: dst is fp32, 4-byte aligned, (b, c, y, x) at b dB + c dC + y dY + x dX (elements, all four positive): y itself
- * One thread per 4 consecutive pixels of a row; md_frames_u8's load widths, 4-byte stores where the 12 bytes start on a 4-byte boundary (byte
- * stores otherwise), 16-byte stores per channel where dX = 1 and the 4 floats start on a 16-byte boundary (element stores otherwise); 256
+ * One thread per 4 consecutive pixels of a row; md_frames_u8's loads and byte writer (csrc/frame_io.h), 16-byte stores per channel where dX = 1 and the 4 floats start on a 16-byte boundary (element stores otherwise); 256
  * threads, at most 2048 workgroups, a grid-stride loop past that.  No atomics, no LDS.  Nothing outside the B H rows of the destination is
  * written.  B, H, W positive with B H W <= INT_MAX; MD_ERR_ARG otherwise, with nothing launched. */
 int md_color_apply(const void* src, int src_is_f32, const void* coef, void* dst, int dst_is_f32, int B, int H, int W, long sB, long sC, long sY,

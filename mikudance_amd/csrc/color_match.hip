@@ -5,15 +5,9 @@
 //   md_color_moments   frames -> B x 9 fp64 colour moments (sums of s_c and of s_c s_c' over a frame's pixels), deterministic
 //   md_color_apply     frames, B x 12 fp32 coefficients -> clamp(M s + t), as the writers' bytes or as fp32
 //
-//   src   md_frames_u8's: fp16 or fp32 (src_is_f32), element (b, c, y, x) at b sB + c sC + y sY + x sX in elements, 3 channels
-//   s     the displayed colour, fp32:  s = min(max(0.5 v + 0.5, 0), 1), the product and the sum rounded separately, NaN kept (the comparisons are false for it)
-//
-// Loads (cm_load): `packed` = channels last (sC = 1) at pixel pitch 3, 4 or 8, the NPIX pixels of a unit are NPIX pitch contiguous elements,
-// read as whole vectors of VE elements -- the padding channels of pitch 4 / 8 come along and are dropped --; `planar` = sX = 1, NPIX
-// contiguous elements per channel.  Either needs the unit complete (no row tail) and its first element on a vector boundary; everything
-// else takes element loads.  At pitch 4 / 8 the unit that holds its row's last pixel takes element loads too: the padding read always lies below
-// a later pixel of the same row, so nothing outside the view's own span is ever read (the last pixel's padding need not exist).
-// md_color_moments: NPIX = 8, VE = 16 bytes; md_color_apply: NPIX = 4, VE = 4 elements, md_frames_u8's widths.
+//   src   frame_io.h's source with 3 channels, read by its load rule: md_color_moments in units of NPIX = 8 pixels with 16-byte vectors,
+//         md_color_apply in md_frames_u8's units (NPIX = 4, vectors of 4 elements)
+//   s     frame_io.h's display colour (fio_display); md_color_apply's bytes are its byte and its byte writer
 //
 // THE SUMMATION ORDER of md_color_moments (tests/color_match_ref.py restates the depth, tests/test_color_match_gpu.py takes its bound from it).
 // A unit is 8 consecutive pixels of a row; a frame has U = H ceil(W / 8) units and P = ceil(U / 1024) workgroups of 256 threads, workgroup
@@ -33,80 +27,15 @@
 //
 // Both kernels are HBM-bound streams (2 or 4 bytes read per element once; 1 or 4 written by apply).  Lanes run along a row, so a wave
 // reads one run of its row; the moments kernel's unit loop is unrolled so that a thread has several units' loads in flight.
-#include "common.h"
+#include "frame_io.h"
 #include "color_match.h"
-#include <limits.h>
 
-#define CM_THREADS 256
+#define CM_THREADS FIO_THREADS
 #define CM_UNITS_PER_BLOCK 1024                                      // 4 units of 8 pixels per thread
-#define CM_MAX_BLOCKS 2048                                           // md_color_apply's grid cap, md_frames_u8's
-
-#pragma clang fp contract(off)
-
-struct cm_src_t {
-  const void* src;
-  int B, H, W;
-  long sB, sC, sY, sX;
-};
-
-template <typename T, int NPIX, int VE, int PITCH>
-__device__ __forceinline__ void cm_load_packed(const T* ps, float (&v)[NPIX][3]) {
-  typedef T vec_t __attribute__((ext_vector_type(VE)));
-#pragma unroll
-  for (int k = 0; k < NPIX * PITCH / VE; ++k) {
-    if (PITCH == 8 && VE == 4 && (k & 1)) continue;                 // elements 4 .. 7 of a pixel: padding only
-    const vec_t in = *reinterpret_cast<const vec_t*>(ps + VE * k);
-#pragma unroll
-    for (int j = 0; j < VE; ++j)
-      if ((VE * k + j) % PITCH < 3) v[(VE * k + j) / PITCH][(VE * k + j) % PITCH] = (float)in[j];
-  }
-}
-
-// The np <= NPIX pixels that start at ps -> v[pixel][channel]; pixels np .. NPIX - 1 are left as they are.  `inner`: a pixel of the row follows the unit.
-template <typename T, int NPIX, int VE>
-__device__ __forceinline__ void cm_load(const T* ps, long sC, long sX, int np, bool inner, float (&v)[NPIX][3]) {
-  typedef T vec_t __attribute__((ext_vector_type(VE)));
-  const bool whole = np == NPIX;
-  if (whole && sC == 1 && (sX == 3 || ((sX == 4 || sX == 8) && inner)) && ((uintptr_t)ps % (VE * sizeof(T))) == 0) {
-    if (sX == 3)
-      cm_load_packed<T, NPIX, VE, 3>(ps, v);
-    else if (sX == 4)
-      cm_load_packed<T, NPIX, VE, 4>(ps, v);
-    else
-      cm_load_packed<T, NPIX, VE, 8>(ps, v);
-    return;
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const T* pc = ps + (long)c * sC;
-    if (whole && sX == 1 && ((uintptr_t)pc % (VE * sizeof(T))) == 0) {
-#pragma unroll
-      for (int k = 0; k < NPIX / VE; ++k) {
-        const vec_t in = *reinterpret_cast<const vec_t*>(pc + VE * k);
-#pragma unroll
-        for (int j = 0; j < VE; ++j) v[VE * k + j][c] = (float)in[j];
-      }
-    } else {
-#pragma unroll
-      for (int p = 0; p < NPIX; ++p)
-        if (p < np) v[p][c] = (float)pc[(long)p * sX];
-    }
-  }
-}
-
-// One rounding each, never fused: plain operators compiled under the contract(off) above.  (The toolkit's __fmul_rn / __fadd_rn are plain
-// operators too, but compiled under the header's own contraction mode: after inlining, a product and the sum that takes it become one fma.)
-__device__ __forceinline__ float cm_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float cm_add(float a, float b) { return a + b; }
-
-__device__ __forceinline__ float cm_display(float v) {
-  const float s = cm_add(cm_mul(0.5f, v), 0.5f);
-  return s < 0.f ? 0.f : (s > 1.f ? 1.f : s);                        // a NaN fails both comparisons and stays
-}
 
 // ---------------------------------------------------------------------------------------------------------------- md_color_moments
 template <typename T>
-__global__ void __launch_bounds__(CM_THREADS) color_moments_partial_kernel(cm_src_t a, int G, long U, int P, float* __restrict__ partial) {
+__global__ void __launch_bounds__(CM_THREADS) color_moments_partial_kernel(fio_src_t a, int G, long U, int P, float* __restrict__ partial) {
   constexpr int VE = 16 / sizeof(T);
   __shared__ float waves[CM_THREADS / 64][9];
   const int b = blockIdx.x / P, j = blockIdx.x - b * P;              // b < B: the grid is B P
@@ -116,33 +45,28 @@ __global__ void __launch_bounds__(CM_THREADS) color_moments_partial_kernel(cm_sr
 #pragma unroll 2
   for (long i = (long)j * CM_THREADS + threadIdx.x; i < U; i += (long)P * CM_THREADS) {
     const int y = (int)(i / G), xg = (int)(i - (long)y * G);         // y < H: i < U = H G
-    const int x0 = xg * 8, np = a.W - x0 < 8 ? a.W - x0 : 8;         // 1 <= np: xg < G = ceil(W / 8)
-    const T* ps = (const T*)a.src + (long)b * a.sB + (long)y * a.sY + (long)x0 * a.sX;
-    float v[8][3];
-#pragma unroll
-    for (int p = 0; p < 8; ++p)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[p][c] = 0.f;
-    cm_load<T, 8, VE>(ps, a.sC, a.sX, np, x0 + 8 < a.W, v);
+    const fio_unit_t un = fio_unit_at<8>(b, y, xg, a.W);             // 1 <= np: xg < G = ceil(W / 8)
+    FIO_PIXELS(v, 8, 3);
+    fio_load<T, 3, 8, VE>(fio_src_at<T>(a, un), a.sC, a.sX, un.np, un.inner, v);
     float u[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) u[k] = 0.f;
 #pragma unroll
     for (int p = 0; p < 8; ++p)
-      if (p < np) {
-        const float s0 = cm_display(v[p][0]), s1 = cm_display(v[p][1]), s2 = cm_display(v[p][2]);
-        u[0] = cm_add(u[0], s0);
-        u[1] = cm_add(u[1], s1);
-        u[2] = cm_add(u[2], s2);
-        u[3] = cm_add(u[3], cm_mul(s0, s0));
-        u[4] = cm_add(u[4], cm_mul(s1, s1));
-        u[5] = cm_add(u[5], cm_mul(s2, s2));
-        u[6] = cm_add(u[6], cm_mul(s0, s1));
-        u[7] = cm_add(u[7], cm_mul(s0, s2));
-        u[8] = cm_add(u[8], cm_mul(s1, s2));
+      if (p < un.np) {
+        const float s0 = fio_display(v[p][0]), s1 = fio_display(v[p][1]), s2 = fio_display(v[p][2]);
+        u[0] = fio_add(u[0], s0);
+        u[1] = fio_add(u[1], s1);
+        u[2] = fio_add(u[2], s2);
+        u[3] = fio_add(u[3], fio_mul(s0, s0));
+        u[4] = fio_add(u[4], fio_mul(s1, s1));
+        u[5] = fio_add(u[5], fio_mul(s2, s2));
+        u[6] = fio_add(u[6], fio_mul(s0, s1));
+        u[7] = fio_add(u[7], fio_mul(s0, s2));
+        u[8] = fio_add(u[8], fio_mul(s1, s2));
       }
 #pragma unroll
-    for (int k = 0; k < 9; ++k) acc[k] = cm_add(acc[k], u[k]);
+    for (int k = 0; k < 9; ++k) acc[k] = fio_add(acc[k], u[k]);
   }
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
@@ -153,7 +77,7 @@ __global__ void __launch_bounds__(CM_THREADS) color_moments_partial_kernel(cm_sr
   if (threadIdx.x < 9) {
     float r = waves[0][threadIdx.x];
 #pragma unroll
-    for (int w = 1; w < CM_THREADS / 64; ++w) r = cm_add(r, waves[w][threadIdx.x]);
+    for (int w = 1; w < CM_THREADS / 64; ++w) r = fio_add(r, waves[w][threadIdx.x]);
     partial[(long)blockIdx.x * 9 + threadIdx.x] = r;                 // < 9 B P floats: the workspace's count
   }
 }
@@ -187,31 +111,26 @@ __global__ void __launch_bounds__(CM_THREADS) color_moments_final_kernel(const f
   }
 }
 
-static inline bool cm_shape_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0 && (long)B * H <= INT_MAX / W; }
-
 static inline long cm_blocks_per_frame(int H, int W) {
   const long U = (long)H * ((W + 7) / 8);
   return (U + CM_UNITS_PER_BLOCK - 1) / CM_UNITS_PER_BLOCK;
 }
 
 extern "C" size_t md_color_moments_workspace_bytes(int B, int H, int W) {
-  if (!cm_shape_ok(B, H, W)) return 0;
+  if (!fio_shape_ok(B, H, W)) return 0;
   return (size_t)B * (size_t)cm_blocks_per_frame(H, W) * 9 * sizeof(float);
 }
 
 extern "C" int md_color_moments(const void* src, int src_is_f32, int B, int H, int W, long sB, long sC, long sY, long sX, void* workspace,
                                 size_t workspace_bytes, void* out, void* stream) {
   MD_CHECK_ARG(src && workspace && out, "md_color_moments: NULL pointer");
-  MD_CHECK_ARG(B > 0 && H > 0 && W > 0, "md_color_moments: B, H, W must be positive (%d, %d, %d)", B, H, W);
-  MD_CHECK_ARG(cm_shape_ok(B, H, W), "md_color_moments: B*H*W must fit an int (B=%d, %d x %d)", B, H, W);
-  MD_CHECK_ARG(src_is_f32 == 0 || src_is_f32 == 1, "md_color_moments: src_is_f32 must be 0 or 1, got %d", src_is_f32);
-  MD_CHECK_ARG(((uintptr_t)src % (src_is_f32 ? 4 : 2)) == 0, "md_color_moments: src must be aligned to its element (%d bytes)", src_is_f32 ? 4 : 2);
+  if (int e = fio_check_src("md_color_moments", src, src_is_f32, B, H, W)) return e;
   MD_CHECK_ARG(((uintptr_t)workspace % 4) == 0 && ((uintptr_t)out % 8) == 0, "md_color_moments: workspace needs 4-byte, out 8-byte alignment");
   MD_CHECK_ARG(workspace_bytes >= md_color_moments_workspace_bytes(B, H, W), "md_color_moments: workspace of %zu bytes, %zu needed", workspace_bytes,
                md_color_moments_workspace_bytes(B, H, W));
   const long P = cm_blocks_per_frame(H, W);                          // <= B H W / 8192 + 1
   MD_CHECK_ARG((long)B * P <= INT_MAX, "md_color_moments: %d frames of %ld workgroups exceed the grid", B, P);
-  const cm_src_t a = {src, B, H, W, sB, sC, sY, sX};
+  const fio_src_t a = {src, B, H, W, sB, sC, sY, sX};
   const int G = (W + 7) / 8;
   const long U = (long)H * G;
   const dim3 grid((unsigned)((long)B * P)), block(CM_THREADS);
@@ -233,34 +152,27 @@ struct cm_dst_t {
   long dB, dC, dY, dX;
 };
 
-// Thread i of B * H * G, G = ceil(W / 4): pixels x0 = 4 (i % G) .. x0 + np - 1 of row (i / G) % H of frame i / G / H, md_frames_u8's map.
+// One thread per unit of 4 pixels, md_frames_u8's map (fio_unit).
 template <typename T, bool F32D>
-__global__ void __launch_bounds__(CM_THREADS) color_apply_kernel(cm_src_t a, cm_dst_t d, long total, int G) {
+__global__ void __launch_bounds__(CM_THREADS) color_apply_kernel(fio_src_t a, cm_dst_t d, long total, int G) {
   for (long i = (long)blockIdx.x * CM_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * CM_THREADS) {
-    const int xg = (int)(i % G);
-    const long row = i / G;
-    const int y = (int)(row % a.H), b = (int)(row / a.H);            // b < B: i < total = B H G
-    const int x0 = xg * 4, np = a.W - x0 < 4 ? a.W - x0 : 4;
-    const T* ps = (const T*)a.src + (long)b * a.sB + (long)y * a.sY + (long)x0 * a.sX;
-    float v[4][3];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[p][c] = 0.f;
-    cm_load<T, 4, 4>(ps, a.sC, a.sX, np, x0 + 4 < a.W, v);
+    const fio_unit_t un = fio_unit<4>((unsigned)i, G, a.H, a.W);     // b < B: i < total = B H G
+    const int b = un.b, y = un.y, x0 = un.x0, np = un.np;
+    FIO_PIXELS(v, 4, 3);
+    fio_load<T, 3, 4, 4>(fio_src_at<T>(a, un), a.sC, a.sX, np, un.inner, v);
     float m[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) m[k] = d.coef[(long)b * 12 + k];    // row-major M, then t
     float o[4][3];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const float s0 = cm_display(v[p][0]), s1 = cm_display(v[p][1]), s2 = cm_display(v[p][2]);
+      const float s0 = fio_display(v[p][0]), s1 = fio_display(v[p][1]), s2 = fio_display(v[p][2]);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        float r = cm_add(m[9 + c], cm_mul(m[3 * c], s0));
-        r = cm_add(r, cm_mul(m[3 * c + 1], s1));
-        r = cm_add(r, cm_mul(m[3 * c + 2], s2));
-        o[p][c] = r < 0.f ? 0.f : (r > 1.f ? 1.f : r);               // NaN kept
+        float r = fio_add(m[9 + c], fio_mul(m[3 * c], s0));
+        r = fio_add(r, fio_mul(m[3 * c + 1], s1));
+        r = fio_add(r, fio_mul(m[3 * c + 2], s2));
+        o[p][c] = fio_clamp01(r);                                    // NaN kept
       }
     }
     if (F32D) {
@@ -277,24 +189,7 @@ __global__ void __launch_bounds__(CM_THREADS) color_apply_kernel(cm_src_t a, cm_
         }
       }
     } else {
-      unsigned w[3] = {0u, 0u, 0u};                                  // the 12 bytes, little-endian in 3 words
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float r = o[p][c];
-          const unsigned q = r != r ? 0u : (unsigned)cm_mul(r, 255.f);         // NaN -> 0; r in [0, 1]: the product is in [0, 255]
-          w[(p * 3 + c) / 4] |= q << (8 * ((p * 3 + c) % 4));
-        }
-      unsigned char* pd = (unsigned char*)d.dst + (long)b * d.dB + (long)y * d.dY + (long)x0 * 3;
-      if (np == 4 && ((uintptr_t)pd % 4) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) reinterpret_cast<unsigned*>(pd)[k] = w[k];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 12; ++j)
-          if (j < np * 3) pd[j] = (unsigned char)(w[j / 4] >> (8 * (j % 4)));
-      }
+      fio_store_bytes<3>((unsigned char*)d.dst + (long)b * d.dB + (long)y * d.dY + (long)x0 * 3, np, o);
     }
   }
 }
@@ -302,28 +197,21 @@ __global__ void __launch_bounds__(CM_THREADS) color_apply_kernel(cm_src_t a, cm_
 extern "C" int md_color_apply(const void* src, int src_is_f32, const void* coef, void* dst, int dst_is_f32, int B, int H, int W, long sB, long sC,
                               long sY, long sX, long dB, long dC, long dY, long dX, void* stream) {
   MD_CHECK_ARG(src && coef && dst, "md_color_apply: NULL src, coef or dst");
-  MD_CHECK_ARG(B > 0 && H > 0 && W > 0, "md_color_apply: B, H, W must be positive (%d, %d, %d)", B, H, W);
-  MD_CHECK_ARG(cm_shape_ok(B, H, W), "md_color_apply: B*H*W must fit an int (B=%d, %d x %d)", B, H, W);
-  MD_CHECK_ARG((src_is_f32 == 0 || src_is_f32 == 1) && (dst_is_f32 == 0 || dst_is_f32 == 1), "md_color_apply: src_is_f32 and dst_is_f32 must be 0 or 1, got %d, %d",
-               src_is_f32, dst_is_f32);
-  MD_CHECK_ARG(((uintptr_t)src % (src_is_f32 ? 4 : 2)) == 0, "md_color_apply: src must be aligned to its element (%d bytes)", src_is_f32 ? 4 : 2);
+  if (int e = fio_check_src("md_color_apply", src, src_is_f32, B, H, W)) return e;
+  MD_CHECK_ARG(dst_is_f32 == 0 || dst_is_f32 == 1, "md_color_apply: dst_is_f32 must be 0 or 1, got %d", dst_is_f32);
   MD_CHECK_ARG(((uintptr_t)coef % 4) == 0, "md_color_apply: coef needs 4-byte alignment");
   if (dst_is_f32) {
     MD_CHECK_ARG(((uintptr_t)dst % 4) == 0, "md_color_apply: an fp32 dst needs 4-byte alignment");
     MD_CHECK_ARG(dB > 0 && dC > 0 && dY > 0 && dX > 0, "md_color_apply: the strides of an fp32 dst must be positive (%ld, %ld, %ld, %ld)", dB, dC, dY, dX);
   } else {
-    const long wc = (long)W * 3;
     MD_CHECK_ARG(dC == 1 && dX == 3, "md_color_apply: a byte dst has packed pixels, dC = 1 and dX = 3, got %ld and %ld", dC, dX);
-    MD_CHECK_ARG(dY >= wc && dY <= (LONG_MAX - wc) / H, "md_color_apply: the row pitch dY = %ld must be at least 3*W = %ld (and (H-1)*dY + 3*W within long)", dY, wc);
-    MD_CHECK_ARG(dB >= (long)(H - 1) * dY + wc && dB <= LONG_MAX / B, "md_color_apply: the frame pitch dB = %ld must be at least (H-1)*dY + 3*W = %ld (and B*dB within long)",
-                 dB, (long)(H - 1) * dY + wc);
+    if (int e = fio_check_bytes("md_color_apply", B, H, W, 3, dB, dY)) return e;
   }
-  const cm_src_t a = {src, B, H, W, sB, sC, sY, sX};
+  const fio_src_t a = {src, B, H, W, sB, sC, sY, sX};
   const cm_dst_t d = {dst, (const float*)coef, dB, dC, dY, dX};
   const int G = (W + 3) / 4;
   const long total = (long)B * H * G;
-  const long blocks = (total + CM_THREADS - 1) / CM_THREADS;
-  const dim3 grid((unsigned)(blocks < CM_MAX_BLOCKS ? blocks : CM_MAX_BLOCKS)), block(CM_THREADS);
+  const dim3 grid = fio_grid(total), block(CM_THREADS);
   const hipStream_t st = (hipStream_t)stream;
   if (src_is_f32) {
     if (dst_is_f32)

@@ -681,29 +681,16 @@ def frames_u8(src, out=None, *, f32_math=None):
     ((x / 2 + 0.5).clamp(0, 1).float() * 255) truncated, operation by operation: in fp16 with f32_math=False, in fp32 with f32_math=True;
     None: as the source dtype.  An fp32 source needs fp32 arithmetic.  NaN gives 0.  `out`: a uint8 (B, H, W, C) tensor or VIEW whose last two
     dimensions are packed (stride C and 1); the row and frame pitches are free, so a frame can land inside a larger canvas.  Returns out."""
-    if not src.is_cuda or src.dtype not in (torch.float16, torch.float32):
-        raise _lib.MdanceHipError("frames_u8: src must be a CUDA fp16/fp32 tensor")
-    if src.dim() != 4 or not 1 <= src.shape[1] <= 4 or min(src.shape) < 1:
-        raise _lib.MdanceHipError(f"frames_u8: src must be (B, C, H, W)-shaped with C in 1..4 and no empty dimension, got {tuple(src.shape)}")
-    B, C, H, W = src.shape
+    B, C, H, W = _frame_src("frames_u8", src, range(1, 5))
     if f32_math is None:
         f32_math = src.dtype == torch.float32
     if not isinstance(f32_math, bool):
         raise _lib.MdanceHipError(f"frames_u8: f32_math must be True, False or None, got {f32_math!r}")
     if src.dtype == torch.float32 and not f32_math:
         raise _lib.MdanceHipError("frames_u8: an fp32 source needs f32_math=True")
-    if out is None:
-        out = torch.empty((B, H, W, C), device=src.device, dtype=torch.uint8)
-    if not out.is_cuda or out.dtype != torch.uint8 or out.device != src.device:
-        raise _lib.MdanceHipError("frames_u8: out must be a CUDA uint8 tensor on src's device")
-    if tuple(out.shape) != (B, H, W, C) or out.stride(3) != 1 or out.stride(2) != C:
-        raise _lib.MdanceHipError(f"frames_u8: out must be a (B, H, W, C) = ({B}, {H}, {W}, {C}) view with packed pixels (strides (*, *, {C}, 1)), got shape "
-                                  f"{tuple(out.shape)} strides {tuple(out.stride())}")
-    sB, sC, sY, sX = src.stride()
-    dY = out.stride(1) if H > 1 else max(out.stride(1), W * C)           # the stride of a dimension of size 1 says nothing
-    dB = out.stride(0) if B > 1 else max(out.stride(0), (H - 1) * dY + W * C)
+    out, dB, dY = _byte_dst("frames_u8", out, B, H, W, C, src.device)
     n = B * H * W * C
-    _lib.call("md_frames_u8", src.data_ptr(), int(src.dtype == torch.float32), int(f32_math), out.data_ptr(), B, H, W, C, sB, sC, sY, sX, dB, dY, _st(),
+    _lib.call("md_frames_u8", src.data_ptr(), int(src.dtype == torch.float32), int(f32_math), out.data_ptr(), B, H, W, C, *src.stride(), dB, dY, _st(),
               meta=(f"frames_u8 B={B} {H}x{W} C={C} {'f32' if f32_math else 'f16'}", 0.0, float(src.element_size() * n + n)))
     return out
 
@@ -786,16 +773,33 @@ def rel_l1(a, b, out=None):
     return out
 
 
-def _color_src(who, src):
-    """The refusals both colour-matching operators share with frames_u8, for 3 channels -> (B, H, W)."""
+def _frame_src(who, src, channels):
+    """The source refusals frames_u8 and both colour-matching operators share; channels: the counts taken, a range -> (B, C, H, W)."""
     if not src.is_cuda or src.dtype not in (torch.float16, torch.float32):
         raise _lib.MdanceHipError(f"{who}: src must be a CUDA fp16/fp32 tensor")
-    if src.dim() != 4 or src.shape[1] != 3 or min(src.shape) < 1:
-        raise _lib.MdanceHipError(f"{who}: src must be (B, 3, H, W)-shaped with no empty dimension, got {tuple(src.shape)}")
-    B, _, H, W = src.shape
+    if src.dim() != 4 or src.shape[1] not in channels or min(src.shape) < 1:
+        lo, hi = channels[0], channels[-1]
+        form = f"(B, {lo}, H, W)-shaped with" if lo == hi else f"(B, C, H, W)-shaped with C in {lo}..{hi} and"
+        raise _lib.MdanceHipError(f"{who}: src must be {form} no empty dimension, got {tuple(src.shape)}")
+    B, C, H, W = src.shape
     if B * H * W >= 1 << 31:
         raise _lib.MdanceHipError(f"{who}: B*H*W = {B * H * W} exceeds the entry point's int arguments")
-    return B, H, W
+    return B, C, H, W
+
+
+def _byte_dst(who, out, B, H, W, C, device):
+    """The byte destination of frames_u8 and color_apply: a uint8 (B, H, W, C) tensor or VIEW with packed pixels (a new tensor for None) ->
+    (out, dB, dY), the frame and row pitches the entry points take."""
+    if out is None:
+        out = torch.empty((B, H, W, C), device=device, dtype=torch.uint8)
+    if not out.is_cuda or out.dtype != torch.uint8 or out.device != device:
+        raise _lib.MdanceHipError(f"{who}: out must be a CUDA uint8 tensor on src's device")
+    if tuple(out.shape) != (B, H, W, C) or out.stride(3) != 1 or out.stride(2) != C:
+        raise _lib.MdanceHipError(f"{who}: out must be a (B, H, W, C) = ({B}, {H}, {W}, {C}) view with packed pixels (strides (*, *, {C}, 1)), got shape "
+                                  f"{tuple(out.shape)} strides {tuple(out.stride())}")
+    dY = out.stride(1) if H > 1 else max(out.stride(1), W * C)           # the stride of a dimension of size 1 says nothing
+    dB = out.stride(0) if B > 1 else max(out.stride(0), (H - 1) * dY + W * C)
+    return out, dB, dY
 
 
 def color_moments(src, out=None):
@@ -804,7 +808,7 @@ def color_moments(src, out=None):
     s = clamp(0.5 v + 0.5, 0, 1) in fp32 (NaN kept): fp32 terms, fp32 sums per workgroup, fp64 across workgroups, all in a fixed order
     (csrc/color_match.hip), so the same input gives the same bits.  Nothing is read back: the caller does.  `out`: a contiguous float64
     (B, 9) destination.  The workspace (36 bytes per 8192 pixels) is kept per (device, stream)."""
-    B, H, W = _color_src("color_moments", src)
+    B, _, H, W = _frame_src("color_moments", src, range(3, 4))
     if out is None:
         out = torch.empty((B, 9), device=src.device, dtype=torch.float64)
     _chk(out, "out", torch.float64)
@@ -823,7 +827,7 @@ def color_apply(src, coef, out=None, *, dtype=torch.uint8):
     fp32 on the device, frame b's row-major 3 x 3 matrix M then its offset t -> y = clamp(M s + t, 0, 1), every operation rounded in fp32.
     dtype torch.uint8: out (B, H, W, 3) bytes, fp32(y * 255) truncated, NaN -> 0, `out` as frames_u8 takes it (packed pixels, free row and
     frame pitches); dtype torch.float32: out (B, 3, H, W) fp32 with any positive strides, y itself, NaN kept.  Returns out."""
-    B, H, W = _color_src("color_apply", src)
+    B, _, H, W = _frame_src("color_apply", src, range(3, 4))
     _chk(coef, "coef", torch.float32)
     if tuple(coef.shape) != (B, 12) or not coef.is_contiguous() or coef.device != src.device:
         raise _lib.MdanceHipError(f"color_apply: coef must be ({B}, 12) contiguous fp32 on src's device, got {tuple(coef.shape)}")
@@ -832,15 +836,7 @@ def color_apply(src, coef, out=None, *, dtype=torch.uint8):
     sB, sC, sY, sX = src.stride()
     n = B * H * W * 3
     if dtype == torch.uint8:
-        if out is None:
-            out = torch.empty((B, H, W, 3), device=src.device, dtype=torch.uint8)
-        if not out.is_cuda or out.dtype != torch.uint8 or out.device != src.device:
-            raise _lib.MdanceHipError("color_apply: out must be a CUDA uint8 tensor on src's device")
-        if tuple(out.shape) != (B, H, W, 3) or out.stride(3) != 1 or out.stride(2) != 3:
-            raise _lib.MdanceHipError(f"color_apply: out must be a (B, H, W, 3) = ({B}, {H}, {W}, 3) view with packed pixels (strides (*, *, 3, 1)), got "
-                                      f"shape {tuple(out.shape)} strides {tuple(out.stride())}")
-        dY = out.stride(1) if H > 1 else max(out.stride(1), W * 3)          # the stride of a dimension of size 1 says nothing
-        dB = out.stride(0) if B > 1 else max(out.stride(0), (H - 1) * dY + W * 3)
+        out, dB, dY = _byte_dst("color_apply", out, B, H, W, 3, src.device)
         dst = (dB, 1, dY, 3)
     else:
         if out is None:

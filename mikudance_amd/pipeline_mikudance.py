@@ -937,26 +937,50 @@ class MikuDanceVideoPipeline:
         lat = torch.cat([self._encode(u[i:i + self.vae_batch]) for i in range(0, u.shape[0], self.vae_batch)], dim=0)
         return lat if len(rep) == x.shape[0] else lat[torch.tensor(inverse, device=lat.device)]
 
-    def _decode_u8(self, latents, batch, temporal=False):
-        """The uint8 twin of decode_latents / decode_temporal: the same scaling, frame order and VAE batches, every batch through the VAE's
-        decode_u8 (md_frames_u8: quantised on the device, straight into its rows of one (b f, H, W, 3) buffer), ONE device-to-host copy of
-        bytes -> a CPU torch.uint8 (b, f, H, W, 3) tensor: bit for bit (the float path's array * 255) cast to uint8 and permuted."""
-        if not hasattr(self.vae, "decode_u8"):
-            raise ValueError(f"output_type 'uint8' / 'pil': {type(self.vae).__name__} has no decode_u8")
+    def _decode_frames(self, latents, batch, temporal, per_batch, display=False):
+        """The one road from (b, c, f, h, w) latents to frames on the host, shared by the float, the bytes and the colour-matched output: the
+        scaling and the frame order of the reference, VAE batches of `batch` frames (num_frames= for the temporal decoder), clips again, ONE
+        device-to-host copy.  per_batch(i, chunk, kw, rows) decodes frames i .. i + len(chunk) - 1 of the `total` = b f: it either returns
+        them (the batches are concatenated) or writes them to rows(i, n, frame_shape, dtype, device) -- rows i .. i + n - 1 of ONE
+        (total, *frame_shape) device buffer, allocated at the first call, which alone needs the last three: the first batch tells the frame
+        size (the VAE's factor is its own) -- and returns None.  uint8 frames are (H, W, 3): the result is the CPU (b, f, H, W, 3) tensor.  Other frames are (c, H, W): the
+        result is the float32 (b, c, f, H, W) numpy array, after (x / 2 + 0.5).clamp(0, 1) if `display`."""
         video_length = latents.shape[2]
         latents = 1 / 0.18215 * latents
         latents = latents.permute(0, 2, 1, 3, 4).reshape((-1,) + tuple(latents.shape[1:2]) + tuple(latents.shape[3:]))
-        video = None
-        for i in range(0, latents.shape[0], batch):
+        total, parts, whole = latents.shape[0], [], []
+
+        def rows(i, n, frame_shape=None, dtype=None, device=None):
+            if not whole:
+                whole.append(torch.empty((total,) + tuple(frame_shape), device=device, dtype=dtype))
+            return whole[0][i:i + n]
+
+        for i in range(0, total, batch):
             chunk = latents[i:i + batch].to(self.vae.dtype)
-            kw = dict(num_frames=chunk.shape[0]) if temporal else {}
-            if video is None:                                              # the first batch tells the frame size (the VAE's factor is its own)
-                first = self.vae.decode_u8(chunk, **kw)
-                video = torch.empty((latents.shape[0],) + tuple(first.shape[1:]), device=first.device, dtype=torch.uint8)
-                video[:first.shape[0]] = first
+            parts.append(per_batch(i, chunk, dict(num_frames=chunk.shape[0]) if temporal else {}, rows))
+        video = whole[0] if whole else torch.cat(parts)                     # per-frame arithmetic: batching changes nothing
+        video = video.reshape((-1, video_length) + tuple(video.shape[1:]))
+        if video.dtype == torch.uint8:
+            return video.cpu()
+        video = video.permute(0, 2, 1, 3, 4)
+        if display:
+            video = (video / 2 + 0.5).clamp(0, 1)
+        return video.cpu().float().numpy()
+
+    def _decode_u8(self, latents, batch, temporal=False):
+        """The uint8 twin of decode_latents / decode_temporal: every batch through the VAE's decode_u8 (md_frames_u8: quantised on the device,
+        straight into its rows of the one buffer) -> a CPU torch.uint8 (b, f, H, W, 3) tensor: bit for bit (the float path's array * 255)
+        cast to uint8 and permuted."""
+        if not hasattr(self.vae, "decode_u8"):
+            raise ValueError(f"output_type 'uint8' / 'pil': {type(self.vae).__name__} has no decode_u8")
+
+        def per_batch(i, chunk, kw, rows):
+            if i:
+                self.vae.decode_u8(chunk, out=rows(i, chunk.shape[0]), **kw)
             else:
-                self.vae.decode_u8(chunk, out=video[i:i + chunk.shape[0]], **kw)
-        return video.reshape((-1, video_length) + tuple(video.shape[1:])).cpu()
+                first = self.vae.decode_u8(chunk, **kw)
+                rows(0, first.shape[0], first.shape[1:], torch.uint8, first.device)[:] = first
+        return self._decode_frames(latents, batch, temporal, per_batch)
 
     def color_match_plan(self, color_match, color_match_strength, color_match_target, color_match_scope, ref_image, height, width, clips):
         """__call__'s color_match keywords, checked before anything runs -> None (off) or the plan _decode_color_matched takes:
@@ -1005,50 +1029,38 @@ class MikuDanceVideoPipeline:
         then every batch is applied.  Target "first_frame": the sums of the clip's own frame 0.  self.last_color_match: (M', t', fallback)
         per frame, in frame order, float64."""
         from . import color_match as CM
-        video_length = latents.shape[2]
-        latents = 1 / 0.18215 * latents
-        latents = latents.permute(0, 2, 1, 3, 4).reshape((-1,) + tuple(latents.shape[1:2]) + tuple(latents.shape[3:]))
-        total = latents.shape[0]
+        video_length, total = latents.shape[2], latents.shape[0] * latents.shape[2]
         mode, strength, per_clip, targets = plan["mode"], plan["strength"], plan["scope"] == "clip", plan["targets"]
-        video, held, sums, pixels = None, [], np.empty((total, 9), dtype=np.float64), 0
+        held, sums, maps = [], np.empty((total, 9), dtype=np.float64), []
 
-        def target_of(clip):
+        def target_of(clip, pixels):
             t = targets[clip]
             return (sums[clip * video_length], pixels) if t == "first_frame" else t
 
-        def apply(i, view, maps):
-            coef = torch.from_numpy(CM.coefficients(maps)).to(view.device)
-            if as_bytes:
-                ops.color_apply(view, coef, out=video[i:i + view.shape[0]], dtype=torch.uint8)
-            else:
-                ops.color_apply(view, coef, out=video[i:i + view.shape[0]], dtype=torch.float32)
-
-        maps = []
-        for i in range(0, total, batch):
-            chunk = latents[i:i + batch].to(self.vae.dtype)
-            view = self.vae.decode_image_view(chunk, **(dict(num_frames=chunk.shape[0]) if temporal else {}))
+        def apply(i, view, maps, rows):
             n, _, H, W = view.shape
-            if video is None:                                              # the first batch tells the frame size (the VAE's factor is its own)
-                pixels = H * W
-                video = torch.empty((total, H, W, 3) if as_bytes else (total, 3, H, W), device=view.device, dtype=torch.uint8 if as_bytes else torch.float32)
+            out = rows(i, n, (H, W, 3) if as_bytes else (3, H, W), torch.uint8 if as_bytes else torch.float32, view.device)
+            ops.color_apply(view, torch.from_numpy(CM.coefficients(maps)).to(view.device), out=out, dtype=out.dtype)
+
+        def per_batch(i, chunk, kw, rows):
+            view = self.vae.decode_image_view(chunk, **kw)
+            n, pixels = view.shape[0], view.shape[2] * view.shape[3]
             sums[i:i + n] = ops.color_moments(view).cpu().numpy()          # the one host read of this batch
-            if per_clip:
-                held.append((i, view))
-                continue
-            batch_maps = [CM.transform(sums[j], pixels, *target_of(j // video_length), mode, strength) for j in range(i, i + n)]
-            apply(i, view, batch_maps)
-            maps += batch_maps
-        if per_clip:
-            clip_maps = [CM.transform(sums[c * video_length:(c + 1) * video_length].sum(0), pixels * video_length, *target_of(c), mode, strength)
-                         for c in range(total // video_length)]
-            maps = [clip_maps[j // video_length] for j in range(total)]
-            for i, view in held:
-                apply(i, view, maps[i:i + view.shape[0]])
-            del held[:]
+            if not per_clip:
+                maps.extend(CM.transform(sums[j], pixels, *target_of(j // video_length, pixels), mode, strength) for j in range(i, i + n))
+                apply(i, view, maps[i:], rows)
+                return
+            held.append((i, view))
+            if i + n == total:                                             # the last batch's sums are in
+                clip_maps = [CM.transform(sums[c * video_length:(c + 1) * video_length].sum(0), pixels * video_length, *target_of(c, pixels), mode, strength)
+                             for c in range(total // video_length)]
+                maps.extend(clip_maps[j // video_length] for j in range(total))
+                for j, held_view in held:
+                    apply(j, held_view, maps[j:j + held_view.shape[0]], rows)
+                del held[:]
+        video = self._decode_frames(latents, batch, temporal, per_batch)
         self.last_color_match = maps
-        if as_bytes:
-            return video.reshape((-1, video_length) + tuple(video.shape[1:])).cpu()
-        return video.reshape((-1, video_length) + tuple(video.shape[1:])).permute(0, 2, 1, 3, 4).cpu().numpy()
+        return video
 
     def decode_latents(self, latents, output_type=None):
         """reference :115-130 -- per-frame VAE decode, (x/2+0.5).clamp(0,1), float32 numpy (b,c,f,h,w).  output_type "uint8": a CPU torch.uint8
@@ -1057,14 +1069,7 @@ class MikuDanceVideoPipeline:
             if output_type != "uint8":
                 raise ValueError(f"decode_latents: output_type must be None or 'uint8', got {output_type!r}")
             return self._decode_u8(latents, self.vae_batch)
-        video_length = latents.shape[2]
-        latents = 1 / 0.18215 * latents
-        latents = latents.permute(0, 2, 1, 3, 4).reshape((-1,) + tuple(latents.shape[1:2]) + tuple(latents.shape[3:]))
-        video = [self.vae.decode(latents[i:i + self.vae_batch].to(self.vae.dtype)).sample for i in range(0, latents.shape[0], self.vae_batch)]
-        video = torch.cat(video)                                             # per-frame arithmetic: batching changes nothing
-        video = video.reshape((-1, video_length) + tuple(video.shape[1:])).permute(0, 2, 1, 3, 4)
-        video = (video / 2 + 0.5).clamp(0, 1)
-        return video.cpu().float().numpy()
+        return self._decode_frames(latents, self.vae_batch, False, lambda i, chunk, kw, rows: self.vae.decode(chunk, **kw).sample, display=True)
 
     def decode_temporal(self, latents, decode_chunk_size=None, output_type=None):
         """reference :132-150 (AutoencoderKLTemporalDecoder in chunks of self.decode_chunk_size = 16 frames).  output_type as decode_latents."""
@@ -1073,17 +1078,7 @@ class MikuDanceVideoPipeline:
             if output_type != "uint8":
                 raise ValueError(f"decode_temporal: output_type must be None or 'uint8', got {output_type!r}")
             return self._decode_u8(latents, decode_chunk_size, temporal=True)
-        video_length = latents.shape[2]
-        latents = 1 / 0.18215 * latents
-        latents = latents.permute(0, 2, 1, 3, 4).reshape((-1,) + tuple(latents.shape[1:2]) + tuple(latents.shape[3:]))
-        video = []
-        for i in range(0, latents.shape[0], decode_chunk_size):
-            chunk = latents[i:i + decode_chunk_size]
-            video.append(self.vae.decode(chunk.to(self.vae.dtype), num_frames=chunk.shape[0]).sample)
-        video = torch.cat(video)
-        video = video.reshape((-1, video_length) + tuple(video.shape[1:])).permute(0, 2, 1, 3, 4)
-        video = (video / 2 + 0.5).clamp(0, 1)
-        return video.cpu().float().numpy()
+        return self._decode_frames(latents, decode_chunk_size, True, lambda i, chunk, kw, rows: self.vae.decode(chunk, **kw).sample, display=True)
 
     def interpolate_latents(self, latents, interpolation_factor, device):
         """reference :317-360 -- (F - 1) * factor + 1 frames: every original frame, and factor - 1 blends between neighbours
@@ -1368,17 +1363,14 @@ class MikuDanceVideoPipeline:
                 # colour matched on the device between the decode and the quantisation (md_color_moments / md_color_apply)
                 images = self._decode_color_matched(latents, self.decode_chunk_size if self.video_decoder else self.vae_batch, color_plan,
                                                     temporal=bool(self.video_decoder), as_bytes=output_type in ("uint8", "pil"))
-                if output_type == "pil":
-                    from PIL import Image
-                    images = [[Image.fromarray(frame.numpy()) for frame in clip] for clip in images]
             elif output_type in ("uint8", "pil"):
                 # frames quantised on the device (md_frames_u8), in the layout the writers take: half the bytes of the fp16 transfer, a quarter of the fp32 host array's
                 images = self.decode_temporal(latents, output_type="uint8") if self.video_decoder else self.decode_latents(latents, output_type="uint8")
-                if output_type == "pil":
-                    from PIL import Image
-                    images = [[Image.fromarray(frame.numpy()) for frame in clip] for clip in images]
             else:
                 images = self.decode_temporal(latents) if self.video_decoder else self.decode_latents(latents)
+            if output_type == "pil":
+                from PIL import Image
+                images = [[Image.fromarray(frame.numpy()) for frame in clip] for clip in images]
             if output_type == "tensor":
                 images = torch.from_numpy(images)
             if not return_dict:

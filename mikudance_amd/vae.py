@@ -338,13 +338,7 @@ class AutoencoderKL(_Packed):
         chain for fp16 latents, fp32 chain for fp32).  Untiled, the decoder's NHWC image goes into ops.frames_u8 (md_frames_u8) directly: no
         NCHW tensor, no elementwise pass.  With tiling or slicing on, decode runs as it stands and one frames_u8 reads its NCHW result.
         `out`: a destination view as ops.frames_u8 takes it."""
-        if z.dim() != 4 or z.shape[1] != self.zc:
-            raise ValueError(f"AutoencoderKL.decode_u8 expects (B, {self.zc}, h, w), got {tuple(z.shape)}")
-        f32 = self._out_dtype(z) == torch.float32
-        tiled = self.use_tiling and max(z.shape[2:]) > self.tile_latent_min_size
-        if tiled or (self.use_slicing and z.shape[0] > 1):
-            return ops.frames_u8(self.decode(z).sample, out, f32_math=f32)
-        return ops.frames_u8(self._image_nhwc(z).permute(0, 3, 1, 2), out, f32_math=f32)
+        return ops.frames_u8(self.decode_image_view(z), out, f32_math=self._out_dtype(z) == torch.float32)
 
     @torch.no_grad()
     def decode_image_view(self, z):

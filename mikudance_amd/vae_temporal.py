@@ -259,10 +259,7 @@ class AutoencoderKLTemporalDecoder(_Packed):
         """decode(z, num_frames) as the bytes a writer takes: (B, H, W, out_channels) uint8 on the device, bit for bit
         ((decode(...).sample / 2 + 0.5).clamp(0, 1).float() * 255) truncated, in the arithmetic of the dtype decode would have returned.  The
         decoder's NHWC result (pixel pitch 8) goes into ops.frames_u8 (md_frames_u8) directly: no NCHW tensor, no elementwise pass."""
-        if z.dim() != 4 or z.shape[1] != self.zc or z.shape[0] % num_frames:
-            raise ValueError(f"decode_u8 expects (clips * num_frames, {self.zc}, h, w), got {tuple(z.shape)} with num_frames={num_frames}")
-        y = self._image_nhwc(z, num_frames)                                              # (B, 8h, 8w, 8): 3 valid channels
-        return ops.frames_u8(y[..., :self.decoder.out_channels].permute(0, 3, 1, 2), out, f32_math=z.dtype in (torch.float32, torch.float64))
+        return ops.frames_u8(self.decode_image_view(z, num_frames), out, f32_math=z.dtype in (torch.float32, torch.float64))
 
     @torch.no_grad()
     def decode_image_view(self, z, num_frames=1):

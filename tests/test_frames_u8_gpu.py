@@ -76,9 +76,9 @@ def _values(shape, dtype, seed):
     return x
 
 
-def _nhwc(B, C, H, W, ldc, dtype=F16, seed=3):
-    buf = _values((B, H, W, ldc), dtype, seed).to(DEV)
-    return buf[..., :C].permute(0, 3, 1, 2)
+def _nhwc(B, C, H, W, ldc, dtype=F16, seed=3, offset=0):
+    buf = _values((B * H * W * ldc + offset,), dtype, seed).to(DEV)
+    return buf[offset:].view(B, H, W, ldc)[..., :C].permute(0, 3, 1, 2)
 
 
 def _nchw_view(B, C, H, W, dtype=F16, seed=4):
@@ -101,6 +101,12 @@ FORMS = {
     "f32-nchw": lambda B, H, W: (_values((B, 3, H, W), torch.float32, 9).to(DEV), None),
     "f32-nhwc-ld3": lambda B, H, W: (_nhwc(B, 3, H, W, 3, torch.float32), None),
     "f32-nchw-odd-view": lambda B, H, W: (_nchw_view(B, 3, H, W, torch.float32), None),
+    # pitch 4 / 8 with padding channels: vector loads with the padding dropped, element loads on the last unit of every row
+    "nhwc-ld4-c3": lambda B, H, W: (_nhwc(B, 3, H, W, 4), None),
+    "c2-nhwc-ld4": lambda B, H, W: (_nhwc(B, 2, H, W, 4), None),
+    "c2-nhwc-ld8": lambda B, H, W: (_nhwc(B, 2, H, W, 8), None),
+    "nhwc-ld8-c3-2byte-base": lambda B, H, W: (_nhwc(B, 3, H, W, 8, offset=1), None),      # aligned to its element only: element loads
+    "f32-nhwc-ld4-c3": lambda B, H, W: (_nhwc(B, 3, H, W, 4, torch.float32), None),
 }
 
 
@@ -120,7 +126,7 @@ def _window(B, H, W, C, pitch_extra=11):
 
 
 @pytest.mark.parametrize("size", [(2, 5, 7), (2, 16, 16)], ids=["2x5x7", "2x16x16"])
-@pytest.mark.parametrize("form", ["nhwc-ld3", "nchw", "c4-nchw", "c1-nchw"])
+@pytest.mark.parametrize("form", ["nhwc-ld3", "nchw", "c4-nchw", "c1-nchw", "nhwc-ld8-c3"])
 def test_window_of_a_canvas(form, size):
     B, H, W = size
     src, f32_math = FORMS[form](*size)
@@ -140,7 +146,7 @@ def test_window_of_a_canvas(form, size):
     assert (canvas1[:, :, :11] == SENTINEL).all() and (canvas1[:, :, 11 + W * C:] == SENTINEL).all()
 
 
-@pytest.mark.parametrize("B,form", [(9, "nhwc-ld3"), (9, "nchw"), (33, "nhwc-ld3"), (33, "nchw-odd-view")])
+@pytest.mark.parametrize("B,form", [(9, "nhwc-ld3"), (9, "nchw"), (33, "nhwc-ld3"), (33, "nchw-odd-view"), (33, "nhwc-ld8-c3")])
 def test_past_one_grid_round(B, form):
     """B = 9 of 256 x 256 x 3: 589 824 pixels, more than 2048 x 256 threads.  The kernel gives a thread 4 pixels of a row, so ITS grid-stride loop
     starts a second round at B = 33 (540 672 groups of 4 > 524 288 threads): both sizes run."""

@@ -88,6 +88,7 @@ def paths_equal_the_package(vae, dev):
     """The timed paths against MikuDanceVideoPipeline's own methods on a small clip."""
     from mikudance_amd.pipeline_mikudance import MikuDanceVideoPipeline as P
     pipe = types.SimpleNamespace(vae=vae, vae_batch=VAE_BATCH)
+    pipe._decode_frames = types.MethodType(P._decode_frames, pipe)
     lat = torch.randn(1, 4, 10, 32, 32, generator=torch.Generator().manual_seed(3)).half().to(dev)
     z = (1 / 0.18215 * lat).permute(0, 2, 1, 3, 4).reshape(-1, 4, 32, 32).to(vae.dtype)
     target = target_sums(256)
@@ -154,7 +155,9 @@ def main():
         coef = (torch.eye(3).reshape(1, 9).repeat(VAE_BATCH, 1) * 0.9).to(dev)
         coef = torch.cat([coef, torch.full((VAE_BATCH, 3), 0.05, device=dev)], 1).contiguous()
         n = out.numel()
-        for label, src in (("nhwc", nhwc.permute(0, 3, 1, 2)), ("nchw", nchw)):
+        ld8 = torch.zeros((VAE_BATCH, size, size, 8), device=dev, dtype=nhwc.dtype)                  # the temporal decoder's image: pixel pitch 8
+        ld8[..., :3] = nhwc
+        for label, src in (("nhwc", nhwc.permute(0, 3, 1, 2)), ("nchw", nchw), ("nhwc_ld8", ld8[..., :3].permute(0, 3, 1, 2))):
             us = _events(lambda: ops.color_moments(src, sums))
             rec[f"moments_{label}_batch8"] = dict(us_per_call=round(us, 2), gb_per_s=round(2.0 * n / us / 1e3, 1), launches=2)
             us = _events(lambda: ops.color_apply(src, coef, out))

@@ -101,7 +101,7 @@ def paths_equal_the_package(vae, dev):
     from mikudance_amd import io_utils as U
     from mikudance_amd.pipeline_mikudance import MikuDanceVideoPipeline as P
     pipe = types.SimpleNamespace(vae=vae, vae_batch=VAE_BATCH)
-    pipe._decode_u8 = types.MethodType(P._decode_u8, pipe)
+    pipe._decode_u8, pipe._decode_frames = types.MethodType(P._decode_u8, pipe), types.MethodType(P._decode_frames, pipe)
     lat = torch.randn(1, 4, 10, 32, 32, generator=torch.Generator().manual_seed(3)).half().to(dev)
     images, keep = [], U.save_videos_from_pil
     U.save_videos_from_pil = lambda pils, path, fps=8: images.extend(pils)
@@ -183,7 +183,9 @@ def main():
         nhwc = (torch.rand(VAE_BATCH, size, size, 3, generator=g) * 3 - 1.5).half().to(dev)
         nchw = nhwc.permute(0, 3, 1, 2).contiguous()
         out = torch.empty((VAE_BATCH, size, size, 3), device=dev, dtype=torch.uint8)
-        for label, src in (("nhwc", nhwc.permute(0, 3, 1, 2)), ("nchw", nchw)):
+        ld8 = torch.zeros((VAE_BATCH, size, size, 8), device=dev, dtype=nhwc.dtype)                  # the temporal decoder's image: pixel pitch 8
+        ld8[..., :3] = nhwc
+        for label, src in (("nhwc", nhwc.permute(0, 3, 1, 2)), ("nchw", nchw), ("nhwc_ld8", ld8[..., :3].permute(0, 3, 1, 2))):
             for _ in range(10):
                 ops.frames_u8(src, out)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
