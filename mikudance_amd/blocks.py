@@ -252,7 +252,7 @@ class SelfAttnCall:
     """How the spatial self-attention of ONE UNet call differs from the plain one; handed unchanged to every TransformerBlock of the call.
     half: which rows of a classifier-free-guidance batch the call holds.  None: the whole batch (rows [0, M/2) unconditional, the rest
       conditional); 0: the unconditional rows only (the bank is ignored: reference src/models/mutual_mix_attention.py:181-201); 1: the
-      conditional rows only (every row reads the bank).  0 / 1 are the two kernel queues of UNet3DConditionModel._forward_two_queues.
+      conditional rows only (every row reads the bank).  0 / 1 are the two lanes (kernel queues) of UNet3DConditionModel._two_queues.
     identity: None, or the TransformerBlocks whose attention map softmax(q k^T d^-1/2) is the identity (perturbed-attention guidance, Ahn et
       al., arXiv 2403.17377; diffusers PAGIdentitySelfAttnProcessor2_0): attn1(x) = to_out(to_v(norm1(x) + bank)) + x, no q, no k, no
       attention launch, V row-major.

@@ -123,7 +123,7 @@ class MikuDanceVideoPipeline:
         self.vae_batch = 8                                                   # images per VAE call (the reference: 1)
         self.reference_reuse = True
         self.share_first_layers = True                                       # denoising UNet: conv_in + first resnet once for both CFG halves
-        # ... and, behind them, OPTIONALLY the unconditional and the conditional half as two kernel queues (UNet3DConditionModel._forward_two_queues;
+        # ... and, behind them, OPTIONALLY the unconditional and the conditional half as two kernel queues (UNet3DConditionModel._two_queues;
         # needs share_first_layers; pipe.two_queues = True or MD_TWO_QUEUES=1).  Off by default: on MI355X two queues of B = f kernels finish 7 % sooner
         # than the same launches back to back, but one queue of B = 2f kernels is already that much more efficient -- +0.2-0.35 % end to end
         # (profiles/r06_ab_two_queue_halves.log): measured, validated (tests/test_two_queues_gpu.py), not worth a second evaluation order by default

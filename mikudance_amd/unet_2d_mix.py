@@ -13,8 +13,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .blocks import MANModule
-from .unet_3d_mix import _Config, _Skips, _UNetBase
+from .blocks import PLAIN, MANModule
+from .unet_3d_mix import _Config, _Lane, _Pass, _Skips, _UNetBase
 
 
 @dataclass
@@ -23,9 +23,6 @@ class UNet2DConditionOutput:
 
     def __getitem__(self, i):
         return (self.sample,)[i]
-
-
-_NO_MOTION = dict(down=[False] * 4, up=[False] * 4, mid=False)
 
 
 class _UNet2DBase(_UNetBase):
@@ -119,58 +116,26 @@ class UNet2DConditionModel(_UNet2DBase):
         resized scene-motion map; timesteps: None (t = 0, what the pipeline passes: pipeline_mikudance.py:649), one value, or
         one value per sample.  Returns the (unused) sample."""
         pk = self.packed()
-        dev = x.device
         B, hh, ww, _ = x.shape
-        force_size = self._needs_upsample_size(hh, ww, len(self.down_blocks))
         t = torch.zeros(1) if timesteps is None else torch.as_tensor(timesteps, dtype=torch.float32).reshape(-1).cpu()
         if t.numel() > 1 and bool((t == t[0]).all()):
             t = t[:1]
         assert t.numel() in (1, B), f"timestep: one value or one per sample ({B}), got {t.numel()}"
-        trows = self._time_rows(pk, t, dev)                                  # one group (every frame shares t) or one per frame
+        trows = self._time_rows(pk, t, x.device)                             # one group (every frame shares t) or one per frame
         fpg = B // t.numel()                                                 # frames per time-embedding row
         blocks = self.transformer_blocks_in_order()
-        # last bank writer in EXECUTION order (down -> mid -> up): the last attention of the last up block
+        # last bank writer in EXECUTION order (down -> mid -> up): the last attention of the last up block.  The sample after the LAST bank
+        # write is discarded by the pipeline: skip_dead_tail stops the walk there (result preserving)
         last_writer = self.up_blocks[-1].attentions[-1].transformer_blocks[0] \
-            if blocks and all(b.ref_mode == "write" for b in blocks) else None
-        # the sample after the LAST bank write is discarded by the pipeline: skip that dead tail (result preserving)
+            if self.skip_dead_tail and blocks and all(b.ref_mode == "write" for b in blocks) else None
+        # the 3-D net's walk (_UNetBase._down / _mid_up) with no motion modules, per-frame GroupNorm and one lane: fpg frames per "clip"
+        ps = _Pass(fpg, pk, 1, self._needs_upsample_size(hh, ww, len(self.down_blocks)), None, list(self._down_ops()))
+        ln = _Lane(None, _Skips(self._skip_plan()), B // fpg, trows, cross, PLAIN)      # skips are born inside their concat buffers
         c0 = self.conv_in.weight.shape[0]
-        skips = _Skips(self._skip_plan())                                    # skips are born inside their concat buffers
-        x = ops.conv3x3(x, pk["cin"], c0, bias=pk["cinb"], out=skips.slot(B, hh, ww, c0, dev))
-        for i, blk in enumerate(self.down_blocks):
-            for j, r in enumerate(blk.resnets):
-                H_, W_ = x.shape[1:3]
-                dst = skips.slot(B, H_, W_, r.cout, dev)
-                x = r(x, self._temb(pk, trows, r), fpg * H_ * W_, out=None if blk.has_cross_attention else dst)
-                if blk.has_cross_attention:
-                    x = blk.attentions[j](x, cross, out=dst)
-            if blk.downsamplers is not None:
-                x = blk.downsamplers[0](x, out=skips.slot(B, (x.shape[1] + 1) // 2, (x.shape[2] + 1) // 2, blk.downsamplers[0].c, dev))
-            # MAN after the skips were captured (quirk 10, src/models/unet_2d_mix.py:1272-1289): reads the skip slice, writes a fresh tensor
-            x = self.man_blocks[i](x, motion_at(x.shape[1], x.shape[2]))
-        mb = self.mid_block
-        x = mb.resnets[0](x, self._temb(pk, trows, mb.resnets[0]), fpg * x.shape[1] * x.shape[2])
-        x = mb.attentions[0](x, cross)
-        x = mb.resnets[1](x, self._temb(pk, trows, mb.resnets[1]), fpg * x.shape[1] * x.shape[2], out=skips.hidden_slot())
-        for blk in self.up_blocks:
-            for j, r in enumerate(blk.resnets):
-                x = skips.pop(x)                                             # [hidden | skip]: nothing is copied
-                H_, W_ = x.shape[1:3]
-                last = j == len(blk.resnets) - 1
-                dst = skips.hidden_slot() if len(skips) and not (last and blk.upsamplers is not None) else None
-                x = r(x, self._temb(pk, trows, r), fpg * H_ * W_, out=None if blk.has_cross_attention else dst)
-                if blk.has_cross_attention:
-                    tb = blk.attentions[j].transformer_blocks[0]
-                    if self.skip_dead_tail and tb is last_writer:
-                        tb.stop_after_bank = True
-                        try:
-                            blk.attentions[j](x, cross)
-                        finally:
-                            tb.stop_after_bank = False
-                        return None
-                    x = blk.attentions[j](x, cross, out=dst)
-            if blk.upsamplers is not None:
-                x = blk.upsamplers[0](x, skips.top_hw() if force_size else None, out=skips.hidden_slot())
-        return x
+        ln.x = ops.conv3x3(x, pk["cin"], c0, bias=pk["cinb"], out=ln.skips.slot(B, hh, ww, c0, x.device))
+        # MAN after the skips were captured (quirk 10, src/models/unet_2d_mix.py:1272-1289): reads the skip slice, writes a fresh tensor
+        ln.x = self._down(ps, ln, ps.down_ops, after_block=lambda i, h: self.man_blocks[i](h, motion_at(h.shape[1], h.shape[2])))
+        return self._mid_up(ps, ln, stop_at=last_writer)
 
     skip_dead_tail = False
 

@@ -1,4 +1,4 @@
-"""The two clip-halves of a classifier-free-guidance batch as two kernel queues (UNet3DConditionModel._forward_two_queues).
+"""The two clip-halves of a classifier-free-guidance batch as two kernel queues (UNet3DConditionModel._two_queues).
 
 Behind conv_in and the first resnet the unconditional and the conditional half of the denoising UNet never meet again until the guidance formula
 (reference src/models/unet_3d_mix.py:418-598: per-image GroupNorm, per-row LayerNorm / attention; src/models/mutual_mix_attention.py:173-201: the
